@@ -2,8 +2,8 @@
 """bench.py -- Mcell-steps/s of the Godunov + HLLC fp64 step on the synthetic flat-DEM dam-break (S-DAM).
 
 Contract (see the task statement): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
-N = 1 : BASELINE.json configs[1], 4096 x 4096, one MI355X.  The line also carries a `strict` leg (the exact mode: the
-        reference's bits, the only mode that meets 1e-9 m on every config) and the Manning-array leg.
+N = 1 : BASELINE.json configs[1], 4096 x 4096, one MI355X.  With --full the line also carries a `strict` leg (the exact mode:
+        the reference's bits, the only mode that meets 1e-9 m on every config), the Manning-array leg and the legs below.
 N > 1 : one process per GPU (torch.distributed.run), 1-D row strips with per-iteration ghost rows and an 8-byte MAX, the
         per-iteration loop run by the library itself (hp_strip_step_batch).  BASELINE.json's metric is quoted on the 4096^2
         grid at 1/2/4/8 GPUs and north_star's target is STRONG scaling, so `value` is the strong-scaling leg -- the 4096^2
@@ -11,6 +11,15 @@ N > 1 : one process per GPU (torch.distributed.run), 1-D row strips with per-ite
         runs on its own GPU in the same invocation; the object `weak` is the second leg, the configs' ladder 4096^2 ->
         8192x4096 -> 8192^2 -> 16384x8192 (configs[3] at N = 8; 16,777,216 cells per GPU at every N) with its own
         roofline.  `--scaling weak|strong` runs one leg only (then `value` is that leg's).
+
+A plain run measures the headline only: the strong-scaling leg (N > 1) or the one domain (N = 1), ONE timed run of exactly K
+steps, and the `roofline` priced from it.  `--full` adds everything else the line carries: the strict, Manning-array,
+moving-water, c3_muscl and c5_fp32_rain legs and the CPU baseline (N = 1), the weak and single-domain legs (N > 1, unless
+--scaling says otherwise), and three timed repeats per leg instead of one (--repeats overrides either default).
+`--dump-outputs DIR` writes what the timed run computed in its last step, as its caller would receive it: DIR/state.npy, the cell
+state {Z, Zmax, Qx, Qy} in the run's precision of a fixed, seeded sample of 2^20 cells in cell order (every cell of a smaller
+grid), and DIR/scalars.npy, [time, timestep] in float64.  The inputs are synthesised deterministically (seeded where random):
+the same arguments give the same inputs on every run.
 
 The timed region starts with all inputs resident in HBM.  An untimed, time-based pre-warm (--prewarm-s) settles clocks
 and caches; the state is then put back from a device-side checkpoint (hp_state_restore), W untimed warm-up steps run,
@@ -211,10 +220,38 @@ def variant(args, **kw):
     return argparse.Namespace(**{**vars(args), **kw})
 
 
-def run_leg(args, hp, cols, rows, world, rank, local_rank, math, manning_array=False, repeats=None, last=True, workload=None, force_period=None):
+DUMP_CELLS = 1 << 20             # --dump-outputs: cells sampled from a larger grid (32 MB of fp64 state)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(outdir, runner, cols, rows, world, rank):
+    """--dump-outputs: the state and scalars the timed run leaves its caller (see the module docstring).  The sample is drawn over
+    the whole grid, whatever N; with N > 1 every rank takes the sampled cells of the rows it owns and rank 0 writes them in cell order."""
+    n = cols * rows
+    cells = np.arange(n) if n <= DUMP_CELLS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_CELLS, replace=False))
+    if world == 1:
+        state = runner.domain.download().reshape(-1, 4)[cells]
+    else:
+        lo, hi = runner.own_lo * cols, runner.own_hi * cols
+        mine = cells[(cells >= lo) & (cells < hi)]
+        local = runner.engine.download()[runner.own_lo - runner.local_lo:runner.own_hi - runner.local_lo].reshape(-1, 4)
+        parts = [None] * world
+        runner.dist.all_gather_object(parts, np.ascontiguousarray(local[mine - lo]))     # ranks own ascending row blocks
+        if rank != 0:
+            return
+        state = np.concatenate(parts, axis=0)
+    sc = runner.domain.read_scalars()
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "state.npy"), state)
+    np.save(os.path.join(outdir, "scalars.npy"), np.array([sc["time"], sc["timestep"]], np.float64))
+
+
+def run_leg(args, hp, cols, rows, world, rank, local_rank, math, manning_array=False, repeats=None, last=True, workload=None, force_period=None,
+            dump=None):
     """One timed leg: build this rank's runner for a `cols x rows` grid cut into `world` strips, load the workload, pre-warm,
     then `repeats` x (restore, W warm-up steps, EXACTLY K timed steps between barrier + device sync); median repeat.
-    Returns what rank 0 needs for the line (every rank gets the same timing numbers: max over ranks)."""
+    Returns what rank 0 needs for the line (every rank gets the same timing numbers: max over ranks).  `dump`: a directory for
+    dump_outputs, written after the last timed step."""
     from hipims_mi import synthetic as syn
     workload = workload or args.workload
     scheme = {"godunov": hp.SCHEME_GODUNOV, "muscl": hp.SCHEME_MUSCL_HANCOCK, "inertial": hp.SCHEME_INERTIAL}[args.scheme]
@@ -322,12 +359,14 @@ def run_leg(args, hp, cols, rows, world, rank, local_rank, math, manning_array=F
             # again on the transport every earlier probe used, and the line says so
             runner.close(destroy_group=False)
             leg = run_leg(args, hp, cols, rows, world, rank, local_rank, math, manning_array=manning_array, repeats=repeats, last=last,
-                          workload=workload, force_period=1)
+                          workload=workload, force_period=1, dump=dump)
             leg["exchange_fallback"] = f"two reaches + iteration pairs: {bad} ghost-row cells differed from their owners' after the timed batch; re-run with one reach"
             return leg
         if bad:
             raise SystemExit(f"bench.py --gpus {world}: {bad} ghost-row cells differ from their owners' values after the timed "
                              f"batch of the {cols}x{rows} leg -- the strips did not exchange correctly; no line is printed for a broken run")
+    if dump:
+        dump_outputs(dump, runner, cols, rows, world, rank)
     strip_info = runner.domain.strip_info() if world > 1 and getattr(runner, "loop", "") == "cxx" else None
     leg = dict(cols=cols, rows=rows, world=world, math=math, elapsed=elapsed, runs=runs, k_ms=k_ms, k_n=k_n, sc=sc,
                exchange_period=getattr(runner, "exchange_period", 1),
@@ -420,9 +459,9 @@ def main():
     ap.add_argument("--workload", choices=["s-dam", "s-rain", "s-rough"], default="s-dam",
                     help="s-dam: BASELINE configs[1..3]; s-rain: configs[4] (initially dry terrain + gridded rainfall, dx = 2 m); "
                          "s-rough: SURVEY 8(d)'s wet/dry rough terrain at full size (every tile on the general path; N = 1)")
-    ap.add_argument("--scaling", choices=["both", "weak", "strong"], default="both",
-                    help="N > 1: both (default) = `value` from the strong leg (the metric's 4096^2 grid cut into N strips) and the "
-                         "object `weak` from the configs' ladder (16.8 Mcell per GPU); weak / strong = that leg only")
+    ap.add_argument("--scaling", choices=["both", "weak", "strong"], default=None,
+                    help="N > 1: both (default with --full) = `value` from the strong leg (the metric's 4096^2 grid cut into N strips) and the "
+                         "object `weak` from the configs' ladder (16.8 Mcell per GPU); weak / strong = that leg only (strong: default)")
     ap.add_argument("--exchange-period", type=int, choices=[0, 1, 2], default=0,
                     help="N > 1: iterations per ghost-row exchange (2: two reaches of ghost rows, which lets Godunov FAST strips run iteration "
                          "pairs; 0 = 2 where that is possible, else 1)")
@@ -432,10 +471,18 @@ def main():
     ap.add_argument("--no-moving-leg", action="store_true", help="skip the moving-water leg (S-ROUGH) of the default line")
     ap.add_argument("--no-config-legs", action="store_true", help="skip the c3_muscl / c5_fp32_rain legs of the default line (BASELINE configs[2], [4])")
     ap.add_argument("--no-single-leg", action="store_true", help="N > 1: skip rank 0's single-domain leg (speedup_vs_1gpu_same_run)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of --steps steps; the median is reported (default 1, 3 with --full)")
     ap.add_argument("--prewarm-s", type=float, default=0.4, help="untimed time-based pre-warm (the state is restored afterwards)")
     ap.add_argument("--evolve-steps", type=int, default=0, help="untimed steps after the warm-up: time a developed flood")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other legs, the CPU baseline, three timed repeats (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed run's last state (a seeded sample of 2^20 cells) and scalars to DIR/*.npy")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
@@ -458,22 +505,22 @@ def main():
 
     if world == 1:
         cols, rows = strong_grid
-        main_leg = run_leg(args, hp, cols, rows, 1, 0, local_rank, args.math)
+        main_leg = run_leg(args, hp, cols, rows, 1, 0, local_rank, args.math, dump=args.dump_outputs)
         default_cfg = ((cols, rows) == (4096, 4096) and args.precision == "f64" and args.kernel == "auto"
                        and args.workload == "s-dam" and args.math == "fast")
         manning_leg = strict_leg = None
-        if args.workload == "s-dam" and not args.no_manning_leg:
+        if args.full and args.workload == "s-dam" and not args.no_manning_leg:
             manning_leg = run_leg(args, hp, cols, rows, 1, 0, local_rank, args.math, manning_array=True, repeats=1)
             manning_leg["manning_uniform"] = False
         strict_args = args
-        if args.math == "fast" and not args.no_strict_leg:
+        if args.full and args.math == "fast" and not args.no_strict_leg:
             # (the exact mode chooses between iteration pairs and single iterations by measurement -- the same bits either way -- from
             # a sample of twelve iterations every 128, taken anew after a state restore: at least 24 warm-up steps keep that sample
             # out of a short timed region, where it would stand for 60 % of the steps instead of 9 %)
             strict_args = variant(args, warmup=max(args.warmup, 24))
             strict_leg = run_leg(strict_args, hp, cols, rows, 1, 0, local_rank, "strict", repeats=1)
         c3_legs, c5_leg = {}, None
-        if default_cfg and not args.no_config_legs:
+        if args.full and default_cfg and not args.no_config_legs:
             # BASELINE.json configs[2] and configs[4] on the driver's own line (missing #2): the MUSCL-Hancock kernel on
             # the same grid -- the bench window and a developed flood -- and C5's shape, 8192^2 fp32 with gridded rain fused into the
             # flux kernel (at least 50 warm-up steps: the hydrological gate, one second of model time, opens inside the window)
@@ -484,19 +531,19 @@ def main():
             a5 = variant(args, precision="f32", workload="s-rain", warmup=max(args.warmup, 50))
             c5_leg = (a5, run_leg(a5, hp, 8192, 8192, 1, 0, local_rank, "fast", repeats=1, workload="s-rain"))
         moving_leg = None
-        if args.workload == "s-dam" and not args.no_moving_leg:
+        if args.full and args.workload == "s-dam" and not args.no_moving_leg:
             # the headline window of S-DAM is ~98 % still water; this leg is the same grid, scheme and mode on water that moves
             # everywhere (S-ROUGH: wet/dry rough terrain, every tile live) -- VERDICT r04 item 1
             moving_leg = run_leg(args, hp, cols, rows, 1, 0, local_rank, args.math, repeats=1, workload="s-rough")
         scaling, weak_leg, single_leg = "weak", None, None
     else:
         legs = {"both": ("strong", "weak"), "weak": ("weak",), "strong": ("strong",)}[args.scaling]
-        single = "strong" in legs and not args.no_single_leg
+        single = args.full and "strong" in legs and not args.no_single_leg
         results = {}
         for i, kind in enumerate(legs):
             cols, rows = strong_grid if kind == "strong" else weak_grid
             results[kind] = run_leg(args, hp, cols, rows, world, rank, local_rank, args.math,
-                                    last=(i == len(legs) - 1 and not single))
+                                    last=(i == len(legs) - 1 and not single), dump=(args.dump_outputs if i == 0 else None))
         main_leg = results[legs[0]]
         weak_leg = results.get("weak") if legs[0] == "strong" else None
         scaling = legs[0]
@@ -596,7 +643,7 @@ def main():
             # (the pair kernel's name when launches covered two iterations: hp::godunov_march2<...>)
             attach_pmc(out["roofline"], "godunov_march2<" if out["roofline"]["iterations_per_launch"] == 2 else args.scheme + "_march<false",
                        args.scheme + "4096", args.precision)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             scheme = {"godunov": hp.SCHEME_GODUNOV, "muscl": hp.SCHEME_MUSCL_HANCOCK, "inertial": hp.SCHEME_INERTIAL}[args.scheme]
             out["cpu_baseline"] = cpu_baseline(main_leg["cols"], args.precision, scheme, main_leg["levels"])
         print(json.dumps(out), flush=True)

@@ -160,14 +160,23 @@ def test_cli_fails_loudly_without_a_gpu(tmp_path):
     assert r.returncode != 0 and ("no usable HIP device" in r.stderr or "HP_ERR" in r.stderr or "hip" in r.stderr.lower())
 
 
-REFERENCE_EXAMPLE = "/root/reference/test/newcastle-centre.xml"
+def reference_example(where):
+    """The reference's OWN example model laid out as it ships (newcastle-centre.xml beside newcastle-centre/boundaries/*.csv and
+    newcastle-centre/topography/NewcastleCentreDEM_2m.img), from the untouched copies of its files under tests/golden/."""
+    import shutil
+    src = os.path.join(GOLDEN, "newcastle-centre-example")
+    os.makedirs(os.path.join(where, "newcastle-centre", "topography"))
+    os.makedirs(os.path.join(where, "newcastle-centre", "output"))
+    shutil.copytree(os.path.join(src, "boundaries"), os.path.join(where, "newcastle-centre", "boundaries"))
+    shutil.copy(os.path.join(GOLDEN, "NewcastleCentreDEM_2m.img"), os.path.join(where, "newcastle-centre", "topography"))
+    return shutil.copy(os.path.join(src, "newcastle-centre.xml"), where)
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_EXAMPLE), reason="reference checkout not present (only in the build container)")
 def test_the_reference_example_directory_parses_as_is(tmp_path):
-    """Drop-in check on the reference's OWN model directory, untouched (read-only): its XML, its CSV series and its HFA
-    raster give the same configuration and initial conditions as the fixture directory the other tests build."""
-    ref = frontend.parse_configuration(REFERENCE_EXAMPLE)
+    """Drop-in check on the reference's OWN model directory, untouched: its XML, its CSV series and its HFA raster give the
+    same configuration and initial conditions as the fixture directory the other tests build."""
+    os.makedirs(tmp_path / "ref")
+    ref = frontend.parse_configuration(reference_example(str(tmp_path / "ref")))
     mine = frontend.parse_configuration(make_newcastle(tmp_path))
     assert (ref.duration, ref.output_frequency, ref.precision, ref.scheme, ref.courant, ref.friction, ref.dry_threshold) == \
            (mine.duration, mine.output_frequency, mine.precision, mine.scheme, mine.courant, mine.friction, mine.dry_threshold)

@@ -215,7 +215,7 @@ def test_multi_process_rehearsal_on_one_gpu(scheme, world, tmp_path):
 
 
 def test_bench_multi_rank_branch_rehearsal():
-    """bench.py's N > 1 branch end to end THROUGH ITS OWN LAUNCHER (`python bench.py --gpus 2`, no torchrun around it:
+    """bench.py's N > 1 branch end to end THROUGH ITS OWN LAUNCHER (`python bench.py --gpus 2 --full`, no torchrun around it:
     it starts the two rank processes itself), default time-based pre-warm included (its pass count must be the same on
     both ranks), strip inputs, barrier, max-over-ranks timing, rank-0 JSON line; two processes share the GPU over the
     rehearsal transport; the numbers are meaningless, the line must be well formed.  BASELINE.json's metric is quoted on
@@ -228,7 +228,7 @@ def test_bench_multi_rank_branch_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5",
-                        "--cols", "512", "--rows", "512", "--repeats", "1"], capture_output=True, text=True, timeout=900,
+                        "--cols", "512", "--rows", "512", "--repeats", "1", "--full"], capture_output=True, text=True, timeout=900,
                        env=dict(env, HIPIMS_MI_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -267,6 +267,32 @@ def test_bench_single_leg_options():
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["scaling"] == "weak" and "256x512" in d["config"]["workload"] and "weak" not in d and "speedup_vs_1gpu_same_run" not in d
+
+
+def test_plain_bench_multi_rank_line_and_its_outputs(tmp_path):
+    """A plain `python bench.py --gpus 2` (rehearsal transport) times the strong leg alone, and `--dump-outputs` assembles the
+    two strips' sampled cells on rank 0 in cell order: the same cells, and within FAST's tolerance the same values, as the one
+    domain's dump of the same command at N = 1 (more cells than the sample, so the sampling is exercised too)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    common = ["--steps", "12", "--warmup", "2", "--cols", "1100", "--rows", "1000", "--prewarm-s", "0.05"]
+    lines = {}
+    for n in (2, 1):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dump-outputs", str(tmp_path / f"n{n}")] + common,
+                           capture_output=True, text=True, timeout=900, env=dict(env, HIPIMS_MI_BACKEND="gloo"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[n] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    d = lines[2]
+    assert d["n_gpus"] == 2 and d["scaling"] == "strong" and len(d["repeats_ms_per_step"]) == 1
+    assert "weak" not in d and "speedup_vs_1gpu_same_run" not in d
+    a, b = (np.load(tmp_path / f"n{n}" / "state.npy") for n in (2, 1))
+    sa, sb = (np.load(tmp_path / f"n{n}" / "scalars.npy") for n in (2, 1))
+    assert a.shape == b.shape == (1 << 20, 4) and a.dtype == b.dtype == np.float64
+    assert sa[0] == d["config"]["sim_time_s"] and abs(sa[0] - sb[0]) <= 1e-12 * sb[0]
+    assert np.abs(a - b).max() < 1e-9
 
 
 def test_bench_line_names_the_collective_library_on_the_cxx_loop():

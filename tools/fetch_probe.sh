@@ -4,9 +4,9 @@ cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG=$1; shift
 for a in "$@"; do export "$a"; done
 OUT=gpurun_out/probe_$TAG; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/f -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/f.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/w -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/w.log 2>&1
-python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/b.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/f -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/f.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/w -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/w.log 2>&1
+python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/b.log 2>&1
 python3 - <<PY
 import csv,glob,json
 def avg(d,c):

@@ -4,8 +4,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$1; mkdir -p $OUT
 ARGS="--no-cpu-baseline --no-manning-leg --no-strict-leg"
 for i in $(seq 1 ${2:-2}); do
-  python3 bench.py $ARGS > $OUT/new_$i.json 2> $OUT/new_$i.err
-  HIPIMS_MI_LIB=$PWD/hipims-ocl_amd/lib/variants/libhipims_mi_prev.so python3 bench.py $ARGS > $OUT/prev_$i.json 2> $OUT/prev_$i.err
+  python3 bench.py --full $ARGS > $OUT/new_$i.json 2> $OUT/new_$i.err
+  HIPIMS_MI_LIB=$PWD/hipims-ocl_amd/lib/variants/libhipims_mi_prev.so python3 bench.py --full $ARGS > $OUT/prev_$i.json 2> $OUT/prev_$i.err
 done
 for f in $OUT/*.json; do python3 -c "
 import json

@@ -7,9 +7,9 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$1; mkdir -p $OUT
 ARGS="--no-cpu-baseline --no-manning-leg --no-strict-leg"
 for i in $(seq 1 ${2:-2}); do
-  python3 bench.py $ARGS > $OUT/shipped_$i.json 2> $OUT/shipped_$i.err
-  HP_PAIR_EXACT=1 python3 bench.py $ARGS > $OUT/exact_$i.json 2> $OUT/exact_$i.err
-  HP_PAIR_BDY=0 python3 bench.py $ARGS > $OUT/nobdypairs_$i.json 2> $OUT/nobdypairs_$i.err
+  python3 bench.py --full $ARGS > $OUT/shipped_$i.json 2> $OUT/shipped_$i.err
+  HP_PAIR_EXACT=1 python3 bench.py --full $ARGS > $OUT/exact_$i.json 2> $OUT/exact_$i.err
+  HP_PAIR_BDY=0 python3 bench.py --full $ARGS > $OUT/nobdypairs_$i.json 2> $OUT/nobdypairs_$i.err
 done
 python3 - <<'PY'
 import json,glob,os,sys

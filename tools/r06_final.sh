@@ -5,10 +5,10 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG=${1:-r06z}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; tail -3 $OUT/pytest.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/driver_style_bench_line.json 2> $OUT/driver_style.err
-python bench.py > $OUT/default_bench_line.json 2> $OUT/default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/driver_style_bench_line.json 2> $OUT/driver_style.err
+python bench.py --full > $OUT/default_bench_line.json 2> $OUT/default.err
 Q="--no-cpu-baseline --no-manning-leg --no-moving-leg --no-strict-leg --no-config-legs --steps 200 --warmup 20"
-line() { name=$1; shift; l=$(timeout 900 python3 bench.py $Q "$@" 2>/dev/null | grep '^{' | tail -1); python3 - "$name" "$l" <<'PY'
+line() { name=$1; shift; l=$(timeout 900 python3 bench.py --full $Q "$@" 2>/dev/null | grep '^{' | tail -1); python3 - "$name" "$l" <<'PY'
 import json, sys
 n, l = sys.argv[1:3]
 b = json.loads(l); r = b["roofline"]

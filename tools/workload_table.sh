@@ -1,7 +1,7 @@
 #!/bin/bash
 # One box, every workload/scheme/precision the bench knows: JSON lines into gpurun_out/<name>.jsonl
 OUT=gpurun_out/${1:-workloads}.jsonl; mkdir -p gpurun_out; : > $OUT
-run() { python bench.py --steps 300 --warmup 30 --no-cpu-baseline "$@" | tail -1 >> $OUT; }
+run() { python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline "$@" | tail -1 >> $OUT; }
 run --scheme godunov
 run --scheme godunov --math strict
 run --scheme muscl
