@@ -600,6 +600,8 @@ __device__ __forceinline__ double first_lane(const double v)
 {
 	return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
+// the bits of a value (equal bits: equal values, and -0 / +0 told apart; still_run is fp64 only)
+__device__ __forceinline__ unsigned long long value_bits(const double v) { return (unsigned long long)__double_as_longlong(v); }
 template <typename V> __device__ __forceinline__ V from_east(const V v) { return lane_move<DPP_WAVE_ROL1>(v); }   // lane + 1
 template <typename V> __device__ __forceinline__ V from_west(const V v) { return lane_move<DPP_WAVE_ROR1>(v); }   // lane - 1
 
@@ -1435,14 +1437,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	const bool live0 = LIVE && (act & 1u) != 0, live1 = LIVE && (act & 2u) != 0, live2 = LIVE && (act & 4u) != 0;
 
 	// ---- stage A: source row r -> U1(r), K1's row step with the result kept in registers ----
-	RowRegs<T> rc = load_row(y0 - 1);                                              // the first row stage A produces
-	RowRegs<T> rP = load_row(y0), rQ;
+	RowRegs<T> rc, rP, rQ;                                                         // rc: the row stage A produces next (prime)
 	Side<T> sCa;
 	FaceFlux<T> fSa = {};
 	bool drySa;
 	// Still water (STRICT; K1's skip, see there: a row whose 64 cells hold ONE wet state at rest between two rows that hold the same
 	// state cell for cell comes out of the update as it went in, bit for bit).  Both stages have it -- stage B on the intermediate rows
-	// -- and on such rows a pair is what it is for the FAST flavour: a copy at half the bytes.
+	// -- and on such rows a pair is what it is for the FAST flavour: a copy at half the bytes.  FAST fp64 takes still water in runs at
+	// a tile's start instead (still_run, below): the row-by-row skip costs its loop registers it does not have.
 	constexpr bool STILL = STRICT;
 	constexpr unsigned REST_S = 1, REST_C = 2, EQ_S = 4, PRICED = 16;              // (K1's flags, one word per stage)
 	unsigned stA = 0, stB = 0;
@@ -1452,19 +1454,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 		const T z_first = first_lane(c.z), b_first = first_lane(zb_);
 		return wave_all(c.z == z_first && zb_ == b_first && (c.z - zb_) > vs && !(c.zmax <= T(-9999.0) || c.z == T(-9999.0))) != 0;
 	};
-	{
-		RowRegs<T> rs = load_row(y0 - 2);
-		if (live0) { rs.c = apply(J0(), rs.c, rs.zb, y0 - 2 < 0 ? 0 : y0 - 2); rc.c = apply(J0(), rc.c, rc.zb, y0 - 1); }
-		const Side<T> sS = make_side<STRICT>(rs.c.z, rs.c.qx, rs.c.qy, rs.zb, vs);
-		sCa = make_side<STRICT>(rc.c.z, rc.c.qx, rc.c.qy, rc.zb, vs);
-		drySa = (rs.c.z - rs.zb) < vs;
-		if (STILL) {
-			if (at_rest(rs.c)) stA |= REST_S;
-			if (at_rest(rc.c)) stA |= REST_C;
-			if (stA == (REST_S | REST_C) && same_level(rs.c, rs.zb, rc.c, rc.zb)) stA |= EQ_S;
-		}
-		if (!skip_a) fSa = face_solve<AXIS_Y, STRICT, true, true>(sS, sCa, vs).forR;
-	}
 	auto stage_a = [&](const long r, const RowRegs<T>& rn_in, RowRegs<T>& pre) {
 		pre = load_row(r + 2, r + 2 <= y1 + 1);                                   // nothing beyond the row north of the tile's halo row
 		RowRegs<T> rn = rn_in;
@@ -1674,24 +1663,107 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 		sCb = sN;
 	};
 
-	// prologue: U1(y0 - 1) and U1(y0), and the face between them
-	{
+	// (still_run, below: FAST fp64 without area boundaries; the exact flavour, HZ, goes over its register budget with it)
+	constexpr bool RUNS = !STRICT && !BDY && !HZ && sizeof(T) == 8;
+	// prologue, from row yb on (the tile's first row; RUNS: the row a still run hands back): the south faces of both stages,
+	// U1(yb - 1) and U1(yb), and the face between them -- what a tile that began at yb would have, so the march goes on with
+	// the bits it would have had without the run (results do not depend on where tiles begin)
+	auto prime = [&](const long yb) {
+		stA = 0; stB = 0;
+		if (RUNS) { fSa = {}; fSb = {}; drySb = false; }                           // (as at the tile's start: nothing is carried over a still run)
+		rc = load_row(yb - 1);
+		rP = load_row(yb);
+		{
+			RowRegs<T> rs = load_row(yb - 2);
+			if (live0) { rs.c = apply(J0(), rs.c, rs.zb, yb - 2 < 0 ? 0 : yb - 2); rc.c = apply(J0(), rc.c, rc.zb, yb - 1); }
+			const Side<T> sS = make_side<STRICT>(rs.c.z, rs.c.qx, rs.c.qy, rs.zb, vs);
+			sCa = make_side<STRICT>(rc.c.z, rc.c.qx, rc.c.qy, rc.zb, vs);
+			drySa = (rs.c.z - rs.zb) < vs;
+			if (STILL) {
+				if (at_rest(rs.c)) stA |= REST_S;
+				if (at_rest(rc.c)) stA |= REST_C;
+				if (stA == (REST_S | REST_C) && same_level(rs.c, rs.zb, rc.c, rc.zb)) stA |= EQ_S;
+			}
+			if (!skip_a) fSa = face_solve<AXIS_Y, STRICT, true, true>(sS, sCa, vs).forR;
+		}
 		const T n0 = rc.n;
-		uc = stage_a(y0 - 1, rP, rQ);                                              // (rc = row y0, rP -> rQ holds row y0 + 1)
+		uc = stage_a(yb - 1, rP, rQ);                                              // (rc = row yb, rP -> rQ holds row yb + 1)
 		n_c = n0;
 		sCb = make_side<STRICT>(uc.c.z, uc.c.qx, uc.c.qy, uc.zb, vs);
 		if (STILL && at_rest(uc.c)) stB |= REST_C;
 		const T n1 = rc.n;
-		const RowU1<T> u0 = stage_a(y0, rQ, rP);
-		stage_b(y0 - 1, u0, n1, false);                                            // stage B without an update: the face below row y0 and its dry flag
+		const RowU1<T> u0 = stage_a(yb, rQ, rP);
+		stage_b(yb - 1, u0, n1, false);                                            // stage B without an update: the face below row yb and its dry flag
+	};
+	// Still runs (FAST fp64 without area boundaries, round 7).  A tile whose first rows hold ONE wet state at rest -- the same level
+	// and bed bits in all 64 lanes and in every row, discharge +0, no disabled cell -- is marched by still_run until a row breaks
+	// the run: final row y is source row y with Zmax following Z as long as source rows y - 2 .. y + 2 hold the state (K1's argument,
+	// above: both steps solve every face on one state, the flux differences are x - x = +0, no friction acts on zero discharge).  The
+	// discharge must be +0 bit for bit: next to a +0 neighbour the full march may turn a -0 into +0 (tests/test_gpu_still_pairs.py).
+	// Four rows are loaded at a time -- the bytes in flight the general loop cannot afford -- and the state is priced once.  Returns
+	// the first final row the run does not cover: the general march takes over there (prime), or the tile is done.  (Only at the
+	// tile's start: the row-by-row skip of STRICT, or a vote on every row that could start a run mid-tile, costs this flavour's loop
+	// 14 % more vector instructions and 8-14 spilled registers; an outer loop that goes back and forth between the two spills 140 --
+	// compiler figures, LAB_NOTES R7.1.  In the dam break a window of columns is still for all its rows or for none.)
+	auto still_run = [&]() -> long {
+		auto load_rz = [&](const long yl) {                                        // (rows beyond y1 + 1 are not loaded: they end the run)
+			unsigned vs_ = yl <= y1 + 1 ? voff_state : HP_OOB, vc_ = yl <= y1 + 1 ? voff_scalar : HP_OOB;
+			asm volatile("" : "+v"(vs_), "+v"(vc_));
+			const unsigned k = (unsigned)((yl < 0 ? 0 : (yl > last_row ? last_row : yl)) - row_base);
+			RowRegs<T> q;
+			q.c = buf_load_state(srd_src, vs_, k * row_state, T());
+			q.zb = buf_load_scalar(srd_bed, vc_, k * row_scalar, T());
+			return q;
+		};
+		long y = y0;
+		RowRegs<T> q[4];
+		#pragma unroll
+		for (int j = 0; j < 4; ++j) q[j] = load_rz(y - 2 + j);
+		const T z0 = first_lane(q[0].c.z), b0 = first_lane(q[0].zb), h0 = z0 - b0;
+		if (!(h0 > vs && h0 < T(1e100) && z0 != T(-9999.0))) return y;          // (wave-uniform) a wet, finite state
+		const unsigned long long run_z = value_bits(z0), run_b = value_bits(b0);
+		auto in_run = [&](const RowRegs<T>& q_) {
+			return wave_all(value_bits(q_.c.z) == run_z && value_bits(q_.zb) == run_b && value_bits(q_.c.qx) == 0 && value_bits(q_.c.qy) == 0 &&
+			                !(q_.c.zmax <= T(-9999.0))) != 0;
+		};
+		if (!(in_run(q[0]) && in_run(q[1]) && in_run(q[2]) && in_run(q[3]))) return y;
+		const T spd = cfl_speed<STRICT>(q[2].c.z, q[2].c.zmax, q[2].c.qx, q[2].c.qy, q[2].zb, p.qs);
+		auto put = [&](State4<T> c, const long yy) {
+			if (c.z > c.zmax && c.zmax > T(-9990.0)) c.zmax = c.z;                    // :375-376
+			const unsigned row_k = (unsigned)__builtin_amdgcn_readfirstlane((int)(yy - row_base));
+			buf_store_state(c, srd_dst, out_x ? voff_state : HP_OOB, row_k * row_state);
+			if (TAIL == 2) store_peer(c, yy, out_x);
+			if (CFL_MODE == 1 && out_x && (int)yy >= tm.price_lo && (int)yy < tm.price_hi && spd > vmax) vmax = spd;
+		};
+		State4<T> a = q[2].c, b = q[3].c;                                          // source rows y, y + 1
+		for (;;) {
+			if (y >= y1) return y;
+			#pragma unroll
+			for (int j = 0; j < 4; ++j) q[j] = load_rz(y + 2 + j);
+			if (!in_run(q[0])) return y;
+			put(a, y);
+			if (y + 1 >= y1 || !in_run(q[1])) return y + 1;
+			put(b, y + 1);
+			if (y + 2 >= y1 || !in_run(q[2])) return y + 2;
+			put(q[0].c, y + 2);
+			if (y + 3 >= y1 || !in_run(q[3])) return y + 3;
+			put(q[1].c, y + 3);
+			a = q[2].c; b = q[3].c;
+			y += 4;
+		}
+	};
+
+	const long yb = (RUNS && !skip_a && !skip_b) ? still_run() : y0;              // the still rows at the tile's start, if any
+	if (!RUNS || yb < y1) {
+		prime(yb);
+		// steady state: stage A on row r, stage B on row r - 1
+		long r = yb + 1;
+		for (; r + 1 <= y1; r += 2) {
+			{ const T nn = rc.n; const RowU1<T> u = stage_a(r, rP, rQ); stage_b(r - 1, u, nn, true); }
+			{ const T nn = rc.n; const RowU1<T> u = stage_a(r + 1, rQ, rP); stage_b(r, u, nn, true); }
+		}
+		if (r <= y1) { const T nn = rc.n; const RowU1<T> u = stage_a(r, rP, rQ); stage_b(r - 1, u, nn, true); }
 	}
-	// steady state: stage A on row r, stage B on row r - 1
-	long r = y0 + 1;
-	for (; r + 1 <= y1; r += 2) {
-		{ const T nn = rc.n; const RowU1<T> u = stage_a(r, rP, rQ); stage_b(r - 1, u, nn, true); }
-		{ const T nn = rc.n; const RowU1<T> u = stage_a(r + 1, rQ, rP); stage_b(r, u, nn, true); }
-	}
-	if (r <= y1) { const T nn = rc.n; const RowU1<T> u = stage_a(r, rP, rQ); stage_b(r - 1, u, nn, true); }
 
 	// cells the second step leaves untouched: the primary buffer keeps state k with the first iteration's boundaries (and the
 	// reduction prices it; the next iteration's boundaries act on it in place)
