@@ -175,6 +175,14 @@ struct hp_domain {
 	void*            z_state = nullptr;               // stamp records, one per cell: State4<T> + the number of the pair launch that wrote it (allocated with the first pair)
 	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
 	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while other_stale holds
+	// still records of the FAST fp64 pair kernel (hp_kernels.hpp: StillRec; round 8): two halves of windows x rows records, the last launch's
+	// in half still_rec_half, then two counters (hp_pair_stats).  Valid while no writer of either state buffer has run since that launch
+	// other than such launches themselves (still_rec_forget)
+	void*            still_rec = nullptr;
+	size_t           still_rec_slots = 0;             // records per half
+	int              still_rec_half = 0;
+	bool             still_rec_valid = false;
+	bool             still_rec_last = false;          // the last pair launch wrote records (hp_pair_stats)
 	bool             saved_m1_valid = false;
 	bool             pair_fused_next = false;         // the last pair stored its state with the next iteration's boundaries applied (SLOT_BDY = 1)
 	bool             m1_valid = false;                // area boundaries: cfl_slot[SLOT_M1] prices the primary buffer with the next iteration's boundaries (left by the last pair)
@@ -924,6 +932,30 @@ static int pair_stamps_alloc(hp_domain* d)
 	HIP_TRY(hipMemsetAsync(d->haz_words, 0, 64, d->stream));
 	return HP_OK;
 }
+// Still records (hp_kernels.hpp: StillRec): a tile of a FAST fp64 pair launch whose stencil the launch before recorded as one still state,
+// found as it was left, is skipped.  That holds only while nothing else writes either state buffer (or the bed) between the two launches:
+// every such writer calls still_rec_forget -- single iterations and their FILL, the boundary passes (dispatch_begin; pair_cold_start),
+// repair_other_buffer, uploads of any array, hp_state_restore, a speculative batch's replay, a device pointer handed out (hp_device_ptr),
+// and every pair launch that does not write records itself (run_pair_t).  HP_PAIR_SKIP=0: no records, nothing skipped (A/B runs).
+static bool pair_skip_enabled()
+{
+	static const bool v = !(std::getenv("HP_PAIR_SKIP") && std::atoi(std::getenv("HP_PAIR_SKIP")) == 0);
+	return v;
+}
+static void still_rec_forget(hp_domain* d) { d->still_rec_valid = false; }
+static int still_rec_alloc(hp_domain* d, const int windows)
+{
+	const size_t slots = (size_t)windows * (size_t)d->desc.rows;
+	if (d->still_rec && d->still_rec_slots == slots) return HP_OK;
+	hipFree(d->still_rec);
+	d->still_rec = nullptr;
+	d->still_rec_valid = false;
+	const size_t bytes = (2 * slots + 1) * sizeof(StillRec);              // (+1: the counters of hp_pair_stats)
+	HIP_TRY(hipMalloc(&d->still_rec, bytes));
+	HIP_TRY(hipMemsetAsync(d->still_rec, 0xff, bytes, d->stream));       // the sentinel (rows no launch writes: the edge ring's)
+	d->still_rec_slots = slots;
+	return HP_OK;
+}
 // Area boundaries: the pair kernel needs the primary buffer priced WITH the first iteration's boundaries (slot[SLOT_M1]).  Every BDY
 // pair leaves that figure for its successor; where there is no such predecessor -- the first pair after single iterations, an upload,
 // a new target time -- the first half of iteration k is done the reference's own way: the stand-alone boundary pass on the primary
@@ -931,6 +963,7 @@ static int pair_stamps_alloc(hp_domain* d)
 template <typename T> int pair_cold_start(hp_domain* d)
 {
 	int rc;
+	still_rec_forget(d);
 	if ((rc = apply_boundaries<T>(d, d->state[0])) != HP_OK) return rc;
 	if ((rc = launch_reduce<T>(d, d->state[0], d->own_lo, d->own_hi)) != HP_OK) return rc;
 	hipLaunchKernelGGL((pair_cold_start_words<T>), dim3(1), dim3(1), 0, d->stream, (T*)d->cfl_slot);
@@ -985,6 +1018,16 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	if (aux.gen == 0) aux.gen = ++d->pair_gen;                            // (0 means "no launch")
 	aux.list = (const AreaBdyList<T>*)d->fused_list; aux.fuse_next = bdy && followed ? 1 : 0; aux.in_place = in_place ? 1 : 0;
 	aux.truncated = (d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0 ? 1 : 0;
+	// still records: the instantiations that take still runs on a single domain (FAST fp64, no area boundaries, no stamps) -- this launch
+	// writes the half the launch before did not, and reads that one if nothing has written a state buffer since (still_rec_forget)
+	const bool recs = sizeof(T) == 8 && pair_skip_enabled() && !strip && !bdy && !exact && d->desc.math_mode != HP_MATH_STRICT && rseg2 <= 32;
+	if (recs) {
+		if ((rc = still_rec_alloc(d, tm.nstrips)) != HP_OK) return rc;
+		StillRec* const base = (StillRec*)d->still_rec;
+		aux.still_out = base + (size_t)(d->still_rec_half ^ 1) * d->still_rec_slots;
+		aux.still_in = d->still_rec_valid ? base + (size_t)d->still_rec_half * d->still_rec_slots : nullptr;
+		aux.still_rows = d->desc.rows;
+	}
 	const void* src = d->state[0];
 	void* dst = d->state[1];
 	// flux-kernel timing (hp_kernel_timing): as in step_begin_impl -- a sampled launch here covers two iterations
@@ -1009,6 +1052,8 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	d->pair_fused_next = bdy && followed;
 	d->m1_valid = bdy;
 	HIP_TRY(hipGetLastError());
+	if (recs) d->still_rec_half ^= 1;
+	d->still_rec_valid = recs; d->still_rec_last = recs;
 	if (sample) { HIP_TRY(hipEventRecord(d->timing_events[d->timing_used].second, d->stream)); d->timing_used++; }
 	// the pass wrote state k + 2 into the other buffer: that buffer IS the primary one from here on (two single iterations would
 	// have left the newest state in the primary buffer; the two buffers' edge rings are equal -- pair_eligible -- and so are their maxima)
@@ -1038,6 +1083,7 @@ static int run_pair(hp_domain* d, const bool strip = false, const bool followed 
 static int repair_other_buffer(hp_domain* d)
 {
 	if (!d->other_stale) return HP_OK;
+	still_rec_forget(d);
 	// (the edge rings of the two buffers are equal whenever pairs have run: pair_eligible, hp_domain_upload_rows)
 	HIP_TRY(hipMemcpyAsync(d->state[d->use_alt ^ 1], d->state[d->use_alt], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
 	if (d->z_state) {                                                     // ... except where the last pair launch stamped a different value (PairAux)
@@ -1055,6 +1101,7 @@ static int repair_other_buffer(hp_domain* d)
 
 int dispatch_begin(hp_domain* d)
 {
+	still_rec_forget(d);                                                  // (a single iteration writes the other buffer, its boundaries the current one)
 	// after iteration pairs the non-current buffer is out of date; K1 brings it up to date by itself (its FILL flag: every cell of the
 	// launch's rows is stored), any other kernel gets the device copy first
 	static const bool fill_enabled = !(std::getenv("HP_FILL_AFTER_PAIRS") && std::atoi(std::getenv("HP_FILL_AFTER_PAIRS")) == 0);
@@ -1539,7 +1586,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->state[0]); hipFree(d->state[1]); hipFree(d->bed); hipFree(d->manning);
 	hipFree(d->scalars); hipFree(d->cfl_slot);
 	hipFree(d->saved_state); hipFree(d->saved_scalars); hipFree(d->fused_list); hipFree(d->tail_words);
-	hipFree(d->z_state); hipFree(d->haz_words);
+	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
@@ -1560,6 +1607,7 @@ int hp_domain_upload(hp_domain_t* d, int which, const void* host, size_t bytes)
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	still_rec_forget(d);                                                  // (state, bed or Manning: the records describe the old ones)
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
 	if (d->in_step) return fail(HP_ERR_STATE, "upload between hp_step_begin and hp_step_end");
 	switch (which) {
@@ -1642,6 +1690,7 @@ int hp_state_restore(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_restore between hp_step_begin and hp_step_end");
 	if (!d->saved_valid) return fail(HP_ERR_STATE, "hp_state_restore without a saved state");
+	still_rec_forget(d);
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// both ping-pong buffers return to what EACH of them held (rollbackSimulation writes the saved next-source state into both,
@@ -1700,6 +1749,7 @@ int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	still_rec_forget(d);
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
 	if (row0 < 0 || nrows < 0 || row0 + nrows > d->desc.rows) return fail(HP_ERR_INVALID, "row range out of bounds");
 	const size_t per_row = (size_t)d->desc.cols * d->esize * 4;
@@ -2062,6 +2112,7 @@ int spec_resolve(hp_domain* d)
 	d->spec_replays++;
 	log_line(HP_LOG_INFORMATION, "a speculative STRICT batch of " + std::to_string(n) + " iterations is re-run with the plain divisions");
 	const size_t bytes = d->cells * 4 * d->esize, sc_bytes = sizeof(Scalars<double>);
+	still_rec_forget(d);
 	HIP_TRY(hipMemcpyAsync(d->state[0], d->spec_state, bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->state[1], (char*)d->spec_state + bytes, bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->scalars, d->spec_scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
@@ -2200,6 +2251,7 @@ int hp_device_ptr(hp_domain_t* d, int which, void** ptr)
 {
 	if (!d || !ptr) return fail(HP_ERR_INVALID, "null argument");
 	d->fork_is_advance = false;          // the caller may queue work on these buffers behind the last advance_time
+	if (which == HP_PTR_STATE_NEXT_SRC || which == HP_PTR_STATE_OTHER || which == HP_PTR_BED) still_rec_forget(d);   // ... or write into them
 	switch (which) {
 	case HP_PTR_STATE_NEXT_SRC: *ptr = d->state[d->use_alt]; return HP_OK;
 	case HP_PTR_STATE_OTHER:    *ptr = d->state[d->use_alt ^ 1]; return HP_OK;
@@ -2885,6 +2937,17 @@ int hp_pair_stats(hp_domain_t* d, uint64_t out[12])
 	out[4] = d->tune_samples; out[5] = d->tune_switches; out[6] = d->tune_prefer_pairs ? 1 : 0;
 	out[7] = d->tune_single_ms > 0.f ? (uint64_t)(1000.0 * d->tune_pair_ms / d->tune_single_ms) : 0;
 	out[8] = out[9] = out[10] = out[11] = 0;
+	if (d->still_rec && d->still_rec_last) {                              // (counted on the device, as the stamps below)
+		const StillRec* half = (const StillRec*)d->still_rec + (size_t)d->still_rec_half * d->still_rec_slots;
+		unsigned long long* counts = (unsigned long long*)((StillRec*)d->still_rec + 2 * d->still_rec_slots);
+		HIP_TRY(hipMemsetAsync(counts, 0, 16, d->stream));
+		hipLaunchKernelGGL(still_rec_count, dim3(256), dim3(256), 0, d->stream, half, d->still_rec_slots, counts);
+		HIP_TRY(hipGetLastError());
+		unsigned long long host_counts[2] = {0, 0};
+		HIP_TRY(hipMemcpyAsync(host_counts, counts, sizeof host_counts, hipMemcpyDeviceToHost, d->stream));
+		HIP_TRY(hipStreamSynchronize(d->stream));
+		out[9] = host_counts[0]; out[10] = host_counts[1];
+	}
 	if (d->haz_words) {
 		unsigned long long used = 0;
 		HIP_TRY(hipMemcpy(&used, d->haz_words + 2, sizeof used, hipMemcpyDeviceToHost));

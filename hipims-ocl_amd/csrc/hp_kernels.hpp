@@ -728,6 +728,13 @@ template <typename T> __device__ __forceinline__ State4<T> stamp_state(const Sta
 	State4<T> c; c.z = v[0]; c.zmax = v[1]; c.qx = v[2]; c.qy = v[3];
 	return c;
 }
+// Still records (round 8; FAST fp64 single domains: godunov_march2 without area boundaries or stamps, TAIL 1).  One record per row of a
+// window (a wave's 60 updated columns), rec[window * rows + row], written for every updated row by every launch of that instantiation:
+// the row's still state -- level and bed bits -- where the launch stored the row as it found it (a still run that raised no Zmax, or a
+// skipped tile), the sentinel (all-ones level bits: no wet, finite level has them) everywhere else.  `tag` tells the two kinds apart for
+// hp_pair_stats (STILL_TAG_*); the vote of the next launch reads the first 16 bytes only.
+struct StillRec { unsigned long long z, b; unsigned tag, pad[3]; };
+constexpr unsigned STILL_TAG_RUN = 1, STILL_TAG_SKIP = 2;
 template <typename T> struct PairAux {
 	StampBufs<T>          stamps;      // rec == nullptr: no stamps (nothing to look up, nothing written down).  (By value: kernel arguments are
 	                                   // uniform by construction -- loaded through a pointer the addresses came back as per-lane values and every
@@ -737,6 +744,11 @@ template <typename T> struct PairAux {
 	int                   fuse_next;   // (BDY) another iteration of the same batch follows the pair: store the state with ITS boundaries applied
 	int                   in_place;    // (BDY) the first iteration's boundaries are in the source buffer already (the launch before stored them / the stand-alone pass ran)
 	int                   truncated;   // HP_QUIRK_BDY_TRUNCATED
+	// (still records, above) this launch's, and the launch before's -- nullptr unless that launch wrote them and nothing has written either
+	// state buffer since (hp_engine.hip: still_rec_valid); still_rows: a window's stride (the domain's rows)
+	StillRec*             still_out;
+	const StillRec*       still_in;
+	long                  still_rows;
 };
 
 // FUSED (round 3): the instantiation a domain with fusable area boundaries runs.  The reference applies rain / loss IN PLACE
@@ -1409,6 +1421,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	T vmax = T(0), vmax1 = T(0);
 	unsigned stale_rows = 0;                                                       // bit i: row y0 + i of this lane keeps state k (quirk Q3 at the second step); tiles are at most 32 rows
 
+	// ---- still records (StillRec above; round 8) ----
+	constexpr bool RECS = !STRICT && !BDY && !HZ && TAIL == 1 && sizeof(T) == 8;
+	unsigned long long still_kz = 0, still_kb = 0;                                 // the still state of the tile's marked rows (wave-uniform)
+	unsigned still_marks = 0;                                                      // bit i: row y0 + i was stored as it was found, in that state
+	// this launch's records of rows [y0, y1): lane i writes row y0 + i (tiles are at most 32 rows, hp_engine.hip: HP_MARCH2_RSEG)
+	auto write_recs = [&](const unsigned tag) {
+		if (!RECS || aux.still_out == nullptr) return;
+		const __amdgpu_buffer_rsrc_t srd = make_srd(aux.still_out + (size_t)strip * aux.still_rows, (size_t)aux.still_rows * sizeof(StillRec));
+		const bool m = lane < 32 && ((still_marks >> (unsigned)lane) & 1u) != 0;
+		hp_u32x4 a;
+		a.x = m ? (unsigned)still_kz : ~0u; a.y = m ? (unsigned)(still_kz >> 32) : ~0u;
+		a.z = m ? (unsigned)still_kb : ~0u; a.w = m ? (unsigned)(still_kb >> 32) : ~0u;
+		unsigned voff = lane < y1 - y0 ? (unsigned)((y0 + lane) * (long)sizeof(StillRec)) : HP_OOB;
+		asm volatile("" : "+v"(voff));
+		store_operands_own(a);
+		__builtin_amdgcn_raw_buffer_store_b128(a, srd, (int)voff, 0, 0);
+		__builtin_amdgcn_raw_buffer_store_b32(m ? tag : 0u, srd, (int)voff + 16, 0, 0);
+		store_fence(a, voff, 0u);
+	};
+	// Is the tile's result known?  The records of the launch before (it read this launch's destination and wrote its source) say, for rows
+	// y0 - 2 .. y1 + 1 of this window and of the windows either side -- every cell this tile's stencil reads -- that the row holds ONE
+	// still state s (wet, finite, discharge +0, Zmax neither raised nor disabled) and that the launch found the row in s in the buffer this
+	// launch writes.  Then this launch's source is s on the whole stencil, still_run would cover every row of the tile and store its source
+	// row as it is, and the destination holds those bits already: nothing to load, nothing to store.  Tiles next to the edge ring (whose
+	// rows and columns no launch writes) are never skipped.
+	auto tile_known = [&]() -> bool {
+		const long xw = strip * MARCH2_COLS - 1;                                   // lane 0's column
+		if (xw < 1 || xw + 63 > p.cols - 2 || y0 - 2 < 1 || y1 + 1 > last_row - 1 || y1 - y0 > 32) return false;
+		const int nr = (int)(y1 - y0) + 4, n = 3 * nr;                             // entries: window strip - 1 + w, row y0 - 2 + r  (<= 108)
+		const __amdgpu_buffer_rsrc_t srd = make_srd(aux.still_in + (size_t)(strip - 1) * aux.still_rows, (size_t)3 * aux.still_rows * sizeof(StillRec));
+		auto voff = [&](const int i) {
+			const int w = i < nr ? 0 : (i < 2 * nr ? 1 : 2);
+			return i < n ? (unsigned)(((long)w * aux.still_rows + y0 - 2 + (i - w * nr)) * (long)sizeof(StillRec)) : HP_OOB;
+		};
+		const hp_u32x4 e0 = __builtin_amdgcn_raw_buffer_load_b128(srd, (int)voff(lane), 0, 0);
+		const hp_u32x4 e1 = __builtin_amdgcn_raw_buffer_load_b128(srd, (int)voff(lane + 64), 0, 0);
+		const unsigned k0 = __builtin_amdgcn_readfirstlane(e0.x), k1 = __builtin_amdgcn_readfirstlane(e0.y);
+		const unsigned k2 = __builtin_amdgcn_readfirstlane(e0.z), k3 = __builtin_amdgcn_readfirstlane(e0.w);
+		if (k0 == ~0u && k1 == ~0u) return false;                                  // (wave-uniform) the sentinel
+		auto same = [&](const hp_u32x4& e) { return e.x == k0 && e.y == k1 && e.z == k2 && e.w == k3; };
+		if (!wave_all((lane >= n || same(e0)) && (lane + 64 >= n || same(e1)))) return false;
+		still_kz = ((unsigned long long)k1 << 32) | k0;
+		still_kb = ((unsigned long long)k3 << 32) | k2;
+		return true;
+	};
+
 	// The march, in two builds of the same statements: LIVE carries the boundary applications (a launch in which the hydrological
 	// gate opens at one of its three moments), !LIVE is the kernel as it is without boundaries -- which is what a BDY launch runs on
 	// all the iterations in between (the gate opens once per second of model time).
@@ -1728,7 +1786,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 		};
 		if (!(in_run(q[0]) && in_run(q[1]) && in_run(q[2]) && in_run(q[3]))) return y;
 		const T spd = cfl_speed<STRICT>(q[2].c.z, q[2].c.zmax, q[2].c.qx, q[2].c.qy, q[2].zb, p.qs);
+		still_kz = run_z; still_kb = run_b;
 		auto put = [&](State4<T> c, const long yy) {
+			// (the record: the row leaves as it came -- no Zmax raised -- and prices as s does: no NaN Zmax, which cfl_speed reads as disabled)
+			if (RECS && !wave_any(!(c.zmax > T(-9999.0)) || (c.z > c.zmax && c.zmax > T(-9990.0)))) still_marks |= 1u << (unsigned)(yy - y0);
 			if (c.z > c.zmax && c.zmax > T(-9990.0)) c.zmax = c.z;                    // :375-376
 			const unsigned row_k = (unsigned)__builtin_amdgcn_readfirstlane((int)(yy - row_base));
 			buf_store_state(c, srd_dst, out_x ? voff_state : HP_OOB, row_k * row_state);
@@ -1754,6 +1815,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	};
 
 	const long yb = (RUNS && !skip_a && !skip_b) ? still_run() : y0;              // the still rows at the tile's start, if any
+	write_recs(STILL_TAG_RUN);                                                     // (RECS; before the march: nothing of it lives into the loop)
 	if (!RUNS || yb < y1) {
 		prime(yb);
 		// steady state: stage A on row r, stage B on row r - 1
@@ -1793,9 +1855,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	};   // march
 
 	auto raise_word = [&]() { if (hz_on && wave_any(stamped) && lane == 0) aux.stamps.haz[aux.gen & 1u] = (unsigned long long)aux.gen; };
+	if (RECS && aux.still_in != nullptr && !skip_a && !skip_b && tile_known()) {
+		// (round 8) the tile is skipped: its records say so again for the launch after this one, and the state prices as still_run would
+		// price it -- one speed in every updated lane, if any of the tile's rows is priced at all
+		still_marks = ~0u;
+		write_recs(STILL_TAG_SKIP);
+		if (CFL_MODE == 1 && out_x && (int)y1 > tm.price_lo && (int)y0 < tm.price_hi)
+			vmax = cfl_speed<STRICT>(T(__longlong_as_double((long long)still_kz)), T(0), T(0), T(0), T(__longlong_as_double((long long)still_kb)), p.qs);
+		vmax1 = vmax;
+	} else {
 	if (BDY && act != 0) { if (hz_any) march(std::true_type(), std::true_type()); else march(std::true_type(), std::false_type()); }
 	else                 { if (hz_any) march(std::false_type(), std::true_type()); else march(std::false_type(), std::false_type()); }
 	raise_word();
+	}
 
 	if (CFL_MODE != 0) {
 		if (blockIdx.x == 0 && wave == 0) { const T e = *edge_max; if (e > vmax) vmax = e; if (e > vmax1) vmax1 = e; }
@@ -1831,6 +1903,17 @@ __global__ __launch_bounds__(256) void stamps_count(const StampBufs<T> b, const 
 	}
 	for (int off = 32; off > 0; off >>= 1) { last += __shfl_down(last, off); any += __shfl_down(any, off); }
 	if ((threadIdx.x & 63) == 0 && (last | any)) { atomicAdd(counts, last); atomicAdd(counts + 1, any); }
+}
+// hp_pair_stats: window rows the last pair launch skipped (its records tagged STILL_TAG_SKIP) and window rows it recorded as found (either tag)
+__global__ __launch_bounds__(256) void still_rec_count(const StillRec* __restrict__ rec, const size_t n, unsigned long long* counts)
+{
+	unsigned long long skipped = 0, still = 0;
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+		const unsigned tag = rec[i].tag;
+		skipped += (tag == STILL_TAG_SKIP); still += (tag == STILL_TAG_SKIP || tag == STILL_TAG_RUN);
+	}
+	for (int off = 32; off > 0; off >>= 1) { skipped += __shfl_down(skipped, off); still += __shfl_down(still, off); }
+	if ((threadIdx.x & 63) == 0 && (skipped | still)) { atomicAdd(counts, skipped); atomicAdd(counts + 1, still); }
 }
 
 // Cold start of iteration pairs on a domain with area boundaries (hp_engine.hip: pair_cold_start): the stand-alone boundary pass and the

@@ -353,6 +353,7 @@ int hp_kernel_timing_overhead(hp_domain_t* d, double* overhead_ms);
  *   HP_TWO_STEP=0 / 1    pairs off / on wherever eligible (default: by grid size; STRICT: by the engine's own measurement, the two being
  *                        the same bits)                    HP_PAIR_EXACT=0 / 1   the exact flavour nowhere / everywhere
  *   HP_PAIR_BDY=0        domains with area boundaries keep single iterations      HP_PAIR_STRICT=0   so does STRICT arithmetic
+ *   HP_PAIR_SKIP=0       FAST fp64 pairs keep no still records and skip no tiles (the same bits; A/B runs)
  * hp_launch_counts and hp_pair_stats show what ran. */
 /* How many whole-domain flux launches the domain has queued since it was created, and how many of them carried their own tail
  * block (reduction + time advance inside the flux launch: an iteration is then ONE launch; otherwise the flux launch is followed
@@ -366,7 +367,10 @@ int hp_launch_counts(hp_domain_t* d, uint64_t* flux_launches, uint64_t* with_tai
  * pairs and single iterations (the same bits; chosen by measurement, hp_engine.hip: tuner_poll): out[4] samples taken, out[5] changes
  * of mind, out[6] 1 if pairs are the current choice, out[7] the last sample's pair time over its two single iterations' time, x 1000;
  * out[8] (exact flavour) stale values taken from a stamp that DIFFERED from the cell's current state -- the cells the flavour without
- * stamps would have got wrong on this run (0: it would have left the same bits); out[9..11] reserved. */
+ * stamps would have got wrong on this run (0: it would have left the same bits); FAST fp64 single domains (the pair kernel's still
+ * records; HP_PAIR_SKIP=0 switches them off): out[9] window rows (60 columns each) the LAST pair launch skipped -- found in one
+ * still state on their whole stencil by the launch before, neither loaded nor stored -- and out[10] window rows it recorded as
+ * still (skipped, or stored as found by a still run; its updated rows x ceil((cols - 2) / 60) in all); out[11] reserved. */
 int hp_pair_stats(hp_domain_t* d, uint64_t out[12]);
 
 #ifdef __cplusplus
