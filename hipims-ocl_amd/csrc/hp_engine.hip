@@ -5,6 +5,7 @@
 // the reference's per-device command queue, stream order for its explicit queueBarrier() calls.
 #include "../../include/hipims_mi.h"
 #include "hp_kernels.hpp"
+#include "hp_output.hpp"
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 #include <dlfcn.h>
@@ -211,6 +212,11 @@ struct hp_domain {
 	void*            spec_scalars = nullptr;          // ... Scalars<T> + the slot block
 	struct { int use_alt, adv_fresh; bool need_full_reduce, edge_dirty; long ghost_valid; uint64_t cells_calculated, iterations; } spec_host;
 	uint64_t         spec_batches = 0, spec_replays = 0;
+	// the output stage (hp_output.hpp; hp_domain_derive / hp_domain_stats): allocated on first use
+	void*            out_scratch = nullptr;           // rasters of one block of rows, value after value (at most OUT_SCRATCH_CAP bytes)
+	size_t           out_scratch_bytes = 0;
+	void*            out_stats = nullptr;             // STATS_MAX_BLOCKS block partials + the folded result
+	void*            out_stats_host = nullptr;        // pinned: the folded result
 };
 
 namespace {
@@ -1211,6 +1217,44 @@ int check_domain(hp_domain* d)
 
 } // namespace
 
+// ---- the output stage on the device (hp_output.hpp) ----
+namespace {
+
+static_assert(OUT_VALUES == HP_OUT_COUNT && OUT_FROUDE == HP_OUT_FROUDE && OUT_DEPTH == HP_OUT_DEPTH, "hp_output.hpp and hipims_mi.h disagree");
+static_assert(sizeof(hp_domain_stats_t) == 64, "hp_domain_stats_t layout");
+
+// Cap of the raster scratch.  A request that needs more is worked through in blocks of rows; the kernel of a block runs in
+// well under a hundredth of the time its rasters take to cross the host link, so blocks are queued one after the other on the
+// domain's stream and nothing would be won by overlapping them.
+constexpr size_t OUT_SCRATCH_CAP = (size_t)256 << 20;
+
+template <typename T, typename O>
+int derive_blocks(hp_domain* d, const int* values, const int count, void* const* rasters, const int64_t row0, const int64_t nrows,
+                  const int64_t block_rows)
+{
+	const size_t cols = (size_t)d->desc.cols;
+	const State4<T>* state = (const State4<T>*)d->state[d->use_alt];      // what hp_domain_download(HP_ARRAY_STATE) reads
+	for (int64_t r = 0; r < nrows; r += block_rows) {
+		const int64_t rows_now = std::min<int64_t>(block_rows, nrows - r);
+		const size_t n = (size_t)rows_now * cols;
+		DeriveTargets t = {};
+		for (int k = 0; k < count; ++k) {
+			t.raster[values[k]] = (char*)d->out_scratch + (size_t)k * n * sizeof(O);
+			t.mask |= 1u << values[k];
+		}
+		const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
+		hipLaunchKernelGGL((derive_rasters<T, O>), dim3(blocks), dim3(256), 0, d->stream, state, (const T*)d->bed,
+		                   (size_t)(row0 + r) * cols, n, d->desc.dx, t);
+		HIP_TRY(hipGetLastError());
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)r * cols * sizeof(O), t.raster[values[k]], n * sizeof(O),
+			                       hipMemcpyDeviceToHost, d->stream));
+	}
+	return HP_OK;
+}
+
+} // namespace
+
 // =================================================================================================
 extern "C" {
 
@@ -1589,6 +1633,8 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
+	hipFree(d->out_scratch); hipFree(d->out_stats);
+	if (d->out_stats_host) hipHostFree(d->out_stats_host);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1741,6 +1787,101 @@ int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int6
 	}
 	HIP_TRY(hipMemcpyAsync(host, (const char*)base + (size_t)row0 * per_row, (size_t)nrows * per_row,
 	                       hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+// ---- the output stage on the device (hp_output.hpp: derive_blocks above) ----
+int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
+{
+	// argument checks first: none of them touches the device, and those that do not need the domain come before it
+	if (count < 1 || count > HP_OUT_COUNT) return fail(HP_ERR_INVALID, "hp_domain_derive: count outside 1..HP_OUT_COUNT");
+	if (!values || !rasters) return fail(HP_ERR_INVALID, "hp_domain_derive: values / rasters == NULL");
+	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, "hp_domain_derive: element_bytes must be 4 or 8");
+	unsigned seen = 0;
+	for (int k = 0; k < count; ++k) {
+		if (values[k] < 0 || values[k] >= HP_OUT_COUNT) return fail(HP_ERR_INVALID, "hp_domain_derive: unknown value " + std::to_string(values[k]));
+		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, "hp_domain_derive: value " + std::to_string(values[k]) + " listed twice");
+		seen |= 1u << values[k];
+		if (!rasters[k]) return fail(HP_ERR_INVALID, "hp_domain_derive: rasters[" + std::to_string(k) + "] == NULL");
+	}
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
+	if (nrows == 0) return HP_OK;
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	const size_t row_bytes = (size_t)d->desc.cols * (size_t)count * (size_t)element_bytes;      // of all requested rasters together
+	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
+	const size_t need = (size_t)block_rows * row_bytes;
+	if (need > d->out_scratch_bytes) {
+		// the new block first: if it cannot be had, the smaller one that served so far stays
+		void* grown = nullptr;
+		const hipError_t e = hipMalloc(&grown, need);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();                                      // (the launches of later steps ask for the last error: this one is dealt with here)
+			return fail(HP_ERR_HIP, "hp_domain_derive: cannot allocate " + std::to_string(need) + " bytes of raster scratch: " + hipGetErrorString(e));
+		}
+		if (d->out_scratch) {
+			hipError_t e2 = hipStreamSynchronize(d->stream);              // (an earlier call's copies may still be reading the old block)
+			if (e2 == hipSuccess) e2 = hipFree(d->out_scratch);
+			if (e2 != hipSuccess) { hipFree(grown); return fail(HP_ERR_HIP, std::string("hp_domain_derive: releasing the raster scratch: ") + hipGetErrorString(e2)); }
+		}
+		d->out_scratch = grown;
+		d->out_scratch_bytes = need;
+	}
+	if (d->desc.precision == 8)
+		return element_bytes == 8 ? derive_blocks<double, double>(d, values, count, rasters, row0, nrows, block_rows)
+		                          : derive_blocks<double, float>(d, values, count, rasters, row0, nrows, block_rows);
+	return element_bytes == 8 ? derive_blocks<float, double>(d, values, count, rasters, row0, nrows, block_rows)
+	                          : derive_blocks<float, float>(d, values, count, rasters, row0, nrows, block_rows);
+}
+
+int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats_t* out)
+{
+	if (!out) return fail(HP_ERR_INVALID, "hp_domain_stats: out == NULL");
+	if (out->struct_size != sizeof(hp_domain_stats_t)) return fail(HP_ERR_INVALID, "hp_domain_stats_t size mismatch (ABI)");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
+	out->reserved = 0;
+	out->cells = out->cells_wet = 0;
+	out->volume = out->max_depth = out->max_speed = 0.0;
+	out->max_depth_cell = out->max_speed_cell = UINT64_MAX;
+	if (nrows == 0) return HP_OK;
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->out_stats) {
+		const hipError_t e = hipMalloc(&d->out_stats, (STATS_MAX_BLOCKS + 1) * sizeof(StatsPart));
+		if (e != hipSuccess) {
+			d->out_stats = nullptr;
+			(void)hipGetLastError();
+			return fail(HP_ERR_HIP, std::string("hp_domain_stats: cannot allocate the block partials: ") + hipGetErrorString(e));
+		}
+	}
+	if (!d->out_stats_host) {
+		const hipError_t e = hipHostMalloc(&d->out_stats_host, sizeof(StatsPart), hipHostMallocDefault);
+		if (e != hipSuccess) {
+			d->out_stats_host = nullptr;
+			(void)hipGetLastError();
+			return fail(HP_ERR_HIP, std::string("hp_domain_stats: cannot allocate pinned memory: ") + hipGetErrorString(e));
+		}
+	}
+	const size_t cols = (size_t)d->desc.cols, n = (size_t)nrows * cols, first = (size_t)row0 * cols;
+	// the launch shape is a function of the range alone: the same range is always summed in the same order
+	const int blocks = (int)std::min<size_t>((n + 255) / 256, STATS_MAX_BLOCKS);
+	StatsPart* partial = (StatsPart*)d->out_stats;
+	if (d->desc.precision == 8)
+		hipLaunchKernelGGL((domain_stats<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed, first, n, partial);
+	else
+		hipLaunchKernelGGL((domain_stats<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed, first, n, partial);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(domain_stats_fold, dim3(1), dim3(256), 0, d->stream, partial, blocks, partial + STATS_MAX_BLOCKS);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(d->out_stats_host, partial + STATS_MAX_BLOCKS, sizeof(StatsPart), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	const StatsPart& s = *(const StatsPart*)d->out_stats_host;
+	out->cells = s.cells; out->cells_wet = s.wet;
+	out->volume = d->desc.dx * d->desc.dx * s.sum;
+	if (s.depth_cell != ~0ull) { out->max_depth = s.max_depth; out->max_depth_cell = s.depth_cell; }
+	if (s.speed_cell != ~0ull) { out->max_speed = s.max_speed; out->max_speed_cell = s.speed_cell; }
 	return HP_OK;
 }
 

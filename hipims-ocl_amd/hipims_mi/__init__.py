@@ -26,10 +26,17 @@ GRIDDED_RAIN_INTENSITY, GRIDDED_RAIN_ACCUMUL, GRIDDED_MASS_FLUX = 0, 1, 2
 DEPTH_IGNORE, DEPTH_IS_FSL, DEPTH_IS_DEPTH, DEPTH_IS_CRITICAL = 0, 1, 2, 3
 DISCHARGE_IGNORE, DISCHARGE_IS_DISCHARGE, DISCHARGE_IS_VELOCITY, DISCHARGE_IS_VOLUME = 0, 1, 2, 3
 PTR_STATE_NEXT_SRC, PTR_STATE_OTHER, PTR_BED, PTR_MANNING, PTR_CFL_MAX, PTR_SCALARS = range(6)
+(OUT_DEPTH, OUT_MAXDEPTH, OUT_FSL, OUT_MAXFSL, OUT_DISCHARGE_X, OUT_DISCHARGE_Y, OUT_VELOCITY_X, OUT_VELOCITY_Y, OUT_FROUDE,
+ OUT_COUNT) = range(10)
+# the front end's value names (frontend.data_value_code) -> HP_OUT_*
+OUT_CODES = {"depth": OUT_DEPTH, "maxdepth": OUT_MAXDEPTH, "fsl": OUT_FSL, "maxfsl": OUT_MAXFSL, "dischargex": OUT_DISCHARGE_X,
+             "dischargey": OUT_DISCHARGE_Y, "velocityx": OUT_VELOCITY_X, "velocityy": OUT_VELOCITY_Y, "froude": OUT_FROUDE}
+NO_CELL = 2 ** 64 - 1          # hp_domain_stats_t: "no such cell"
 
 EXPORTS = [
     "hp_abi_version", "hp_device_count", "hp_device_info", "hp_last_error", "hp_set_log_sink", "hp_domain_desc_default",
     "hp_domain_create", "hp_domain_destroy", "hp_domain_upload", "hp_domain_download", "hp_domain_upload_rows", "hp_state_save", "hp_state_restore",
+    "hp_domain_derive", "hp_domain_stats",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -88,6 +95,12 @@ class ScalarsOut(C.Structure):
                 ("batch_skipped", C.c_uint32), ("cells_calculated", C.c_uint64), ("iterations", C.c_uint64)]
 
 
+class DomainStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("cells", C.c_uint64), ("cells_wet", C.c_uint64),
+                ("volume", C.c_double), ("max_depth", C.c_double), ("max_speed", C.c_double),
+                ("max_depth_cell", C.c_uint64), ("max_speed_cell", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -120,6 +133,9 @@ def load_library(path: str | None = None):
     lib.hp_domain_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     lib.hp_domain_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64]
     lib.hp_domain_upload_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+    if hasattr(lib, "hp_domain_derive"):                # (absent from older builds loaded through HIPIMS_MI_LIB for A/B runs: calling it there raises)
+        lib.hp_domain_derive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
+        lib.hp_domain_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DomainStats)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -296,6 +312,49 @@ class Domain:
                "hp_domain_download")
         self.sync()
         return out
+
+    # ---- the output stage on the device (hp_domain_derive / hp_domain_stats) ----
+    def derive(self, values, dtype=np.float64, row0=0, nrows=None):
+        """Output rasters derived on the device, without a state download: {name: array[nrows, cols]} for the front end's
+        value names (frontend.data_value_code: "maxdepth" wins over "depth").  fp64 rasters are bit-identical to
+        frontend.derive_output(name, self.download(), bed, dx); dtype=np.float32 gives those values rounded once."""
+        from .frontend import data_value_code
+        names = [values] if isinstance(values, str) else list(values)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32")
+        nrows = self.rows - row0 if nrows is None else nrows
+        codes = []
+        for name in names:
+            code = OUT_CODES.get(data_value_code(name))
+            if code is None:
+                raise ValueError(f"unknown output {name}")
+            if code not in codes:
+                codes.append(code)
+        arrays = [np.empty((max(0, nrows), self.cols), dtype) for _ in codes]
+        if codes:                                       # (also for nrows == 0: the library checks the range first)
+            c_values = (C.c_int * len(codes))(*codes)
+            c_rasters = (C.c_void_p * len(codes))(*[a.ctypes.data for a in arrays])
+            _check(self.lib, self.lib.hp_domain_derive(self.h, c_values, len(codes), dtype.itemsize, c_rasters, row0, nrows),
+                   "hp_domain_derive")
+            self.sync()
+        out, used = {}, set()
+        for name in names:
+            k = codes.index(OUT_CODES[data_value_code(name)])
+            out[name] = arrays[k].copy() if k in used else arrays[k]        # (two names of one value: separate arrays)
+            used.add(k)
+        return out
+
+    def stats(self, row0=0, nrows=None):
+        """cells, cells_wet, volume (m3), max_depth, max_speed and the local flat cell id of each maximum (None where no
+        cell qualifies) over rows [row0, row0 + nrows); blocks.  See hp_domain_stats_t for the definitions."""
+        nrows = self.rows - row0 if nrows is None else nrows
+        s = DomainStats()
+        s.struct_size = C.sizeof(DomainStats)
+        _check(self.lib, self.lib.hp_domain_stats(self.h, row0, nrows, C.byref(s)), "hp_domain_stats")
+        return dict(cells=s.cells, cells_wet=s.cells_wet, volume=s.volume, max_depth=s.max_depth, max_speed=s.max_speed,
+                    max_depth_cell=None if s.max_depth_cell == NO_CELL else s.max_depth_cell,
+                    max_speed_cell=None if s.max_speed_cell == NO_CELL else s.max_speed_cell)
 
     def upload_rows(self, rows_state, row0):
         a = np.ascontiguousarray(rows_state, dtype=self.real)

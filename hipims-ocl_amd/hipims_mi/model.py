@@ -159,7 +159,7 @@ class Model:
     """CModel for one domain: `run()` is runModelMain."""
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
-                 clock=time.perf_counter):
+                 clock=time.perf_counter, device_outputs=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -183,6 +183,17 @@ class Model:
         self.last_progress = 0.0
         self.outputs = []                                          # [(time, {value: array})]
         self.progress_blocks = []
+        # Where the output rasters are derived: on the device by the engine's `derive` (no state download) or on the host from
+        # the downloaded state.  None = the device wherever the engine has `derive` AND the domain is fp64 (11-18x faster,
+        # profiles/r07_output_stage.txt).  An fp32 domain keeps the host path by default: the front end's bed is fp64 (4-decimal
+        # values, mostly not fp32 numbers) and derive_output takes Z - bed with THAT bed, the device with the fp32 bed it was
+        # given, so the rasters of a single-precision model file would change.  True / False force a path (True on an fp32
+        # domain: rasters of the bed the domain holds).  Engines without `derive` (the oracle of the CPU tests): the host path.
+        if device_outputs and not hasattr(sim, "derive"):
+            raise ValueError("device_outputs=True needs an engine with derive()")
+        self.device_outputs = (hasattr(sim, "derive") and cfg.precision == "f64") if device_outputs is None else bool(device_outputs)
+        self.domain_stats = []                                     # [(time, stats())]: start, then every output time
+        self.log_domain_stats(initial=True)
 
     # CModel::runModelUpdateTarget (:723-770), one domain: run free until the next output is due
     def update_target(self):
@@ -197,10 +208,13 @@ class Model:
             self.current_time > self.last_output_time
         if not due:
             return False
-        final = self.sim.download()
+        if self.device_outputs:                                    # every target in ONE call, rasters only over the host link
+            derived = self.sim.derive([what for what, _ in self.cfg.targets]) if self.cfg.targets else {}
+        else:
+            final = self.sim.download()
         out = {}
         for k, (what, pattern) in enumerate(self.cfg.targets):
-            arr = frontend.derive_output(what, final, self.bed, self.res)
+            arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
             out[what] = arr
             if pattern and self.cfg.target_dir and self.output_format:
                 ext = self.output_format
@@ -214,7 +228,22 @@ class Model:
         self.scheme.force_time_advance()
         if self.log:
             self.log(f"Output files written at {seconds_to_time(self.current_time)} ({len(out)} rasters)")
+        self.log_domain_stats()
         return True
+
+    # CSchemeGodunov::prepareSimulation's "Initial domain volume" line (:1060) and the same figures at every output time
+    def log_domain_stats(self, initial=False):
+        if not hasattr(self.sim, "stats"):
+            return None
+        s = self.sim.stats()
+        self.domain_stats.append((0.0 if initial else self.current_time, s))
+        if self.log:
+            if initial:
+                self.log(f"Initial domain volume: {s['volume']:.0f} m3")
+            else:
+                self.log(f"Domain volume: {s['volume']:.0f} m3, wet cells: {s['cells_wet']} of {s['cells']}, "
+                         f"max depth: {s['max_depth']:.3f} m, max speed: {s['max_speed']:.3f} m/s")
+        return s
 
     # CModel::logProgress (:337-433): the same quantities; returned as a dict and, if a log sink is set, as a block
     def log_progress(self, seconds):

@@ -54,6 +54,26 @@ def partition(global_rows: int, world: int, g: int):
     return parts
 
 
+def assemble_outputs(parts):
+    """The ranks' owned-row rasters ({name: array}, in rank order = south to north) as rasters of the whole grid."""
+    return {name: np.concatenate([p[name] for p in parts], axis=0) for name in parts[0]}
+
+
+def combine_stats(parts, local_los, cols):
+    """Domain.stats() of every rank's OWNED rows (rank order) as the statistics of the whole grid: counts added and maxima
+    combined exactly -- equal maxima go to the lowest cell id, i.e. to the first rank that has them --, volumes added in
+    rank order.  Cell ids become global ones (y * cols + x): `local_los` are the global rows of the ranks' local row 0."""
+    out = dict(cells=0, cells_wet=0, volume=0.0, max_depth=0.0, max_speed=0.0, max_depth_cell=None, max_speed_cell=None)
+    for p, lo in zip(parts, local_los):
+        out["cells"] += p["cells"]
+        out["cells_wet"] += p["cells_wet"]
+        out["volume"] += p["volume"]
+        for val, cell in (("max_depth", "max_depth_cell"), ("max_speed", "max_speed_cell")):
+            if p[cell] is not None and (out[cell] is None or p[val] > out[val]):
+                out[val], out[cell] = p[val], p[cell] + lo * cols
+    return out
+
+
 class HipEngine:
     """The HIP domain of one strip + zero-copy torch views of its device buffers."""
 
@@ -109,6 +129,12 @@ class HipEngine:
 
     def download(self):
         return self.domain.download()
+
+    def derive(self, values, dtype=np.float64, row0=0, nrows=None):
+        return self.domain.derive(values, dtype=dtype, row0=row0, nrows=nrows)
+
+    def stats(self, row0=0, nrows=None):
+        return self.domain.stats(row0=row0, nrows=nrows)
 
     def set_target_time(self, t):
         self.domain.set_target_time(t)
@@ -407,6 +433,21 @@ class StripRunner:
         out = [None] * self.world
         self.dist.all_gather_object(out, mine)
         return np.concatenate(out, axis=0)
+
+    def gather_outputs(self, values, dtype=np.float64):
+        """Output rasters of the whole grid: every rank derives its OWNED rows on its device (Domain.derive), rank 0 gets
+        {name: array[rows, cols]}, the other ranks None.  Pickled objects over the process group, as gather_owned; collective."""
+        mine = self.engine.derive(values, dtype=dtype, row0=self.own_lo - self.local_lo, nrows=self.own_hi - self.own_lo)
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)                 # rasters travel to rank 0 only
+        return assemble_outputs(parts) if self.rank == 0 else None
+
+    def gather_stats(self):
+        """Domain.stats over the whole grid, on every rank (combine_stats); cell ids are global.  Collective."""
+        mine = self.engine.stats(row0=self.own_lo - self.local_lo, nrows=self.own_hi - self.own_lo)
+        parts = [None] * self.world
+        self.dist.all_gather_object(parts, (mine, self.local_lo))
+        return combine_stats([p[0] for p in parts], [p[1] for p in parts], self.cols)
 
     def close(self, destroy_group=True):
         """`destroy_group=False` keeps the process group for another StripRunner of this process (bench.py's second leg)."""

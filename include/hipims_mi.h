@@ -163,6 +163,42 @@ int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int6
 /* COCLBuffer::queueWritePartial into the next source buffer (CDomainLink::pushToBuffer, CDomainLink.cpp:252-270) */
 int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_t nrows);
 
+/* ---- the output stage on the device (no state download).
+ *      CDomainCartesian::writeOutputs (Domain/Cartesian/CDomainCartesian.cpp:804-829) reads the whole cell state back and
+ *      derives every raster on the host (Datasets/CRasterDataset.cpp:185-267); hp_domain_derive derives them where the
+ *      state lives and moves only the rasters asked for (8 or 4 bytes per cell and raster instead of 32 / 16 per cell).
+ *      All arithmetic is fp64 whatever the domain's precision (an fp32 domain's values are widened first) and uses
+ *      correctly rounded operations only: the fp64 rasters equal the host derivation bit for bit, the fp32 ones are
+ *      those values rounded once.  NODATA = -9999, wet threshold 1e-8 (the reference's, not dryThreshold). ---- */
+enum { HP_OUT_DEPTH = 0, HP_OUT_MAXDEPTH = 1, HP_OUT_FSL = 2, HP_OUT_MAXFSL = 3, HP_OUT_DISCHARGE_X = 4, HP_OUT_DISCHARGE_Y = 5,
+       HP_OUT_VELOCITY_X = 6, HP_OUT_VELOCITY_Y = 7, HP_OUT_FROUDE = 8, HP_OUT_COUNT = 9 };
+/* rasters[i] receives value values[i] (each value at most once) for rows [row0, row0 + nrows) of the LOCAL array (a strip's
+ * ghost rows included: the caller picks the owned range), cols elements a row, row 0 = south, element_bytes 8 (double) or
+ * 4 (float).  Reads the buffer hp_domain_download(HP_ARRAY_STATE) reads, in stream order behind whatever is queued, and
+ * changes nothing the steps depend on.  Enqueued on the domain's stream like hp_domain_download: the host memory must
+ * stay alive until hp_sync().  Device scratch for the rasters is allocated on first use and bounded (256 MiB: larger
+ * requests are worked through in blocks of rows); if that allocation fails the call returns HP_ERR_HIP and the domain
+ * stays usable.  Argument errors are HP_ERR_INVALID before any device call; nrows == 0 is HP_OK. */
+int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_bytes,
+                     void* const* rasters, int64_t row0, int64_t nrows);
+/* Statistics of rows [row0, row0 + nrows) of the same buffer: what the reference's progress log takes from
+ * CDomainCartesian::getVolume (CDomainCartesian.cpp:743-760, CSchemeGodunov.cpp:1060, CModel.cpp:1127) and what a user
+ * reads next to it.  A deterministic two-stage reduction (no floating-point atomics: the same state gives the same bits). */
+typedef struct {
+	uint32_t struct_size;        /* = sizeof(hp_domain_stats_t), set by the caller */
+	uint32_t reserved;
+	uint64_t cells;              /* cells counted: not disabled (Zmax > -9999) and bed <= 9999 (closed-edge walls hold no water) */
+	uint64_t cells_wet;          /* counted cells with Z - bed > 1e-8 */
+	double   volume;             /* dx^2 * sum of max(0, Z - bed) over the counted cells, m3.  NOT getVolume's sum, which is
+	                                unclamped (cells whose level lies below their bed count negative) and includes the walls
+	                                and disabled cells */
+	double   max_depth;          /* largest max(0, Z - bed) of a counted cell (0 if none is counted) */
+	double   max_speed;          /* largest sqrt(vx^2 + vy^2), v = Q / (Z - bed), of a wet cell (0 if none is wet) */
+	uint64_t max_depth_cell;     /* flat ids y * cols + x in the LOCAL array; ties go to the lowest id; UINT64_MAX if none */
+	uint64_t max_speed_cell;
+} hp_domain_stats_t;
+int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats_t* out);   /* BLOCKS */
+
 /* Device-side checkpoint: what saveCurrentState + rollbackSimulation do through host memory (CSchemeGodunov.cpp:1720-1736,
  * :1474-1518), kept in HBM instead (two more copies of a 4096^2 fp64 state are 1 GB of 288).  hp_state_save copies BOTH
  * ping-pong buffers and the time-control block; hp_state_restore puts each buffer, the time-control block, the ping-pong phase
