@@ -97,15 +97,9 @@ struct hp_domain {
 	bool             edge_dirty = true;               // edge-ring maxima must be re-priced
 	bool             bdy_on_ring = false;             // a cell boundary imposes values on never-written ring cells: re-price every iteration
 	int              adv_fresh = 1;                   // does hp_step_end's advance kernel read a new maximum?
-	int              march_rseg = 16;                 // rows per wavefront tile of godunov_march
-	int              muscl_rseg = 32;                 // ... of muscl_march (two warm-up rows per tile)
-	int              inertial_rseg = 32;              // ... of inertial_march
-	int              march_nbands = 8, muscl_nbands = 8, inertial_nbands = 8;   // row bands of a whole-domain launch (pick_tiling)
-	int              march_rseg_parts = 16, inertial_rseg_parts = 16;            // tile height of the interior / halo parts of a split step (8 / 2 bands: the classic height)
+	Tiling           tiling;                          // tile heights and row bands of its launches (hp_tiling.hpp: choose_tiling)
 	int              sweep_flip = 0;                  // parity of the whole-domain flux launches: every other one visits each band's tiles from
 	                                                  // the top down, so that it starts on the rows its predecessor wrote last (sweep_alternates)
-	int              tall_rseg = 18;                  // K1/K6 tile height where an XCD band has >= 256 rows (16 if a knob is set)
-	int              tail_rseg = 8, tail_pct = 0;     // optional short tiles for the last tail_pct % of each XCD band (measured: no gain)
 	void*            host_scalars = nullptr;          // pinned mirror
 	int              use_alt = 0;                     // bUseAlternateKernel
 	bool             in_step = false;
@@ -168,10 +162,6 @@ struct hp_domain {
 	bool             rings_checked = false;           // ... and have been compared since (rings_really_differ): the flag is a fact, not a maybe
 	bool             fill_now = false;                // this iteration's K1 launch stores the cells the reference leaves untouched as well (dispatch_begin)
 	bool             other_stale = false;             // pairs (godunov_march2) ran since the non-current state buffer last held a state the single-iteration kernels can build on
-	int              march2_rseg = 24;                // tile height of the two-iterations kernel
-	bool             march2_pays = false;             // the grid is big enough for it (hp_domain_create)
-	int              march2_nbands = 8;               // its row bands (one-round grids: searched)
-	bool             print_tiling = false;
 	// quirk Q3 across pair launches, exactly (hp_kernels.hpp: PairAux): stamps of the cells whose first-step stale value the next launch needs
 	void*            z_state = nullptr;               // stamp records, one per cell: State4<T> + the number of the pair launch that wrote it (allocated with the first pair)
 	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
@@ -351,68 +341,35 @@ template <typename T> int price_edge_ring(hp_domain* d)
 	return HP_OK;
 }
 
-// Which rows of the domain one launch covers
-enum { PART_ALL = 0, PART_HALO = 1, PART_INTERIOR = 2 };
-
-// Row ranges of the three parts.  [lo, hi) are the updated rows of the domain; with the halo overlap the `halo` rows
-// next to each ghost block (one tile height, at least the g rows the neighbours need) form the halo part -- a south
-// and a north block, covered by ONE launch with two bands -- and the rest the interior part.  A domain too thin for
-// an interior part runs whole in the halo part.
-struct RowRange { long lo, hi; };
-
-// TileMap of one launch (see hp_kernels.hpp): 8 XCD bands over [lo, hi), tall tiles first and optionally short tiles
-// for the last `tail_pct` percent of each band; or, for the halo part, the two blocks of `halo` rows as two bands.
-inline bool make_tile_map(long lo, long hi, int g, int part, int nstrips, int rseg, int rseg_tail, int tail_pct,
-                          TileMap& tm, unsigned& blocks, int rseg_tall = 16, long need = 0, long price_lo = 0, long price_hi = 0x7fffffffL,
-                          int nbands = 8)
+// The tiling knobs (hp_tiling.hpp) from the environment: these three readers are the only place that names the variables.  Each is
+// read when it always was: at hp_domain_create HP_RSEG_REFINE and the pair kernel's look at HP_TILING_SEARCH once per process,
+// the others per domain (tools/strong_probe_pair.py creates domains with the K1 / K6 search on and off); once per process, at the
+// first launch, what make_tile_map takes; once per process, at the first pair launch, whether HP_MARCH2_RSEG is set at all.
+TilingKnobs tiling_knobs()
 {
-	static const long halo_env = std::getenv("HP_HALO_ROWS") ? std::atol(std::getenv("HP_HALO_ROWS")) : 0;
-	if (need < g) need = g;                                             // rows at each end that a strip neighbour is sent
-	const long halo = halo_env >= need ? halo_env : (rseg > need ? rseg : need);
-	tm.price_lo = (int)price_lo; tm.price_hi = (int)(price_hi < 0x7fffffffL ? price_hi : 0x7fffffffL);
-	tm.flip = 0;
-	const bool can_split = hi - lo > 2 * halo;
-	tm.nstrips = nstrips;
-	tm.groups = (nstrips + 3) / 4;
-	if (part == PART_HALO && can_split) {
-		tm.y_begin = lo; tm.y_end = hi;
-		tm.nbands = 2; tm.band_stride = (hi - halo) - lo; tm.band_rows = (int)halo;
-		tm.rseg = rseg < tm.band_rows ? rseg : tm.band_rows;
-		tm.nbig = (tm.band_rows + tm.rseg - 1) / tm.rseg;
-		tm.rseg_tail = rseg_tail; tm.ntail = 0;
-		blocks = 2u * (unsigned)(tm.groups * tm.nbig);
-		return true;
-	}
-	if (part == PART_INTERIOR) {
-		if (!can_split) return false;                                   // the halo launch took everything
-		lo += halo; hi -= halo;
-	}
-	tm.y_begin = lo; tm.y_end = hi;
-	const long rows = hi - lo;
-	// Row bands: 8, one per XCD -- or, for a whole-domain launch that fits the chip in ONE round, the number the tiling
-	// search of hp_domain_create found (pick_tiling: such a launch is bound by its most loaded CU, and 8 x groups x segments
-	// only offers coarse block counts).  HP_NBANDS forces a number (tools/history/r04_band_sweep.py).
-	static const int nbands_env = std::getenv("HP_NBANDS") ? std::atoi(std::getenv("HP_NBANDS")) : 0;
-	tm.nbands = part != PART_ALL ? 8 : (nbands_env >= 1 && nbands_env <= 64 ? nbands_env : (nbands >= 1 && nbands <= 64 ? nbands : 8));
-	tm.band_rows = (int)((rows + tm.nbands - 1) / tm.nbands);
-	tm.band_stride = tm.band_rows;
-	// K1/K6 on tall bands: 18-row tiles measured 1.9 % / 2.8 % ahead of 16 at 4096^2 (band of 512 rows) and 0.6 % at
-	// 8192 x 2050 (256), but 3 % behind at 16384 x 1026 (128 rows = eight exact 16-row tiles); interleaved repeats
-	// on one box, tools/rseg_fine_sweep*.sh
-	if (rseg == 16 && g == 1 && tm.band_rows >= 256) rseg = rseg_tall;
-	tm.rseg = rseg < tm.band_rows ? rseg : tm.band_rows;
-	tm.rseg_tail = rseg_tail;
-	if (rseg_tail >= tm.rseg || tail_pct <= 0) {
-		tm.nbig = (tm.band_rows + tm.rseg - 1) / tm.rseg;
-		tm.ntail = 0;
-	} else {
-		const int tail_rows = (int)((long)tm.band_rows * tail_pct / 100);
-		tm.nbig = (tm.band_rows - tail_rows + tm.rseg - 1) / tm.rseg;
-		const int rest = tm.band_rows - tm.nbig * tm.rseg;
-		tm.ntail = rest > 0 ? (rest + rseg_tail - 1) / rseg_tail : 0;
-	}
-	blocks = (unsigned)tm.nbands * (unsigned)(tm.groups * (tm.nbig + tm.ntail));
-	return true;
+	auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? std::atoi(e) : unset; };
+	auto has = [](const char* name) { return std::getenv(name) != nullptr; };
+	static const bool refine = num("HP_RSEG_REFINE", 1) != 0, search_pair = num("HP_TILING_SEARCH", 1) != 0;
+	TilingKnobs k;
+	k.rseg_refine = refine; k.search_pair = search_pair; k.search = num("HP_TILING_SEARCH", 1) != 0;
+	k.search_f32 = has("HP_TILING_SEARCH_F32"); k.print_tiling = has("HP_PRINT_TILING");
+	if (const char* e = std::getenv("HP_TILING_FILL")) k.tiling_fill = std::atof(e);
+	if (const char* e = std::getenv("HP_MARCH2_FILL")) k.march2_fill = std::atof(e);
+	k.march_rseg = num("HP_MARCH_RSEG", 0); k.muscl_rseg = num("HP_MUSCL_RSEG", 0);
+	k.inertial_rseg = num("HP_INERTIAL_RSEG", 0); k.march2_rseg = num("HP_MARCH2_RSEG", 0);
+	k.tail_rseg = num("HP_TAIL_RSEG", 0); k.tail_pct = num("HP_TAIL_PCT", -1);
+	return k;
+}
+const LaunchKnobs& launch_knobs()
+{
+	static const LaunchKnobs k = {std::getenv("HP_HALO_ROWS") ? std::atol(std::getenv("HP_HALO_ROWS")) : 0,
+	                              std::getenv("HP_NBANDS") ? std::atoi(std::getenv("HP_NBANDS")) : 0};
+	return k;
+}
+bool march2_rseg_forced()               // (run_pair_t: no STRICT 12-row cap then)
+{
+	static const bool forced = std::getenv("HP_MARCH2_RSEG") != nullptr;
+	return forced;
 }
 
 // Rows one flux launch updates: everything between the never-written edge ring / the outermost ghost rows.  A strip with
@@ -520,8 +477,9 @@ int launch_muscl(hp_domain* d, const void* src, void* dst, int edge_buffer, int 
 	unsigned blocks;
 	long lo, hi;
 	launch_rows(d, 2, lo, hi);
-	if (!make_tile_map(lo, hi, 2, part, (int)((p.cols - 4 + MUSCL_COLS - 1) / MUSCL_COLS), d->muscl_rseg, d->tail_rseg < 8 ? 8 : d->tail_rseg, d->tail_pct, tm, blocks,
-	                   16, d->ghost_rows, d->own_lo, d->own_hi, d->muscl_nbands))
+	const Tiling& t = d->tiling;
+	if (!make_tile_map(launch_knobs(), lo, hi, 2, part, (int)((p.cols - 4 + MUSCL_COLS - 1) / MUSCL_COLS), t.muscl_rseg, t.tail_rseg < 8 ? 8 : t.tail_rseg, t.tail_pct, tm, blocks,
+	                   16, d->ghost_rows, d->own_lo, d->own_hi, t.muscl_nbands))
 		return HP_OK;
 	sweep_direction(d, part, tm);
 	LaunchTail<T> tail;
@@ -553,8 +511,9 @@ int launch_march(hp_domain* d, const void* src, void* dst, int edge_buffer, int 
 	unsigned blocks;
 	long lo, hi;
 	launch_rows(d, 1, lo, hi);
-	if (!make_tile_map(lo, hi, 1, part, (int)((p.cols - 2 + MARCH_COLS - 1) / MARCH_COLS), part == PART_ALL ? d->march_rseg : d->march_rseg_parts, d->tail_rseg, d->tail_pct, tm, blocks, d->tall_rseg,
-	                   d->ghost_rows, d->own_lo, d->own_hi, d->march_nbands))
+	const Tiling& t = d->tiling;
+	if (!make_tile_map(launch_knobs(), lo, hi, 1, part, (int)((p.cols - 2 + MARCH_COLS - 1) / MARCH_COLS), part == PART_ALL ? t.march_rseg : t.march_rseg_parts, t.tail_rseg, t.tail_pct, tm, blocks, t.tall_rseg,
+	                   d->ghost_rows, d->own_lo, d->own_hi, t.march_nbands))
 		return HP_OK;
 	sweep_direction(d, part, tm);
 	const int truncated = ((d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0 ? 1 : 0) | (d->fill_now ? 2 : 0);   // the kernel's `flags`
@@ -603,8 +562,9 @@ int launch_inertial(hp_domain* d, const void* src, void* dst, int edge_buffer, i
 	unsigned blocks;
 	long lo, hi;
 	launch_rows(d, 1, lo, hi);
-	if (!make_tile_map(lo, hi, 1, part, (int)((p.cols - 2 + MARCH_COLS - 1) / MARCH_COLS), part == PART_ALL ? d->inertial_rseg : d->inertial_rseg_parts, d->tail_rseg, d->tail_pct, tm, blocks, d->tall_rseg,
-	                   d->ghost_rows, d->own_lo, d->own_hi, d->inertial_nbands))
+	const Tiling& t = d->tiling;
+	if (!make_tile_map(launch_knobs(), lo, hi, 1, part, (int)((p.cols - 2 + MARCH_COLS - 1) / MARCH_COLS), part == PART_ALL ? t.inertial_rseg : t.inertial_rseg_parts, t.tail_rseg, t.tail_pct, tm, blocks, t.tall_rseg,
+	                   d->ghost_rows, d->own_lo, d->own_hi, t.inertial_nbands))
 		return HP_OK;
 	sweep_direction(d, part, tm);
 	LaunchTail<T> tail;
@@ -839,7 +799,7 @@ template <typename T> int step_end_impl(hp_domain* d)
 // no strips, the reference's reduction quirk Q1 on (it is what makes the second timestep known in advance), the remembered maximum
 // valid, the launch's own tail block available (it advances the time twice), and the next iteration reads the primary buffer.
 // HP_TWO_STEP=0 switches it off, =1 forces it on wherever it is eligible; default: grids whose launch is at least two rounds of
-// blocks at 12-row tiles (hp_domain_create: march2_pays -- below that the extra halo rows and the shorter tiles cost more than the
+// blocks at 12-row tiles (choose_tiling: march2_pays -- below that the extra halo rows and the shorter tiles cost more than the
 // bytes save: 1024^2 and the 4096 x 514 strip lose 3-5 %, 2048^2 gains 13 %, 4096^2 22 %, profiles/r05n_two_step.txt).
 static int two_step_mode()
 {
@@ -851,7 +811,7 @@ static int two_step_mode()
 static bool pairs_possible_common(const hp_domain* d)
 {
 	const int mode = two_step_mode();
-	if (mode == 0 || (mode < 0 && !d->march2_pays)) return false;
+	if (mode == 0 || (mode < 0 && !d->tiling.march2_pays)) return false;
 	static const bool tail_enabled = !(std::getenv("HP_LAUNCH_TAIL") && std::atoi(std::getenv("HP_LAUNCH_TAIL")) == 0);
 	// boundary conditions: none, or area boundaries the flux kernel can carry itself (`fusable`: uniform / coarse gridded ones; round 6) --
 	// the pair kernel applies them between its two steps and prices the state it stores with and without the next iteration's
@@ -991,10 +951,9 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	} else launch_rows(d, 1, lo, hi);
 	// (STRICT: 12-row tiles -- its live tiles cost 1300 instructions per row and stage, and a 24-row one is what the launch waits for at its
 	// end: S-DAM 4096^2 0.275 ms per iteration at 24 rows, 0.2645 at 12, 0.281 at 8; profiles/r06i_strict_pair_tile_sweep.txt)
-	static const bool rseg_forced = std::getenv("HP_MARCH2_RSEG") != nullptr;
-	const int rseg2 = (d->desc.math_mode == HP_MATH_STRICT && !rseg_forced) ? std::min(d->march2_rseg, 12) : d->march2_rseg;
-	if (!make_tile_map(lo, hi, 1, PART_ALL, (int)((p.cols - 2 + MARCH2_COLS - 1) / MARCH2_COLS), rseg2, rseg2, 0, tm, blocks, rseg2,
-	                   0, d->own_lo, d->own_hi, d->march2_nbands))
+	const int rseg2 = (d->desc.math_mode == HP_MATH_STRICT && !march2_rseg_forced()) ? std::min(d->tiling.march2_rseg, 12) : d->tiling.march2_rseg;
+	if (!make_tile_map(launch_knobs(), lo, hi, 1, PART_ALL, (int)((p.cols - 2 + MARCH2_COLS - 1) / MARCH2_COLS), rseg2, rseg2, 0, tm, blocks, rseg2,
+	                   0, d->own_lo, d->own_hi, d->tiling.march2_nbands))
 		return HP_ERR_STATE;
 	if (blocks > tail_limit()) return HP_ERR_STATE;                      // (the caller falls back to single iterations)
 	d->tail_want = true; d->tail_allowed = true; d->push_now = strip;    // (strip: the final rows of the edge ranges leave with the launch)
@@ -1359,218 +1318,20 @@ int hp_domain_create(const hp_domain_desc_t* desc, hp_domain_t** out)
 	if (d->own_hi - d->own_lo < 1) { delete d; return fail(HP_ERR_INVALID, "strip has no owned rows"); }
 	d->cells = (size_t)desc->cols * (size_t)desc->rows;
 	d->esize = (size_t)desc->precision;
-	// Tile height: a wavefront marches its tile's rows one after the other, so a grid that yields few tiles is bound
-	// by that serial walk, not by bandwidth (342 x 195: 35 us per step at 16 rows, 12 us at 2).  Take the tallest
-	// tile that still gives every CU some blocks (tools/small_grid_probe.py: 4096^2 and 2048^2 want 16, 1024^2 8,
-	// 512^2 4, the 342 x 195 example 2).
 	{
 		int cus = 256;
 		hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device);
-		static const bool refine = !(std::getenv("HP_RSEG_REFINE") && std::atoi(std::getenv("HP_RSEG_REFINE")) == 0);
-		// (read per domain, not once per process: tools/strong_probe_pair.py creates domains both ways)
-		const bool one_round_search = !(std::getenv("HP_TILING_SEARCH") && std::atoi(std::getenv("HP_TILING_SEARCH")) == 0);
-		auto pick = [&](long updated_rows, long updated_cols, int tile_cols, int tallest, int shortest, int blocks_per_cu, int& nbands_out, bool searchable,
-		                int* classic_out = nullptr) {
-			const long groups = ((updated_cols + tile_cols - 1) / tile_cols + 3) / 4;
-			nbands_out = 8;
-			int rseg = tallest;
-			while (rseg > shortest && groups * ((updated_rows + rseg - 1) / rseg) < 350) rseg /= 2;
-			if (rseg < shortest) rseg = shortest;
-			// Round 3: a launch whose blocks all fit the chip at once (a row strip of a strong-scaling run: 4096 x 514 is 544
-			// tiles of 16 rows on 768 block slots) lasts as long as ONE tile does, so the shortest tile that still fits in one
-			// round wins: 13-row tiles put that strip into 680 blocks (56 -> 51 us per iteration).  Fine-tune within
-			// (rseg/2, rseg] where the halving above left a middle-sized tile; launches of more than one round are left alone
-			// (tools/history/r03k.sh: 2048^2, 4096 x 1026 and 8192 x 514 lose 0-9 % with shorter tiles).
-			if (refine && rseg >= 8) {
-				const long band_rows = (updated_rows + 7) / 8, slots = (long)cus * blocks_per_cu;
-				auto cost = [&](int r) {
-					const long blocks = groups * 8 * ((band_rows + r - 1) / r);
-					return ((blocks + slots - 1) / slots) * (long)(2 * r + 7);        // rounds x (rows + 3.5), doubled to stay integral
-				};
-				if (groups * 8 * ((band_rows + rseg - 1) / rseg) <= slots) {        // measured (profiles/r03k): no gain beyond one round
-					int best = rseg;
-					for (int r = rseg - 1; r > rseg / 2; --r) if (cost(r) < cost(best)) best = r;
-					rseg = best;
-					// Round 4: what such a launch really lasts is what its MOST LOADED CU has to walk: blocks are dealt to the CUs
-					// layer by layer (block b lands on CU b mod cus while every CU has room), a block costs its rows plus ~3.5 rows
-					// of pipeline fill, and the blocks of one CU share its SIMDs.  8 bands x groups x segments only offers coarse
-					// block counts (680 blocks on 256 CUs: 168 CUs walk three 13-row tiles, 88 walk two); with another number
-					// of bands the last segment of each band can be a SHORT tile, and "two tall + one short on every CU" (15
-					// bands, 15 + 15 + 5 rows: 765 blocks) measured 39.1 us per iteration on the 4096 x 514 strip against 43.4
-					// (profiles/r04b_band_sweep_4096x514.txt).  The search simulates the dealing for every (bands, rows) pair that
-					// fits one round and takes the cheapest; a CU with fewer than three resident blocks hides less latency
-					// (2 blocks: +20 %, 1 block: +60 %, fitted on the same sweep).
-					// (the searched height is only right TOGETHER with its band count, which only a whole-domain launch gets: the interior /
-					// halo parts of a split step keep the classic height -- ADVICE r04)
-					if (classic_out) *classic_out = rseg;
-					if (one_round_search && searchable) {
-						// a tile's fixed cost in row-times: 3.5 for fp64 K1 / K6 (the pipeline fill and the extra south face)
-						const double fill = std::getenv("HP_TILING_FILL") ? std::atof(std::getenv("HP_TILING_FILL")) : 3.5;
-						double best_cost = 1e30;
-						int best_nb = 8, best_r = rseg;
-						long best_pref = -2;
-						std::vector<double> load((size_t)cus);
-						std::vector<int> count((size_t)cus);
-						for (int nb = 1; nb <= 32; ++nb) {
-							const long brows = (updated_rows + nb - 1) / nb;
-							for (int r = 4; r <= 64 && r <= brows; ++r) {
-								const long nseg = (brows + r - 1) / r, blocks = (long)nb * groups * nseg;
-								if (blocks > slots) continue;
-								std::fill(load.begin(), load.end(), 0.0);
-								std::fill(count.begin(), count.end(), 0);
-								for (long b = 0; b < blocks; ++b) {                  // tile_rows() of hp_kernels.hpp
-									const long band = b % nb, i = b / nb, seg = i / groups;
-									const long y0 = band * brows + seg * r;
-									const long band_end = std::min(updated_rows, (band + 1) * brows);
-									const long h = std::min(y0 + r, band_end) - y0;
-									if (h <= 0) continue;
-									load[(size_t)(b % cus)] += (double)h + fill;
-									count[(size_t)(b % cus)] += 1;
-								}
-								double worst = 0.0;
-								for (int c = 0; c < cus; ++c) {
-									const double f = count[(size_t)c] >= 3 ? 1.0 : count[(size_t)c] == 2 ? 1.2 : 1.6;
-									worst = std::max(worst, load[(size_t)c] * f);
-								}
-								// (ties: round 5 -- the last tile of a band as tall as it can be up to half a full tile (the pair kernel's rule below;
-								// K1 on the 4096 x 514 strip: 14 + 14 + 7 33.3 us, 13 + 13 + 9 33.1, round 4's 15 + 15 + 5 34.3, profiles/r05fq_*) --,
-								// then the taller first tiles, then the tiling nearest to the 8-band one, whose bands keep to their XCD's L2)
-								const long last = brows - (nseg - 1) * r;
-								const long pref = (nseg >= 2 && nseg <= 3 && 2 * last <= r) ? last : -1;
-								if (worst < best_cost - 1e-9 || (worst < best_cost + 1e-9 && (pref > best_pref || (pref == best_pref &&
-								    (r > best_r || (r == best_r && std::abs(nb - 8) < std::abs(best_nb - 8))))))) {
-									best_cost = worst; best_nb = nb; best_r = r; best_pref = pref;
-								}
-							}
-						}
-						nbands_out = best_nb; rseg = best_r;
-					}
-				}
-			}
-			return rseg;
-		};
-		// fp32 (round 4, profiles/r04za_rseg_f32.txt, r04z_band_sweep_f32_shapes.txt): a tile's fill and extra south face want tall
-		// tiles, the dispatcher wants many -- 32 rows is best only where that still leaves six rounds of blocks (8192^2: 6.8); below
-		// that shorter tiles win by more than the fill costs: 4096^2 S-DAM 0.143 -> 0.129 ms and S-RAIN 0.180 -> 0.168 at 12 rows,
-		// the 8192 x 1026 strip of config C5 0.113 -> 0.089 ms (S-RAIN) and 83 -> 66 us (S-DAM); 8 rows lose again.  (Round 2's "32
-		// rows, 13-47 % ahead of 16" was measured on kernels with a dearer fill.)  fp64 is flat from 10 to 20 rows.
-		// fp64 (profiles/r04zc_rseg_f64_shapes.txt): flat from 10 to 20 rows where a launch is many rounds (4096^2, 16384 x 1026); between
-		// one round and 2.5 (2048^2, 4096 x 1026, 8192 x 1026 ...) 12 rows are 5-9 % ahead of 16 for K1, 10 rows 5-7 % ahead of 12 for K2.
-		const bool f32 = desc->precision == 4;
-		auto tallest_by_rounds = [&](long updated_rows, long updated_cols, int tile_cols, int blocks_per_cu, std::initializer_list<int> tall,
-		                             double rounds, int otherwise) {
-			const long groups = ((updated_cols + tile_cols - 1) / tile_cols + 3) / 4, band_rows = (updated_rows + 7) / 8;
-			// (fp64: a launch that fits the chip in about ONE round at the classic height belongs to the one-round logic inside pick();
-			// the 4096 x 516 MUSCL strip, 1.1 rounds at 12 rows, measured 3 % behind with 10)
-			if (!f32 && (double)(groups * 8 * ((band_rows + *tall.begin() - 1) / *tall.begin())) <= 1.25 * cus * blocks_per_cu) return *tall.begin();
-			for (int r : tall)
-				if ((double)(groups * 8 * ((band_rows + r - 1) / r)) >= rounds * cus * blocks_per_cu) return r;
-			return otherwise;
-		};
-		const int k1_tallest = f32 ? tallest_by_rounds(desc->rows - 2, desc->cols - 2, MARCH_COLS, 5, {32, 24, 16}, 6.0, 12)
-		                           : tallest_by_rounds(desc->rows - 2, desc->cols - 2, MARCH_COLS, 3, {16}, 2.5, 12);
-		const int k2_tallest = f32 ? tallest_by_rounds(desc->rows - 4, desc->cols - 4, MUSCL_COLS, 4, {32, 24, 16}, 6.0, 12)
-		                           : tallest_by_rounds(desc->rows - 4, desc->cols - 4, MUSCL_COLS, 3, {12}, 3.0, 10);
-		int classic = 0;
-		d->march_rseg    = pick(desc->rows - 2, desc->cols - 2, MARCH_COLS, k1_tallest, 2, desc->precision == 4 ? 5 : 3, d->march_nbands,
-		                        desc->precision == 8 || std::getenv("HP_TILING_SEARCH_F32") != nullptr, &classic);      // (fp32: 8192 x 1026 measured 83.2 -> 84.4 us with the searched tiling: its fill is not 3.5 rows)
-		d->march_rseg_parts = classic > 0 ? classic : d->march_rseg;
-		d->inertial_rseg = d->march_rseg; d->inertial_nbands = d->march_nbands; d->inertial_rseg_parts = d->march_rseg_parts;
-		// K2 after the inert-row cut (round 2): a tile of still water or dry land costs a fifth of a tile on the flood front,
-		// so fp64 wants more, shorter tiles for the dispatcher to balance (16-20 rows: 0.319 ms against 0.355 at 32 on the
-		// 4096^2 dam break, 0.355 against 0.395 on the developed flood, +2-5 % at 8192^2 and 16384 x 1028)
-		// (round 4, profiles/r04l_k2_rseg.txt: 12 rows: the 4096^2 dam break 0.300 -> 0.287 ms, developed flood 0.343 -> 0.340, 2048^2 -1.4 %,
-		// 8192^2 +0.6 %, every tile live +1.7 %; 10 and below lose again; fp32: as K1 -- 4096^2 dam break 0.192 -> 0.161 ms at 12 rows)
-		d->muscl_rseg    = pick(desc->rows - 4, desc->cols - 4, MUSCL_COLS, k2_tallest, 4, desc->precision == 4 ? 4 : 3, d->muscl_nbands,
-		                        false);                     // (K2's tiles differ fivefold in cost -- inert rows --: the searched tiling lost 20 % on the 4096 x 514 dam break)
-		if (d->muscl_rseg < 4) d->muscl_rseg = 4;
-	}
-	if (std::getenv("HP_PRINT_TILING"))
-		std::fprintf(stderr, "[hipims_mi] tiling %ld x %ld: K1/K6 %d rows x %d bands, K2 %d rows x %d bands\n", (long)desc->cols, (long)desc->rows,
-		             d->march_rseg, d->march_nbands, d->muscl_rseg, d->muscl_nbands);
-	d->print_tiling = std::getenv("HP_PRINT_TILING") != nullptr;
-	if (const char* e = std::getenv("HP_MARCH_RSEG")) {                   // tuning knob: rows per wavefront tile
-		const int v = std::atoi(e);
-		if (v >= 1 && v <= 64) { d->march_rseg = d->march_rseg_parts = v; d->tall_rseg = 16; }   // a forced 16 stays 16
-	}
-	{
-		// the two-iterations kernel: the tallest tile that leaves four rounds of blocks (three 4-wave blocks per CU); worth taking at
-		// all from two rounds at 12-row tiles (profiles/r05n_two_step.txt)
-		int cus = 256;
-		hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device);
-		const long groups = (((long)desc->cols - 2 + MARCH2_COLS - 1) / MARCH2_COLS + 3) / 4, band_rows = ((long)desc->rows - 2 + 7) / 8;
-		const long slots = (long)cus * 3;
-		auto blocks_at = [&](int r) { return groups * 8 * ((band_rows + r - 1) / r); };
-		d->march2_rseg = 12;
-		for (int r : {32, 24, 18}) if (blocks_at(r) >= 4 * slots) { d->march2_rseg = r; break; }
-		d->march2_pays = blocks_at(12) >= 2 * slots;
-		// One round of blocks (the 4096 x 514 strip of a strong-scaling run): as for K1 (pick: one_round_search), what such a launch
-		// lasts is what its most loaded CU walks -- (bands, rows) by simulating the dealing, a tile costing its rows plus the two
-		// extra first-step rows and the pipeline fill.  profiles/r05u_strip_pair_sweep.txt: 14 bands x 15 rows 31.6 us per iteration
-		// against 33.7 in single iterations and 36.0 with 8 bands x 12 rows; taken from 1.5 M cells on (below: untested).
-		static const bool search = !(std::getenv("HP_TILING_SEARCH") && std::atoi(std::getenv("HP_TILING_SEARCH")) == 0);
-		const long updated_rows = (long)desc->rows - 2;
-		if (!d->march2_pays && search && d->cells >= 1500000 && blocks_at(12) >= slots / 2) {
-			const double fill = std::getenv("HP_MARCH2_FILL") ? std::atof(std::getenv("HP_MARCH2_FILL")) : 4.0;
-			double best_cost = 1e30;
-			int best_nb = 0, best_r = 0;
-			long best_pref = -2;
-			std::vector<double> load((size_t)cus);
-			std::vector<int> count((size_t)cus);
-			for (int nb = 8; nb <= 32; ++nb) {                              // (at least a band per XCD: 4 bands x 14 rows lost 2 % at 1448^2)
-				const long brows = (updated_rows + nb - 1) / nb;
-				for (int r = 8; r <= 32 && r <= brows; ++r) {
-					const long nseg = (brows + r - 1) / r, blocks = (long)nb * groups * nseg;
-					if (blocks > slots) continue;
-					std::fill(load.begin(), load.end(), 0.0);
-					std::fill(count.begin(), count.end(), 0);
-					for (long b = 0; b < blocks; ++b) {                      // tile_rows() of hp_kernels.hpp
-						const long band = b % nb, i = b / nb, seg = i / groups;
-						const long y0 = band * brows + seg * r;
-						const long h = std::min(y0 + r, std::min(updated_rows, (band + 1) * brows)) - y0;
-						if (h <= 0) continue;
-						load[(size_t)(b % cus)] += (double)h + fill;
-						count[(size_t)(b % cus)] += 1;
-					}
-					double worst = 0.0;
-					for (int c = 0; c < cus; ++c)
-						worst = std::max(worst, load[(size_t)c] * (count[(size_t)c] >= 3 ? 1.0 : count[(size_t)c] == 2 ? 1.2 : 1.6));
-					// Ties -- the same rows and the same number of tiles on every CU, cut differently (37 rows as 16 + 16 + 5, 15 + 15 + 7,
-					// 14 + 14 + 9 ...): measured over eight one-round shapes (profiles/r05fp_tie_sweep.txt), the pair kernel wants the LAST
-					// tile of a band as tall as it can be without exceeding half a full tile -- 15 + 15 + 7 is 4 % ahead of 16 + 16 + 5 and
-					// 6 % ahead of 13 + 13 + 11 on the 4096 x 514 strip (30.0 against 31.4 / 32.0 us), 11 + 11 + 5 6 % ahead of 12 + 12 + 3
-					// on 3072 x 514 -- and otherwise the taller tiles.
-					// (bands of two or three tiles: with more the rule made 1448^2 slower)
-					const long last = brows - (nseg - 1) * r;
-					const long pref = (nseg >= 2 && nseg <= 3 && 2 * last <= r) ? last : -1;
-					if (worst < best_cost - 1e-9 || (worst < best_cost + 1e-9 && (pref > best_pref || (pref == best_pref && r > best_r)))) {
-						best_cost = worst; best_nb = nb; best_r = r; best_pref = pref;
-					}
-				}
-			}
-			if (best_nb > 0) { d->march2_rseg = best_r; d->march2_nbands = best_nb; d->march2_pays = true; }
-		}
-	}
-	if (const char* e = std::getenv("HP_MARCH2_RSEG")) { const int v = std::atoi(e); if (v >= 2 && v <= 32) d->march2_rseg = v; }
-	if (d->print_tiling)
-		std::fprintf(stderr, "[hipims_mi] tiling %ld x %ld: pair kernel %d rows x %d bands, %s\n", (long)desc->cols, (long)desc->rows, d->march2_rseg,
-		             d->march2_nbands, d->march2_pays ? "taken by default" : "not taken by default");
-	if (const char* e = std::getenv("HP_TAIL_RSEG")) { const int v = std::atoi(e); if (v >= 1 && v <= 64) d->tail_rseg = v; }
-	if (const char* e = std::getenv("HP_TAIL_PCT"))  { const int v = std::atoi(e); if (v >= 0 && v <= 100) d->tail_pct = v; }
-	if (const char* e = std::getenv("HP_INERTIAL_RSEG")) {
-		const int v = std::atoi(e);
-		if (v >= 1 && v <= 64) { d->inertial_rseg = d->inertial_rseg_parts = v; d->tall_rseg = 16; }
-	}
-	if (const char* e = std::getenv("HP_MUSCL_RSEG")) {
-		const int v = std::atoi(e);
-		if (v >= 1 && v <= 4096) d->muscl_rseg = v;
-	}
-
-	{
-		// a wavefront addresses its tile through a buffer resource whose range field is 31 bits wide: the tile's rows
-		// (segment + halo rows) must fit in it
-		const int rseg_max = std::max(std::max(d->march_rseg, d->march2_rseg), std::max(d->muscl_rseg, d->inertial_rseg));
-		if ((double)(rseg_max + 4) * (double)desc->cols * 4.0 * (double)desc->precision >= 2147483647.0) {
+		const TilingKnobs knobs = tiling_knobs();
+		Tiling& t = d->tiling;
+		t = pick_tiling(desc->cols, desc->rows, desc->precision, cus, knobs);
+		if (t.print_tiling)
+			std::fprintf(stderr, "[hipims_mi] tiling %ld x %ld: K1/K6 %d rows x %d bands, K2 %d rows x %d bands\n", (long)desc->cols, (long)desc->rows,
+			             t.march_rseg, t.march_nbands, t.muscl_rseg, t.muscl_nbands);
+		force_heights(t, knobs);
+		if (t.print_tiling)
+			std::fprintf(stderr, "[hipims_mi] tiling %ld x %ld: pair kernel %d rows x %d bands, %s\n", (long)desc->cols, (long)desc->rows, t.march2_rseg,
+			             t.march2_nbands, t.march2_pays ? "taken by default" : "not taken by default");
+		if (!tiles_addressable(t, desc->cols, desc->precision)) {
 			delete d;
 			return fail(HP_ERR_UNSUPPORTED, "grid too wide for the tile addressing (cols * 32 B * (rows per tile + 4) >= 2 GiB)");
 		}

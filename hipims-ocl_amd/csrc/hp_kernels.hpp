@@ -2,6 +2,7 @@
 #pragma once
 
 #include "hp_math.hpp"
+#include "hp_tiling.hpp"
 
 namespace hp {
 
@@ -570,8 +571,6 @@ __device__ __forceinline__ void buf_store_state(const State4<float>& s, __amdgpu
 	store_fence(a, voff, soff);
 }
 
-constexpr int MARCH_COLS = 62;          // updated columns per wavefront (lanes 1..62)
-
 // Neighbour-lane moves.  A lane's column neighbours live in the adjacent lanes of the same wavefront; their values
 // arrive through DPP wavefront ROTATES (one v_mov_b32_dpp per dword, a VALU instruction) instead of a trip through the
 // LDS crossbar (ds_bpermute: an LDS instruction, an address VGPR and an lgkmcnt wait per batch).  A rotate, not a shift
@@ -617,27 +616,7 @@ __device__ __forceinline__ Side<T> side_from_east(const Side<T>& s)
 	return r;
 }
 
-// How one launch's blocks map to tiles.  A launch covers the updated rows [y_begin, y_end) of the domain (all of them,
-// or the interior / one halo block of a strip-decomposed step: hp_engine.hip).  The rows are cut into 8 bands, one per
-// XCD (blocks are dealt round-robin to the XCDs, so blockIdx & 7 IS the XCD: its blocks walk one contiguous band and
-// the halo rows of neighbouring tiles are hits in that XCD's L2).  Inside a band the first `nbig` row segments are
-// `rseg` rows tall and the last `ntail` segments only `rseg_tail`: blocks start in blockIdx order, so the short
-// tiles are what is running when the band drains, and the tail of the launch is one SHORT tile long instead of one
-// tall tile (a tall tile lasts ~48 us at 4096^2 -- 18 % of the launch, measured as the intercept of
-// time-vs-cells between 4096^2 and 16384 x 8192).
-struct TileMap {
-	int  nstrips, groups;        // 62/60-column strips of the grid, and 4-wave groups of them
-	long y_begin, y_end;         // updated rows covered by this launch
-	int  nbands;                 // 8 (one band per XCD); 2 for the halo launch of a strip (south block, north block)
-	long band_stride;            // distance between band starts (= band_rows, except for the halo launch)
-	int  band_rows;              // rows per band
-	int  rseg, nbig;             // tall segments per band
-	int  rseg_tail, ntail;       // short segments per band (after the tall ones)
-	int  price_lo, price_hi;     // rows whose cells the fused CFL epilogue prices: the rows this rank OWNS (a strip with two
-	                             // reaches of ghost rows also updates rows it does not own, hp_engine.hip: strip loop); 32-bit so
-	                             // that the per-row test is two scalar compares
-	int  flip;                   // this launch visits the tiles of every band from the top down (hp_engine.hip: sweep_flip)
-};
+// (struct TileMap -- how one launch's blocks map to tiles -- is in hp_tiling.hpp, with the host code that fills it)
 
 // rows [y0, y1) and the column strip of this wave; false if the block / wave has nothing to do (wave-uniform)
 __device__ __forceinline__ bool tile_rows(const TileMap& tm, const int wave, long& strip, long& y0, long& y1)
@@ -1212,7 +1191,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(march_waves
 //  The pass writes into the OTHER buffer; the host then swaps the two pointers (hp_engine.hip: run_pair), so "primary" is again
 //  the buffer that holds the newest state, as after two single iterations.
 // -------------------------------------------------------------------------------------------------
-constexpr int MARCH2_COLS = 60;          // updated columns per wavefront (lanes 2..61)
 template <typename T> struct RowU1 { State4<T> c; T zb; bool plain; };      // plain: c IS the cell's source value, bit for bit (nothing touched it at the first step)
 
 // HZ: the instantiation that keeps quirk Q3 EXACT across pair launches (the stamps, PairAux).  What it costs the march -- a vote that joins
@@ -1962,8 +1940,6 @@ __global__ __launch_bounds__(256) void rings_compare(const State4<T>* __restrict
 //  Unlike the reference's in-place corrector (whose result depends on work-item order, quirk Q6) the update reads
 //  `src` and writes `dst`; cells the reference leaves untouched are copied.
 // -------------------------------------------------------------------------------------------------
-constexpr int MUSCL_COLS = 60;
-
 template <typename T>
 __device__ __forceinline__ Raw<T> raw_of(const RowRegs<T>& r) { return Raw<T>{r.c.z, r.c.zmax, r.c.qx, r.c.qy, r.zb}; }
 
