@@ -6,6 +6,7 @@
 #include "../../include/hipims_mi.h"
 #include "hp_kernels.hpp"
 #include "hp_output.hpp"
+#include "hp_peaks.hpp"
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 #include <dlfcn.h>
@@ -207,6 +208,17 @@ struct hp_domain {
 	size_t           out_scratch_bytes = 0;
 	void*            out_stats = nullptr;             // STATS_MAX_BLOCKS block partials + the folded result
 	void*            out_stats_host = nullptr;        // pinned: the folded result
+	// the peak tracker (hp_peaks.hpp; hp_peaks_*): nothing of it exists while tracking is off
+	bool             peaks_on = false;
+	unsigned         peaks_mask = 0;                  // HP_PEAK_* bits enabled
+	int              peaks_count = 0;                 // ... how many: the accumulators lie one after the other in peaks_acc, in code order
+	double           peaks_arrival = 0.0;
+	double*          peaks_acc = nullptr;             // peaks_count x cells fp64, followed by the PeakBlock
+	uint64_t         peaks_samples = 0;               // samples queued since enable / reset (its parity picks the time slot)
+	uint64_t         peaks_epoch = 0;                 // counts enable / disable: a checkpoint's peaks belong to one epoch
+	void*            saved_peaks = nullptr;           // hp_state_save's copy of peaks_acc (accumulators + block)
+	bool             saved_peaks_valid = false;
+	uint64_t         saved_peaks_epoch = 0, saved_peaks_samples = 0;
 };
 
 namespace {
@@ -1212,6 +1224,70 @@ int derive_blocks(hp_domain* d, const int* values, const int count, void* const*
 	return HP_OK;
 }
 
+// The raster scratch of the output stage, at least `need` bytes.  The new block first: if it cannot be had, the smaller one
+// that served so far stays.
+int out_scratch_reserve(hp_domain* d, const size_t need, const char* who)
+{
+	if (need <= d->out_scratch_bytes) return HP_OK;
+	void* grown = nullptr;
+	const hipError_t e = hipMalloc(&grown, need);
+	if (e != hipSuccess) {
+		(void)hipGetLastError();                                      // (the launches of later steps ask for the last error: this one is dealt with here)
+		return fail(HP_ERR_HIP, std::string(who) + ": cannot allocate " + std::to_string(need) + " bytes of raster scratch: " + hipGetErrorString(e));
+	}
+	if (d->out_scratch) {
+		hipError_t e2 = hipStreamSynchronize(d->stream);              // (an earlier call's copies may still be reading the old block)
+		if (e2 == hipSuccess) e2 = hipFree(d->out_scratch);
+		if (e2 != hipSuccess) { hipFree(grown); return fail(HP_ERR_HIP, std::string(who) + ": releasing the raster scratch: " + hipGetErrorString(e2)); }
+	}
+	d->out_scratch = grown;
+	d->out_scratch_bytes = need;
+	return HP_OK;
+}
+
+// ---- the peak tracker (hp_peaks.hpp) ----
+static_assert(PEAK_VALUES == HP_PEAK_COUNT && PEAK_SPEED == HP_PEAK_SPEED && PEAK_UNIT_DISCHARGE == HP_PEAK_UNIT_DISCHARGE &&
+              PEAK_HAZARD == HP_PEAK_HAZARD && PEAK_ARRIVAL_TIME == HP_PEAK_ARRIVAL_TIME && PEAK_WET_DURATION == HP_PEAK_WET_DURATION,
+              "hp_peaks.hpp and hipims_mi.h disagree");
+static_assert(sizeof(hp_peaks_desc_t) == 16, "hp_peaks_desc_t layout");
+constexpr size_t HOST_PEAKS = 128;           // byte offset in the pinned block: the PeakBlock read back by hp_peaks_info
+
+inline size_t peaks_bytes(const hp_domain* d) { return (size_t)d->peaks_count * d->cells * sizeof(double) + sizeof(PeakBlock); }
+inline PeakBlock* peaks_block(const hp_domain* d) { return (PeakBlock*)(d->peaks_acc + (size_t)d->peaks_count * d->cells); }
+// accumulator raster of an enabled value: they lie in code order
+inline double* peaks_raster(const hp_domain* d, const int value)
+{
+	return d->peaks_acc + (size_t)__builtin_popcount(d->peaks_mask & ((1u << value) - 1u)) * d->cells;
+}
+// a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
+inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
+
+int peaks_reset_queue(hp_domain* d)
+{
+	const size_t n = (size_t)d->peaks_count * d->cells;
+	if (d->desc.precision == 8)
+		hipLaunchKernelGGL((peaks_reset<double>), dim3(stream_blocks(n)), dim3(256), 0, d->stream, d->peaks_acc, n, (const Scalars<double>*)d->scalars, peaks_block(d));
+	else
+		hipLaunchKernelGGL((peaks_reset<float>), dim3(stream_blocks(n)), dim3(256), 0, d->stream, d->peaks_acc, n, (const Scalars<float>*)d->scalars, peaks_block(d));
+	HIP_TRY(hipGetLastError());
+	d->peaks_samples = 0;
+	return HP_OK;
+}
+
+// frees the tracker (the stream is drained first: queued samples and reads still use the accumulators)
+int peaks_release(hp_domain* d)
+{
+	if (!d->peaks_on && !d->saved_peaks) return HP_OK;
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	hipFree(d->peaks_acc); hipFree(d->saved_peaks);
+	d->peaks_acc = nullptr; d->saved_peaks = nullptr;
+	d->saved_peaks_valid = false;
+	if (d->peaks_on) ++d->peaks_epoch;
+	d->peaks_on = false;
+	d->peaks_mask = 0; d->peaks_count = 0; d->peaks_samples = 0;
+	return HP_OK;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -1395,6 +1471,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
 	hipFree(d->out_scratch); hipFree(d->out_stats);
+	hipFree(d->peaks_acc); hipFree(d->saved_peaks);
 	if (d->out_stats_host) hipHostFree(d->out_stats_host);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
@@ -1468,6 +1545,15 @@ int hp_state_save(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_save between hp_step_begin and hp_step_end");
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
+	// the copy of the peak accumulators first: if it cannot be had the call fails with the checkpoint before it, state and peaks, untouched
+	if (d->peaks_on && !d->saved_peaks) {
+		const hipError_t e = hipMalloc(&d->saved_peaks, peaks_bytes(d));
+		if (e != hipSuccess) {
+			d->saved_peaks = nullptr;
+			(void)hipGetLastError();
+			return fail(HP_ERR_HIP, std::string("hp_state_save: cannot allocate the copy of the peak accumulators: ") + hipGetErrorString(e));
+		}
+	}
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1488,6 +1574,14 @@ int hp_state_save(hp_domain_t* d)
 	d->saved_m1_valid = d->m1_valid;
 	d->saved_ghost_valid = d->ghost_valid;
 	d->saved_valid = true;
+	// the peak tracker, while it is on: accumulators and block in one copy
+	d->saved_peaks_valid = false;
+	if (d->peaks_on) {
+		HIP_TRY(hipMemcpyAsync(d->saved_peaks, d->peaks_acc, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
+		d->saved_peaks_epoch = d->peaks_epoch;
+		d->saved_peaks_samples = d->peaks_samples;
+		d->saved_peaks_valid = true;
+	}
 	return HP_OK;
 }
 
@@ -1529,6 +1623,16 @@ int hp_state_restore(hp_domain_t* d)
 	d->need_full_reduce = d->need_full_reduce || d->saved_full_reduce;
 	d->edge_dirty = d->edge_dirty || d->saved_edge_dirty;
 	d->fork_is_advance = false;
+	if (d->peaks_on) {
+		if (d->saved_peaks_valid && d->saved_peaks_epoch == d->peaks_epoch) {
+			HIP_TRY(hipMemcpyAsync(d->peaks_acc, d->saved_peaks, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
+			d->peaks_samples = d->saved_peaks_samples;
+		} else {
+			// (the time block has come back above: t_previous is the restored time)
+			if ((rc = peaks_reset_queue(d)) != HP_OK) return rc;
+			log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no peaks (the tracker was enabled after it was taken): the peaks are reset");
+		}
+	}
 	return HP_OK;
 }
 
@@ -1573,22 +1677,7 @@ int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_b
 	const size_t row_bytes = (size_t)d->desc.cols * (size_t)count * (size_t)element_bytes;      // of all requested rasters together
 	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
 	const size_t need = (size_t)block_rows * row_bytes;
-	if (need > d->out_scratch_bytes) {
-		// the new block first: if it cannot be had, the smaller one that served so far stays
-		void* grown = nullptr;
-		const hipError_t e = hipMalloc(&grown, need);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();                                      // (the launches of later steps ask for the last error: this one is dealt with here)
-			return fail(HP_ERR_HIP, "hp_domain_derive: cannot allocate " + std::to_string(need) + " bytes of raster scratch: " + hipGetErrorString(e));
-		}
-		if (d->out_scratch) {
-			hipError_t e2 = hipStreamSynchronize(d->stream);              // (an earlier call's copies may still be reading the old block)
-			if (e2 == hipSuccess) e2 = hipFree(d->out_scratch);
-			if (e2 != hipSuccess) { hipFree(grown); return fail(HP_ERR_HIP, std::string("hp_domain_derive: releasing the raster scratch: ") + hipGetErrorString(e2)); }
-		}
-		d->out_scratch = grown;
-		d->out_scratch_bytes = need;
-	}
+	if ((rc = out_scratch_reserve(d, need, "hp_domain_derive")) != HP_OK) return rc;
 	if (d->desc.precision == 8)
 		return element_bytes == 8 ? derive_blocks<double, double>(d, values, count, rasters, row0, nrows, block_rows)
 		                          : derive_blocks<double, float>(d, values, count, rasters, row0, nrows, block_rows);
@@ -1643,6 +1732,134 @@ int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats
 	out->volume = d->desc.dx * d->desc.dx * s.sum;
 	if (s.depth_cell != ~0ull) { out->max_depth = s.max_depth; out->max_depth_cell = s.depth_cell; }
 	if (s.speed_cell != ~0ull) { out->max_speed = s.max_speed; out->max_speed_cell = s.speed_cell; }
+	return HP_OK;
+}
+
+// ---- the peak tracker (hp_peaks.hpp) ----
+int hp_peaks_enable(hp_domain_t* d, const hp_peaks_desc_t* desc)
+{
+	if (!desc) return fail(HP_ERR_INVALID, "hp_peaks_enable: desc == NULL");
+	if (desc->struct_size != sizeof(hp_peaks_desc_t)) return fail(HP_ERR_INVALID, "hp_peaks_desc_t size mismatch (ABI)");
+	if (desc->values_mask == 0) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask is empty");
+	if (desc->values_mask >> HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask names an unknown value");
+	if (!(desc->arrival_depth >= OUT_WET)) return fail(HP_ERR_INVALID, "hp_peaks_enable: arrival_depth must be at least 1e-8");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_enable between hp_step_begin and hp_step_end");
+	if ((rc = peaks_release(d)) != HP_OK) return rc;
+	d->peaks_count = __builtin_popcount(desc->values_mask);
+	const hipError_t e = hipMalloc((void**)&d->peaks_acc, peaks_bytes(d));
+	if (e != hipSuccess) {
+		d->peaks_acc = nullptr; d->peaks_count = 0;
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, std::string("hp_peaks_enable: cannot allocate the accumulators: ") + hipGetErrorString(e));
+	}
+	d->peaks_mask = desc->values_mask;
+	d->peaks_arrival = desc->arrival_depth;
+	d->peaks_on = true;
+	++d->peaks_epoch;
+	if ((rc = peaks_reset_queue(d)) != HP_OK) { peaks_release(d); return rc; }
+	return HP_OK;
+}
+
+int hp_peaks_disable(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	return peaks_release(d);
+}
+
+int hp_peaks_reset(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_reset before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_reset between hp_step_begin and hp_step_end");
+	return peaks_reset_queue(d);
+}
+
+int hp_peaks_sample(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK) return rc;
+	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_sample before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_sample between hp_step_begin and hp_step_end");
+	PeakTargets t = {};
+	for (int v = 0; v < HP_PEAK_COUNT; ++v)
+		if (d->peaks_mask & (1u << v)) t.acc[v] = peaks_raster(d, v);
+	t.mask = d->peaks_mask;
+	t.arrival_depth = d->peaks_arrival;
+	const unsigned sample = (unsigned)(d->peaks_samples & 1u);          // picks the time slot; `first`: the first sample since enable / reset
+	const int first = d->peaks_samples == 0;
+	const unsigned blocks = stream_blocks(d->cells);
+	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
+	if (d->desc.precision == 8)
+		hipLaunchKernelGGL((track_peaks<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed,
+		                   (const Scalars<double>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
+	else
+		hipLaunchKernelGGL((track_peaks<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed,
+		                   (const Scalars<float>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
+	HIP_TRY(hipGetLastError());
+	++d->peaks_samples;
+	return HP_OK;
+}
+
+int hp_peaks_read(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
+{
+	// argument checks first, as in hp_domain_derive: none of them touches the device
+	if (count < 1 || count > HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_read: count outside 1..HP_PEAK_COUNT");
+	if (!values || !rasters) return fail(HP_ERR_INVALID, "hp_peaks_read: values / rasters == NULL");
+	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, "hp_peaks_read: element_bytes must be 4 or 8");
+	unsigned seen = 0;
+	for (int k = 0; k < count; ++k) {
+		if (values[k] < 0 || values[k] >= HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_read: unknown value " + std::to_string(values[k]));
+		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, "hp_peaks_read: value " + std::to_string(values[k]) + " listed twice");
+		seen |= 1u << values[k];
+		if (!rasters[k]) return fail(HP_ERR_INVALID, "hp_peaks_read: rasters[" + std::to_string(k) + "] == NULL");
+	}
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_read before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_read between hp_step_begin and hp_step_end");
+	if (seen & ~d->peaks_mask) return fail(HP_ERR_INVALID, "hp_peaks_read: a value that hp_peaks_enable's values_mask does not track");
+	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
+	if (nrows == 0) return HP_OK;
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	const size_t cols = (size_t)d->desc.cols;
+	if (element_bytes == 8) {                                             // whole rows are contiguous: the accumulators themselves
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync(rasters[k], peaks_raster(d, values[k]) + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double),
+			                       hipMemcpyDeviceToHost, d->stream));
+		return HP_OK;
+	}
+	const size_t row_bytes = cols * (size_t)count * sizeof(float);
+	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
+	if ((rc = out_scratch_reserve(d, (size_t)block_rows * row_bytes, "hp_peaks_read")) != HP_OK) return rc;
+	for (int64_t r = 0; r < nrows; r += block_rows) {
+		const size_t n = (size_t)std::min<int64_t>(block_rows, nrows - r) * cols;
+		for (int k = 0; k < count; ++k) {
+			float* out = (float*)d->out_scratch + (size_t)k * n;
+			hipLaunchKernelGGL(peaks_round, dim3(stream_blocks(n)), dim3(256), 0, d->stream,
+			                   (const double*)(peaks_raster(d, values[k]) + (size_t)(row0 + r) * cols), out, n);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)r * cols * sizeof(float), out, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+		}
+	}
+	return HP_OK;
+}
+
+int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_last)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_info before hp_peaks_enable");
+	PeakBlock* host = (PeakBlock*)((char*)d->host_scalars + HOST_PEAKS);
+	HIP_TRY(hipMemcpyAsync(host, peaks_block(d), sizeof(PeakBlock), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	if (samples) *samples = d->peaks_samples;
+	if (t_first) *t_first = host->t_first;
+	if (t_last) *t_last = host->slot[d->peaks_samples & 1u];                 // (sample n - 1 stored its time into slot n & 1)
 	return HP_OK;
 }
 

@@ -31,12 +31,17 @@ PTR_STATE_NEXT_SRC, PTR_STATE_OTHER, PTR_BED, PTR_MANNING, PTR_CFL_MAX, PTR_SCAL
 # the front end's value names (frontend.data_value_code) -> HP_OUT_*
 OUT_CODES = {"depth": OUT_DEPTH, "maxdepth": OUT_MAXDEPTH, "fsl": OUT_FSL, "maxfsl": OUT_MAXFSL, "dischargex": OUT_DISCHARGE_X,
              "dischargey": OUT_DISCHARGE_Y, "velocityx": OUT_VELOCITY_X, "velocityy": OUT_VELOCITY_Y, "froude": OUT_FROUDE}
+(PEAK_SPEED, PEAK_UNIT_DISCHARGE, PEAK_HAZARD, PEAK_ARRIVAL_TIME, PEAK_WET_DURATION, PEAK_COUNT) = range(6)
+# the front end's peak value names (frontend.peak_value_code) -> HP_PEAK_*
+PEAK_CODES = {"peakspeed": PEAK_SPEED, "peakunitdischarge": PEAK_UNIT_DISCHARGE, "hazard": PEAK_HAZARD,
+              "arrivaltime": PEAK_ARRIVAL_TIME, "wetduration": PEAK_WET_DURATION}
 NO_CELL = 2 ** 64 - 1          # hp_domain_stats_t: "no such cell"
 
 EXPORTS = [
     "hp_abi_version", "hp_device_count", "hp_device_info", "hp_last_error", "hp_set_log_sink", "hp_domain_desc_default",
     "hp_domain_create", "hp_domain_destroy", "hp_domain_upload", "hp_domain_download", "hp_domain_upload_rows", "hp_state_save", "hp_state_restore",
     "hp_domain_derive", "hp_domain_stats",
+    "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -101,6 +106,10 @@ class DomainStats(C.Structure):
                 ("max_depth_cell", C.c_uint64), ("max_speed_cell", C.c_uint64)]
 
 
+class PeaksDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("values_mask", C.c_uint32), ("arrival_depth", C.c_double)]
+
+
 _lib = None
 
 
@@ -136,6 +145,13 @@ def load_library(path: str | None = None):
     if hasattr(lib, "hp_domain_derive"):                # (absent from older builds loaded through HIPIMS_MI_LIB for A/B runs: calling it there raises)
         lib.hp_domain_derive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
         lib.hp_domain_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DomainStats)]
+    if hasattr(lib, "hp_peaks_enable"):                 # (absent from older builds, as above)
+        lib.hp_peaks_enable.argtypes = [C.c_void_p, C.POINTER(PeaksDesc)]
+        lib.hp_peaks_disable.argtypes = [C.c_void_p]
+        lib.hp_peaks_reset.argtypes = [C.c_void_p]
+        lib.hp_peaks_sample.argtypes = [C.c_void_p]
+        lib.hp_peaks_read.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
+        lib.hp_peaks_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -274,6 +290,7 @@ class Domain:
         _check(self.lib, self.lib.hp_domain_create(C.byref(desc), C.byref(self.h)), "hp_domain_create")
         self._keepalive = []
         self._bed_host = None
+        self._peak_values = []                          # HP_PEAK_* codes the library tracks (peaks_enable's mask)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -355,6 +372,70 @@ class Domain:
         return dict(cells=s.cells, cells_wet=s.cells_wet, volume=s.volume, max_depth=s.max_depth, max_speed=s.max_speed,
                     max_depth_cell=None if s.max_depth_cell == NO_CELL else s.max_depth_cell,
                     max_speed_cell=None if s.max_speed_cell == NO_CELL else s.max_speed_cell)
+
+    # ---- the peak tracker (hp_peaks_*): maxima over the SAMPLES the host takes between batches ----
+    @staticmethod
+    def _peak_codes(values):
+        names = [values] if isinstance(values, str) else list(values)
+        codes = []
+        for name in names:
+            code = name if isinstance(name, int) else PEAK_CODES.get(str(name).lower())
+            if code is None or not 0 <= code < PEAK_COUNT:
+                raise ValueError(f"unknown peak value {name}")
+            codes.append(code)
+        return names, codes
+
+    def peaks_enable(self, values, arrival_depth=0.01):
+        """Start tracking `values` (names of PEAK_CODES or HP_PEAK_* codes): allocates one fp64 accumulator raster per value
+        on the device and resets them; t_previous of the first sample is the device time now."""
+        _, codes = self._peak_codes(values)
+        desc = PeaksDesc(C.sizeof(PeaksDesc), sum(1 << c for c in set(codes)), float(arrival_depth))
+        rc = self.lib.hp_peaks_enable(self.h, C.byref(desc))
+        if rc == -3:                                    # HP_ERR_HIP: the allocation failed and the library has switched tracking off
+            self._peak_values = []                      # (an argument or state error leaves the tracker as it was)
+        _check(self.lib, rc, "hp_peaks_enable")
+        self._peak_values = sorted(set(codes))
+
+    def peaks_disable(self):
+        _check(self.lib, self.lib.hp_peaks_disable(self.h), "hp_peaks_disable")
+        self._peak_values = []
+
+    def peaks_reset(self):
+        _check(self.lib, self.lib.hp_peaks_reset(self.h), "hp_peaks_reset")
+
+    def peaks_sample(self):
+        """Fold the current state into the accumulators: one launch on the domain's stream, never blocks."""
+        _check(self.lib, self.lib.hp_peaks_sample(self.h), "hp_peaks_sample")
+
+    def peaks(self, values=None, dtype=np.float64, row0=0, nrows=None):
+        """The peaks so far: {name: array[nrows, cols]} (values=None: every enabled value, by its PEAK_CODES name).  fp64
+        arrays are the accumulators, bit-identical to frontend.PeakTracker fed the same samples; dtype=np.float32 gives
+        those values rounded once."""
+        if values is None:
+            if not self._peak_values:
+                self.peaks_info()                       # not tracking: the library's own answer (HP_ERR_STATE), not an empty dict
+            by_code = {c: n for n, c in PEAK_CODES.items()}
+            values = [by_code[c] for c in self._peak_values]
+        names, codes = self._peak_codes(values)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32")
+        nrows = self.rows - row0 if nrows is None else nrows
+        arrays = [np.empty((max(0, nrows), self.cols), dtype) for _ in codes]
+        if codes:                                       # (also for nrows == 0: the library checks the range first)
+            c_values = (C.c_int * len(codes))(*codes)
+            c_rasters = (C.c_void_p * len(codes))(*[a.ctypes.data for a in arrays])
+            _check(self.lib, self.lib.hp_peaks_read(self.h, c_values, len(codes), dtype.itemsize, c_rasters, row0, nrows),
+                   "hp_peaks_read")
+            self.sync()
+        return dict(zip(names, arrays))
+
+    def peaks_info(self):
+        """dict(samples, t_first, t_last): samples taken since enable / reset and the model times of the first and the
+        last of them; blocks."""
+        n, t0, t1 = C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
+        _check(self.lib, self.lib.hp_peaks_info(self.h, C.byref(n), C.byref(t0), C.byref(t1)), "hp_peaks_info")
+        return dict(samples=n.value, t_first=t0.value, t_last=t1.value)
 
     def upload_rows(self, rows_state, row0):
         a = np.ascontiguousarray(rows_state, dtype=self.real)

@@ -283,6 +283,71 @@ def data_value_code(name):
     return None
 
 
+PEAK_NAMES = ("peakspeed", "peakunitdischarge", "hazard", "arrivaltime", "wetduration")     # = hipims_mi.PEAK_CODES, in code order
+
+
+def peak_value_code(name):
+    """The peak tracker's value names (no reference counterpart): exact matches, case-insensitive.  None of them contains a
+    substring data_value_code matches, so a <dataTarget> is either an output raster or a peak, never both."""
+    n = (name or "").strip().lower()
+    return n if n in PEAK_NAMES else None
+
+
+class PeakTracker:
+    """The peak tracker in NumPy, in exactly the device kernel's operation order (csrc/hp_peaks.hpp: track_peaks): the
+    reference the GPU tests compare against bit for bit, and the tracker of engines without the device path.  All arithmetic
+    in fp64; only add, multiply, divide, sqrt and compare.
+
+        reset(t)               NODATA everywhere, t_previous = t
+        fold(state, bed, t)    one sample: state[rows, cols, 4] = {Z, Zmax, Qx, Qy}, bed[rows, cols], t = the model time
+        rasters()              {name: array} of the five values so far
+    """
+
+    def __init__(self, rows, cols, arrival_depth=0.01, t=0.0):
+        if not arrival_depth >= 1e-8:
+            raise ValueError("arrival_depth must be at least 1e-8")
+        self.shape, self.arrival_depth = (int(rows), int(cols)), float(arrival_depth)
+        self.reset(t)
+
+    def reset(self, t):
+        self.acc = {name: np.full(self.shape, NODATA) for name in PEAK_NAMES}
+        self.t_previous = self.t_first = self.t_last = float(t)
+        self.samples = 0
+
+    def fold(self, state, bed, t):
+        z, zmax, qx, qy = (state[..., k].astype(np.float64) for k in range(4))
+        zb = np.asarray(bed).astype(np.float64)
+        t = float(t)
+        with np.errstate(all="ignore"):                                       # (cells that are not hit may hold anything)
+            self._fold(z, zmax, qx, qy, zb, t)
+        if self.samples == 0:
+            self.t_first = t
+        self.t_previous = self.t_last = t
+        self.samples += 1
+
+    def _fold(self, z, zmax, qx, qy, zb, t):
+        depth = z - zb
+        hit = (zmax > -9999.0) & (zb <= 9999.0) & (depth > 1e-8)             # counted (domain_stats) and wet (the output stage)
+        div = np.where(hit, depth, 1.0)                                       # (a dry cell's quotient is never formed)
+        vx, vy = qx / div, qy / div
+        v = np.sqrt(vx * vx + vy * vy)
+        for name, value in (("peakspeed", v), ("peakunitdischarge", np.sqrt(qx * qx + qy * qy)), ("hazard", depth * (v + 0.5))):
+            a = self.acc[name]
+            larger = hit & (value > a)
+            a[larger] = value[larger]
+        over = hit & (depth > self.arrival_depth)
+        a = self.acc["arrivaltime"]
+        a[over & (a == NODATA)] = t
+        a = self.acc["wetduration"]
+        a[over] = np.where(a[over] == NODATA, 0.0, a[over]) + (t - self.t_previous)
+
+    def rasters(self):
+        return {name: a.copy() for name, a in self.acc.items()}
+
+    def info(self):
+        return dict(samples=self.samples, t_first=self.t_first, t_last=self.t_last)
+
+
 def derive_output(what, state, bed, resolution=1.0):
     """Datasets/CRasterDataset.cpp:185-267."""
     code = data_value_code(what)

@@ -49,6 +49,7 @@ class SchemeDriver:
         self.queue_addition_size = 1
         self.rollback_limit = 999999999
         self.running = False
+        self.peak_sampler = None                                   # Model's: called after every batch queued (the peak tracker)
         self.prepare_simulation()
 
     # ---- adapters: Domain (HIP engine) and OracleSim spell a few things differently ----
@@ -150,6 +151,8 @@ class SchemeDriver:
                 self.iterations_since_sync += n
                 self.iterations += n
                 self.cells_calculated += n * self.cells            # :1299: cols x rows per iteration, skipped or not
+                if self.peak_sampler is not None:                  # one sample per batch, queued behind it (no reference counterpart)
+                    self.peak_sampler()
             self.read_key_statistics()                             # :1309-1313, blockUntilFinished, :1350
         finally:
             self.running = False
@@ -159,7 +162,7 @@ class Model:
     """CModel for one domain: `run()` is runModelMain."""
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
-                 clock=time.perf_counter, device_outputs=None):
+                 clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -192,8 +195,41 @@ class Model:
         if device_outputs and not hasattr(sim, "derive"):
             raise ValueError("device_outputs=True needs an engine with derive()")
         self.device_outputs = (hasattr(sim, "derive") and cfg.precision == "f64") if device_outputs is None else bool(device_outputs)
+        # The peak tracker (no reference counterpart): on for the <dataTarget> values that are peak names (frontend.peak_value_code)
+        # and for the names in `peaks`; one sample after every batch.  On the device (Domain.peaks_*) wherever the output rasters
+        # are derived there, for the same reason; otherwise frontend.PeakTracker on the downloaded state with the front end's bed.
+        self.peak_names = []
+        for what in peaks or []:
+            if frontend.peak_value_code(what) is None:
+                raise ValueError(f"unknown peak value {what}")
+        for what in [w for w, _ in cfg.targets] + list(peaks or []):
+            code = frontend.peak_value_code(what)
+            if code is not None and code not in self.peak_names:
+                self.peak_names.append(code)
+        self.host_peaks, self.device_peaks = None, False
+        if self.peak_names:
+            self.device_peaks = self.device_outputs and hasattr(sim, "peaks_enable")
+            if self.device_peaks:
+                sim.peaks_enable(self.peak_names, arrival_depth=peak_arrival_depth)
+                self.scheme.peak_sampler = sim.peaks_sample
+            else:
+                self.host_peaks = frontend.PeakTracker(self.rows, self.cols, peak_arrival_depth, t=self.scheme.current_time)
+                self.scheme.peak_sampler = self.sample_peaks_on_host
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
+
+    def sample_peaks_on_host(self):
+        s = self.scheme._call("read_scalars", "scalars")()
+        self.host_peaks.fold(self.sim.download(), self.bed, s["time"] if "time" in s else s["t"])
+
+    def peaks(self):
+        """{name: array} of the tracked peak values so far."""
+        if not self.peak_names:
+            return {}
+        if self.host_peaks is not None:
+            all_of_them = self.host_peaks.rasters()
+            return {name: all_of_them[name] for name in self.peak_names}
+        return self.sim.peaks(self.peak_names)
 
     # CModel::runModelUpdateTarget (:723-770), one domain: run free until the next output is due
     def update_target(self):
@@ -208,13 +244,19 @@ class Model:
             self.current_time > self.last_output_time
         if not due:
             return False
+        is_peak = [frontend.peak_value_code(what) is not None for what, _ in self.cfg.targets]
+        plain = [what for (what, _), pk in zip(self.cfg.targets, is_peak) if not pk]
         if self.device_outputs:                                    # every target in ONE call, rasters only over the host link
-            derived = self.sim.derive([what for what, _ in self.cfg.targets]) if self.cfg.targets else {}
-        else:
+            derived = self.sim.derive(plain) if plain else {}
+        elif plain or not self.cfg.targets:
             final = self.sim.download()
+        peaks = self.peaks()                                       # the peaks so far, written like maxdepth at every output time
         out = {}
         for k, (what, pattern) in enumerate(self.cfg.targets):
-            arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
+            if is_peak[k]:
+                arr = peaks[frontend.peak_value_code(what)]
+            else:
+                arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
             out[what] = arr
             if pattern and self.cfg.target_dir and self.output_format:
                 ext = self.output_format
@@ -223,6 +265,8 @@ class Model:
                     ext = ".img" if fmt == "HFA" else ".asc"
                 fname = os.path.splitext(pattern.replace("%t", str(int(round(self.current_time)))))[0] + ext
                 frontend.write_raster(os.path.join(self.cfg.target_dir, fname), arr, self.res)
+        for name, arr in peaks.items():                            # (asked for through Model(peaks=...) only: no file)
+            out.setdefault(name, arr)
         self.outputs.append((self.current_time, out))
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()

@@ -136,6 +136,25 @@ class HipEngine:
     def stats(self, row0=0, nrows=None):
         return self.domain.stats(row0=row0, nrows=nrows)
 
+    # the peak tracker (Domain.peaks_*)
+    def peaks_enable(self, values, arrival_depth=0.01):
+        self.domain.peaks_enable(values, arrival_depth=arrival_depth)
+
+    def peaks_disable(self):
+        self.domain.peaks_disable()
+
+    def peaks_reset(self):
+        self.domain.peaks_reset()
+
+    def peaks_sample(self):
+        self.domain.peaks_sample()
+
+    def peaks(self, values=None, dtype=np.float64, row0=0, nrows=None):
+        return self.domain.peaks(values, dtype=dtype, row0=row0, nrows=nrows)
+
+    def peaks_info(self):
+        return self.domain.peaks_info()
+
     def set_target_time(self, t):
         self.domain.set_target_time(t)
 
@@ -440,6 +459,22 @@ class StripRunner:
         mine = self.engine.derive(values, dtype=dtype, row0=self.own_lo - self.local_lo, nrows=self.own_hi - self.own_lo)
         parts = [None] * self.world if self.rank == 0 else None
         self.dist.gather_object(mine, parts, dst=0)                 # rasters travel to rank 0 only
+        return assemble_outputs(parts) if self.rank == 0 else None
+
+    # ---- the peak tracker: every rank tracks its own strip (ghost rows included: they hold their owners' values between
+    #      batches), nothing is exchanged; only owned rows are ever gathered ----
+    def peaks_enable(self, values, arrival_depth=0.01):
+        self.engine.peaks_enable(values, arrival_depth=arrival_depth)
+
+    def peaks_sample(self):
+        self.engine.peaks_sample()
+
+    def gather_peaks(self, values=None, dtype=np.float64):
+        """Peak rasters of the whole grid: every rank reads its OWNED rows (Domain.peaks), rank 0 gets {name: array[rows, cols]},
+        the other ranks None.  Like gather_outputs; collective."""
+        mine = self.engine.peaks(values, dtype=dtype, row0=self.own_lo - self.local_lo, nrows=self.own_hi - self.own_lo)
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
         return assemble_outputs(parts) if self.rank == 0 else None
 
     def gather_stats(self):

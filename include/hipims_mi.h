@@ -199,6 +199,55 @@ typedef struct {
 } hp_domain_stats_t;
 int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats_t* out);   /* BLOCKS */
 
+/* ---- the peak tracker: run-long maps a final state cannot give (no reference counterpart; closest: the Zmax field,
+ *      CLSchemeGodunov.clc, the one run-long quantity the flux kernels carry because the reference does).
+ *      Opt-in.  A set of fp64 accumulator rasters in device memory (8 bytes per cell and enabled value) into which one kernel
+ *      folds the current state each time the host asks for a sample.  The maxima are maxima over the SAMPLES, not over the
+ *      iterations: the host chooses the cadence, and a sample is only ever taken between batches (inside hp_step_batch every
+ *      iteration but the last carries its successor's rain, and an iteration pair never materialises its middle state).  A
+ *      sample reads the buffer hp_domain_download(HP_ARRAY_STATE) reads and the device's own "Time" scalar, in stream order
+ *      behind whatever is queued, without any host synchronisation, and changes nothing the steps depend on: a tracked run's
+ *      trajectory is the untracked run's, bit for bit.  With tracking off nothing is allocated or launched.
+ *      Conventions of the output stage: all arithmetic in fp64 whatever the domain's precision (an fp32 domain's values are
+ *      widened first), correctly rounded operations only (add, multiply, divide, square root, compare), NODATA = -9999,
+ *      depth = Z - bed, wet = depth > 1e-8, v = sqrt((Qx / depth)^2 + (Qy / depth)^2).  A cell is counted exactly as in
+ *      hp_domain_stats (Zmax > -9999 and bed <= 9999); a sample changes only cells that are counted and wet in it, so cells
+ *      that are never counted stay NODATA in every value.
+ *        HP_PEAK_SPEED           largest v over the samples in which the cell was wet; NODATA if never wet
+ *        HP_PEAK_UNIT_DISCHARGE  largest sqrt(Qx^2 + Qy^2) over those samples
+ *        HP_PEAK_HAZARD          largest depth * (v + 0.5) over those samples (the DEFRA/EA FD2320 rating without the debris term)
+ *        HP_PEAK_ARRIVAL_TIME    model time of the first sample with depth > arrival_depth; NODATA if none
+ *        HP_PEAK_WET_DURATION    sum of (t_sample - t_previous_sample) over the samples with depth > arrival_depth (right-endpoint
+ *                                rule), added in sample order; NODATA if none.  The first sample's t_previous is the device time at
+ *                                hp_peaks_enable / hp_peaks_reset; samples at a suspended sync point repeat the time and add 0. ---- */
+enum { HP_PEAK_SPEED = 0, HP_PEAK_UNIT_DISCHARGE = 1, HP_PEAK_HAZARD = 2, HP_PEAK_ARRIVAL_TIME = 3, HP_PEAK_WET_DURATION = 4,
+       HP_PEAK_COUNT = 5 };
+typedef struct {
+	uint32_t struct_size;        /* = sizeof(hp_peaks_desc_t) */
+	uint32_t values_mask;        /* bit v: HP_PEAK_* value v is tracked; at least one, none beyond HP_PEAK_COUNT */
+	double   arrival_depth;      /* metres; at least 1e-8 (a cell that is dry in a sample changes nothing).  Typical: 0.01 */
+} hp_peaks_desc_t;
+/* Allocates the accumulators of values_mask (and only those) and resets them; on a domain that is already tracking, the old set
+ * is freed first.  If the allocation fails the call returns HP_ERR_HIP and the domain stays usable with tracking off. */
+int hp_peaks_enable(hp_domain_t* d, const hp_peaks_desc_t* desc);
+int hp_peaks_disable(hp_domain_t* d);                  /* frees; idempotent (also done by hp_domain_destroy) */
+/* NODATA everywhere, sample count 0, t_previous = the device time now; enqueued.  hp_domain_upload does not touch the peaks:
+ * a host that replaces the state resets them itself if it wants to. */
+int hp_peaks_reset(hp_domain_t* d);
+/* One sample: enqueued on the domain's stream, never blocks.  HP_ERR_STATE before hp_peaks_enable and between hp_step_begin
+ * and hp_step_end. */
+int hp_peaks_sample(hp_domain_t* d);
+/* hp_domain_derive's contract: rasters[i] receives value values[i] (each at most once, each one of the enabled ones) for rows
+ * [row0, row0 + nrows) of the LOCAL array, element_bytes 8 (the accumulators: a plain device-to-host copy) or 4 (those values
+ * rounded once, through the output stage's bounded scratch in blocks of rows).  Reads in stream order behind the queued
+ * samples; the host memory must stay alive until hp_sync().  Argument errors are HP_ERR_INVALID before any device call,
+ * a read before hp_peaks_enable or inside a split step is HP_ERR_STATE; nrows == 0 is HP_OK. */
+int hp_peaks_read(hp_domain_t* d, const int* values, int count, int element_bytes,
+                  void* const* rasters, int64_t row0, int64_t nrows);
+/* Samples taken since enable / reset and the model times of the first and the last of them (both the time at enable / reset
+ * while there is none).  Any of the three pointers may be NULL.  BLOCKS. */
+int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_last);
+
 /* Device-side checkpoint: what saveCurrentState + rollbackSimulation do through host memory (CSchemeGodunov.cpp:1720-1736,
  * :1474-1518), kept in HBM instead (two more copies of a 4096^2 fp64 state are 1 GB of 288).  hp_state_save copies BOTH
  * ping-pong buffers and the time-control block; hp_state_restore puts each buffer, the time-control block, the ping-pong phase
@@ -206,7 +255,10 @@ int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats
  * writes the saved next-source state into both buffers; cells whose whole neighbourhood is dry, which the flux kernel leaves
  * untouched -- quirk Q3 --, then continue from other values than in the original run.  A host that wants exactly that uploads
  * the state it downloaded, as CSchemeMI::rollbackSimulation does.)  The host may then adjust time / target / timestep with the calls
- * below, exactly as the reference's rollback sequence does. */
+ * below, exactly as the reference's rollback sequence does.
+ * While the peak tracker is on, hp_state_save also snapshots its accumulators and its own block and hp_state_restore puts
+ * them back: the samples that follow repeat the original ones bit for bit.  A snapshot taken before the tracker was enabled,
+ * disabled or re-enabled holds no peaks: hp_state_restore then resets them and sends one HP_LOG_WARNING to the log sink. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
