@@ -7,6 +7,7 @@
 #include "hp_kernels.hpp"
 #include "hp_output.hpp"
 #include "hp_peaks.hpp"
+#include "hp_probes.hpp"
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 #include <dlfcn.h>
@@ -219,6 +220,16 @@ struct hp_domain {
 	void*            saved_peaks = nullptr;           // hp_state_save's copy of peaks_acc (accumulators + block)
 	bool             saved_peaks_valid = false;
 	uint64_t         saved_peaks_epoch = 0, saved_peaks_samples = 0;
+	// the probe recorder (hp_probes.hpp; hp_probes_*): nothing of it exists while recording is off
+	bool             probes_on = false;
+	void*            probes_mem = nullptr;            // the lists (probes_lists points into it)
+	double*          probes_records = nullptr;        // probes_capacity records of probes_stride fp64 words
+	ProbeLists       probes_lists = {};
+	uint64_t         probes_capacity = 0, probes_stride = 0;
+	uint64_t         probes_samples = 0;              // records queued since enable / reset: the next sample's index
+	uint64_t         probes_epoch = 0;                // counts enable / disable / reset: a checkpoint's count belongs to one epoch
+	bool             saved_probes_valid = false;
+	uint64_t         saved_probes_epoch = 0, saved_probes_samples = 0;
 };
 
 namespace {
@@ -1288,6 +1299,25 @@ int peaks_release(hp_domain* d)
 	return HP_OK;
 }
 
+// ---- the probe recorder (hp_probes.hpp) ----
+static_assert(sizeof(hp_probes_desc_t) == 64, "hp_probes_desc_t layout");
+constexpr uint64_t PROBES_MAX_GAUGES = 65536, PROBES_MAX_SECTIONS = 1024;
+constexpr uint64_t PROBES_MAX_BYTES = 256ull << 20;                        // of the record buffer
+
+// frees the recorder (the stream is drained first: queued samples and reads still use the lists and the records)
+int probes_release(hp_domain* d)
+{
+	if (!d->probes_on) return HP_OK;
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	hipFree(d->probes_mem); hipFree(d->probes_records);
+	d->probes_mem = nullptr; d->probes_records = nullptr;
+	d->probes_lists = ProbeLists{};
+	d->probes_on = false;
+	d->probes_capacity = d->probes_stride = d->probes_samples = 0;
+	++d->probes_epoch;
+	return HP_OK;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -1472,6 +1502,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
 	hipFree(d->out_scratch); hipFree(d->out_stats);
 	hipFree(d->peaks_acc); hipFree(d->saved_peaks);
+	hipFree(d->probes_mem); hipFree(d->probes_records);
 	if (d->out_stats_host) hipHostFree(d->out_stats_host);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
@@ -1582,6 +1613,10 @@ int hp_state_save(hp_domain_t* d)
 		d->saved_peaks_samples = d->peaks_samples;
 		d->saved_peaks_valid = true;
 	}
+	// the probe recorder: the sample count only (the records taken after it are re-recorded by the samples a restore repeats)
+	d->saved_probes_valid = d->probes_on;
+	d->saved_probes_epoch = d->probes_epoch;
+	d->saved_probes_samples = d->probes_samples;
 	return HP_OK;
 }
 
@@ -1631,6 +1666,14 @@ int hp_state_restore(hp_domain_t* d)
 			// (the time block has come back above: t_previous is the restored time)
 			if ((rc = peaks_reset_queue(d)) != HP_OK) return rc;
 			log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no peaks (the tracker was enabled after it was taken): the peaks are reset");
+		}
+	}
+	if (d->probes_on) {
+		if (d->saved_probes_valid && d->saved_probes_epoch == d->probes_epoch) {
+			d->probes_samples = d->saved_probes_samples;
+		} else {
+			d->probes_samples = 0;
+			log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no probe sample count (the recorder was enabled or reset after it was taken): the count is 0");
 		}
 	}
 	return HP_OK;
@@ -1860,6 +1903,154 @@ int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_
 	if (samples) *samples = d->peaks_samples;
 	if (t_first) *t_first = host->t_first;
 	if (t_last) *t_last = host->slot[d->peaks_samples & 1u];                 // (sample n - 1 stored its time into slot n & 1)
+	return HP_OK;
+}
+
+// ---- the probe recorder (hp_probes.hpp) ----
+int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
+{
+	// argument checks first: none of them touches the device
+	if (!desc) return fail(HP_ERR_INVALID, "hp_probes_enable: desc == NULL");
+	if (desc->struct_size != sizeof(hp_probes_desc_t)) return fail(HP_ERR_INVALID, "hp_probes_desc_t size mismatch (ABI)");
+	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: capacity must be at least 1");
+	const uint64_t G = desc->gauge_count, S = desc->section_count;
+	if (G > PROBES_MAX_GAUGES) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 65536 gauges");
+	if (S > PROBES_MAX_SECTIONS) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 1024 sections");
+	if (G + S < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: neither a gauge nor a section");
+	if (G && !desc->gauge_cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge_cells == NULL");
+	if (S && (!desc->section_offsets || !desc->section_cells || !desc->section_wx || !desc->section_wy))
+		return fail(HP_ERR_INVALID, "hp_probes_enable: a section array == NULL");
+	const uint64_t stride = 1 + PROBE_GAUGE_WORDS * G + S;
+	if ((uint64_t)desc->capacity * stride * sizeof(double) > PROBES_MAX_BYTES)
+		return fail(HP_ERR_INVALID, "hp_probes_enable: capacity x stride x 8 exceeds 256 MiB");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const uint64_t cells = d->cells;
+	for (uint64_t g = 0; g < G; ++g)
+		if (desc->gauge_cells[g] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge " + std::to_string(g) + ": cell id outside the local array");
+	uint64_t M = 0;
+	if (S) {
+		if (desc->section_offsets[0] != 0) return fail(HP_ERR_INVALID, "hp_probes_enable: section_offsets[0] must be 0");
+		for (uint64_t s = 0; s < S; ++s) {
+			const uint64_t lo = desc->section_offsets[s], hi = desc->section_offsets[s + 1];
+			if (hi < lo || hi - lo < 2) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + " is shorter than 2 entries");
+			if (hi > (1ull << 32)) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + ": offsets out of range");
+		}
+		M = desc->section_offsets[S];
+		for (uint64_t e = 0; e < M; ++e) {
+			if (desc->section_cells[e] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": cell id outside the local array");
+			if (desc->section_wx[e] < -1 || desc->section_wx[e] > 1 || desc->section_wy[e] < -1 || desc->section_wy[e] > 1)
+				return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": weight outside {-1, 0, 1}");
+		}
+	}
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_enable between hp_step_begin and hp_step_end");
+	if ((rc = probes_release(d)) != HP_OK) return rc;
+	// one block for the lists: [gauge cells | section offsets | section cells | wx | wy], the 8-byte arrays first
+	const size_t words = (size_t)(G + (S ? S + 1 : 0) + M);
+	const size_t list_bytes = words * 8 + 2 * (size_t)M;
+	std::vector<unsigned char> host(list_bytes);
+	uint64_t* w = (uint64_t*)host.data();
+	if (G) std::memcpy(w, desc->gauge_cells, G * 8);
+	if (S) {
+		std::memcpy(w + G, desc->section_offsets, (S + 1) * 8);
+		std::memcpy(w + G + S + 1, desc->section_cells, M * 8);
+		std::memcpy(host.data() + words * 8, desc->section_wx, M);
+		std::memcpy(host.data() + words * 8 + M, desc->section_wy, M);
+	}
+	hipError_t e = hipMalloc(&d->probes_mem, list_bytes);
+	if (e == hipSuccess) e = hipMalloc((void**)&d->probes_records, (size_t)desc->capacity * stride * sizeof(double));
+	if (e == hipSuccess) e = hipMemcpyAsync(d->probes_mem, host.data(), list_bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (`host` goes away with this call)
+	if (e != hipSuccess) {
+		hipFree(d->probes_mem); hipFree(d->probes_records);
+		d->probes_mem = nullptr; d->probes_records = nullptr;
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, std::string("hp_probes_enable: cannot allocate the lists and the record buffer: ") + hipGetErrorString(e));
+	}
+	const unsigned long long* dw = (const unsigned long long*)d->probes_mem;
+	ProbeLists& p = d->probes_lists;
+	p.gauge_cells = dw;
+	p.section_offsets = dw + G;
+	p.section_cells = dw + G + (S ? S + 1 : 0);
+	p.section_wx = (const signed char*)d->probes_mem + words * 8;
+	p.section_wy = p.section_wx + M;
+	p.gauges = G;
+	p.gauge_blocks = (unsigned)((G + 255) / 256);
+	p.sections = (unsigned)S;
+	d->probes_capacity = desc->capacity;
+	d->probes_stride = stride;
+	d->probes_samples = 0;
+	d->probes_on = true;
+	++d->probes_epoch;
+	return HP_OK;
+}
+
+int hp_probes_disable(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	return probes_release(d);
+}
+
+int hp_probes_reset(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_reset before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_reset between hp_step_begin and hp_step_end");
+	d->probes_samples = 0;                   // (stream order: a read queued before this call has its records before a later sample overwrites them)
+	++d->probes_epoch;
+	return HP_OK;
+}
+
+int hp_probes_sample(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK) return rc;
+	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_sample before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_sample between hp_step_begin and hp_step_end");
+	if (d->probes_samples >= d->probes_capacity)
+		return fail(HP_ERR_STATE, "hp_probes_sample: the record buffer is full (read the records, then hp_probes_reset)");
+	const ProbeLists& p = d->probes_lists;
+	const unsigned blocks = p.gauge_blocks + p.sections;
+	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
+	if (d->desc.precision == 8)
+		hipLaunchKernelGGL((record_probes<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed,
+		                   (const Scalars<double>*)d->scalars, p, d->probes_records, (unsigned long long)d->probes_samples,
+		                   (unsigned long long)d->probes_stride, d->desc.dx);
+	else
+		hipLaunchKernelGGL((record_probes<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed,
+		                   (const Scalars<float>*)d->scalars, p, d->probes_records, (unsigned long long)d->probes_samples,
+		                   (unsigned long long)d->probes_stride, d->desc.dx);
+	HIP_TRY(hipGetLastError());
+	++d->probes_samples;
+	return HP_OK;
+}
+
+int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_read before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_read between hp_step_begin and hp_step_end");
+	if (first > d->probes_samples || count > d->probes_samples - first)
+		return fail(HP_ERR_INVALID, "hp_probes_read: first + count beyond the samples taken");
+	if (count == 0) return HP_OK;
+	if (!records) return fail(HP_ERR_INVALID, "hp_probes_read: records == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(records, d->probes_records + first * d->probes_stride, (size_t)(count * d->probes_stride) * sizeof(double),
+	                       hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_info before hp_probes_enable");
+	if (samples) *samples = d->probes_samples;
+	if (capacity) *capacity = d->probes_capacity;
+	if (stride) *stride = d->probes_stride;
 	return HP_OK;
 }
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "hp_domain_create", "hp_domain_destroy", "hp_domain_upload", "hp_domain_download", "hp_domain_upload_rows", "hp_state_save", "hp_state_restore",
     "hp_domain_derive", "hp_domain_stats",
     "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
+    "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -110,6 +111,13 @@ class PeaksDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("values_mask", C.c_uint32), ("arrival_depth", C.c_double)]
 
 
+class ProbesDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_uint32), ("gauge_count", C.c_uint64),
+                ("gauge_cells", C.POINTER(C.c_uint64)), ("section_count", C.c_uint32),
+                ("section_offsets", C.POINTER(C.c_uint64)), ("section_cells", C.POINTER(C.c_uint64)),
+                ("section_wx", C.POINTER(C.c_int8)), ("section_wy", C.POINTER(C.c_int8))]
+
+
 _lib = None
 
 
@@ -152,6 +160,13 @@ def load_library(path: str | None = None):
         lib.hp_peaks_sample.argtypes = [C.c_void_p]
         lib.hp_peaks_read.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
         lib.hp_peaks_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "hp_probes_enable"):                # (absent from older builds, as above)
+        lib.hp_probes_enable.argtypes = [C.c_void_p, C.POINTER(ProbesDesc)]
+        lib.hp_probes_disable.argtypes = [C.c_void_p]
+        lib.hp_probes_reset.argtypes = [C.c_void_p]
+        lib.hp_probes_sample.argtypes = [C.c_void_p]
+        lib.hp_probes_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
+        lib.hp_probes_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -205,6 +220,12 @@ def load_library(path: str | None = None):
 def _check(lib, rc, what):
     if rc != 0:
         raise HipimsError(f"{what} failed ({rc}): {lib.hp_last_error().decode(errors='replace')}")
+
+
+def split_probe_records(records, gauges, sections):
+    """[n, 1 + 4 G + S] probe records (hp_probes_read's layout) as {"t": [n], "gauges": [n, G, 4], "sections": [n, S]}."""
+    rec = np.asarray(records, dtype=np.float64).reshape(-1, 1 + 4 * gauges + sections)
+    return dict(t=rec[:, 0].copy(), gauges=rec[:, 1:1 + 4 * gauges].reshape(-1, gauges, 4).copy(), sections=rec[:, 1 + 4 * gauges:].copy())
 
 
 COMM_ID_BYTES = 128
@@ -291,6 +312,10 @@ class Domain:
         self._keepalive = []
         self._bed_host = None
         self._peak_values = []                          # HP_PEAK_* codes the library tracks (peaks_enable's mask)
+        self._probes = None                             # (gauges, sections) the library records (probes_enable's lists)
+        self._probes_drained = []                       # records read back when the device buffer was full: [k, stride] arrays
+        self._probes_saved = None                       # state_save's (recorder generation, samples so far)
+        self._probes_generation = 0
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -437,6 +462,76 @@ class Domain:
         _check(self.lib, self.lib.hp_peaks_info(self.h, C.byref(n), C.byref(t0), C.byref(t1)), "hp_peaks_info")
         return dict(samples=n.value, t_first=t0.value, t_last=t1.value)
 
+    # ---- the probe recorder (hp_probes_*): gauge and cross-section time series, one record per SAMPLE the host takes ----
+    def probes_enable(self, gauges=(), sections=(), capacity=4096):
+        """Start recording: `gauges` are (x, y) cell indices, `sections` (cells, wx, wy) triples -- cells as (x, y) pairs, one
+        weight pair in {-1, 0, 1} per cell -- or what frontend.rasterise_section returns.  `capacity` is the number of samples
+        the device buffer holds; probes_sample() drains a full buffer by itself, so it only sets how often that happens."""
+        def flat(cells):
+            c = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+            if c.size and (c.min() < 0 or (c[:, 0] >= self.cols).any() or (c[:, 1] >= self.rows).any()):
+                raise ValueError("a probe cell lies outside the domain")
+            return c[:, 1] * self.cols + c[:, 0]
+        self.probes_enable_cells(flat(gauges), [(flat(s[0]), s[1], s[2]) for s in sections], capacity)
+
+    def probes_enable_cells(self, gauge_cells, sections=(), capacity=4096):
+        """probes_enable with flat cell ids y * cols + x of the local array (what hp_probes_desc_t takes; not range-checked
+        here: the library does that)."""
+        g = np.ascontiguousarray(gauge_cells, dtype=np.uint64).reshape(-1)
+        offsets = np.zeros(len(sections) + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(np.reshape(s[0], -1)) for s in sections], dtype=np.uint64)
+        join = lambda k, dtype: np.ascontiguousarray(np.concatenate([np.asarray(s[k]).reshape(-1) for s in sections]), dtype=dtype) \
+            if len(sections) else np.zeros(0, dtype)
+        for s in sections:
+            if not len(np.reshape(s[0], -1)) == len(np.reshape(s[1], -1)) == len(np.reshape(s[2], -1)):
+                raise ValueError("a section needs one weight pair per cell")
+        cells, wx, wy = join(0, np.uint64), join(1, np.int8), join(2, np.int8)
+        desc = ProbesDesc(C.sizeof(ProbesDesc), int(capacity), g.size, g.ctypes.data_as(C.POINTER(C.c_uint64)), len(sections),
+                          offsets.ctypes.data_as(C.POINTER(C.c_uint64)), cells.ctypes.data_as(C.POINTER(C.c_uint64)),
+                          wx.ctypes.data_as(C.POINTER(C.c_int8)), wy.ctypes.data_as(C.POINTER(C.c_int8)))
+        rc = self.lib.hp_probes_enable(self.h, C.byref(desc))
+        if rc == -3:                                    # HP_ERR_HIP: the allocation failed and the library has switched recording off
+            self._probes, self._probes_drained = None, []   # (an argument or state error leaves the recorder as it was)
+        _check(self.lib, rc, "hp_probes_enable")
+        self._probes, self._probes_drained = (int(g.size), len(sections)), []
+        self._probes_generation += 1
+
+    def probes_disable(self):
+        _check(self.lib, self.lib.hp_probes_disable(self.h), "hp_probes_disable")
+        self._probes, self._probes_drained = None, []
+        self._probes_generation += 1
+
+    def probes_info(self):
+        """dict(samples, pending, capacity, stride): samples taken since probes_enable, how many of them are still in the device
+        buffer, that buffer's capacity and the record length in fp64 words; host-side counters, does not block."""
+        n, cap, stride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_probes_info(self.h, C.byref(n), C.byref(cap), C.byref(stride)), "hp_probes_info")
+        return dict(samples=sum(len(a) for a in self._probes_drained) + n.value, pending=n.value, capacity=cap.value, stride=stride.value)
+
+    def _probes_pending(self):
+        info = self.probes_info()
+        out = np.empty((info["pending"], info["stride"]), np.float64)
+        if info["pending"]:
+            _check(self.lib, self.lib.hp_probes_read(self.h, 0, info["pending"], out.ctypes.data_as(C.POINTER(C.c_double))), "hp_probes_read")
+            self.sync()
+        return out, info
+
+    def probes_sample(self):
+        """One record of the current state: one launch on the domain's stream.  Does not block -- except when the device buffer
+        is full: then its records are read back first (one copy, one sync per `capacity` samples)."""
+        info = self.probes_info() if self._probes else None        # (not recording: the library's own answer below)
+        if info and info["pending"] == info["capacity"]:
+            self._probes_drained.append(self._probes_pending()[0])
+            _check(self.lib, self.lib.hp_probes_reset(self.h), "hp_probes_reset")
+        _check(self.lib, self.lib.hp_probes_sample(self.h), "hp_probes_sample")
+
+    def probes(self):
+        """Every sample since probes_enable, in order: {"t": [n], "gauges": [n, G, 4] (z, depth, qx, qy), "sections": [n, S]
+        (discharge, m3/s)}, bit-identical to frontend.ProbeRecorder fed the same samples; blocks."""
+        pending, _ = self._probes_pending()
+        rec = np.concatenate(self._probes_drained + [pending], axis=0)
+        return split_probe_records(rec, *self._probes)
+
     def upload_rows(self, rows_state, row0):
         a = np.ascontiguousarray(rows_state, dtype=self.real)
         _check(self.lib, self.lib.hp_domain_upload_rows(self.h, a.ctypes.data_as(C.c_void_p), row0, a.shape[0]),
@@ -446,9 +541,16 @@ class Domain:
     def state_save(self):
         """Device-side checkpoint of cell states + time-control block (saveCurrentState without the PCIe trip)."""
         _check(self.lib, self.lib.hp_state_save(self.h), "hp_state_save")
+        self._probes_saved = (self._probes_generation, self.probes_info()["samples"]) if self._probes else None
 
     def state_restore(self):
         _check(self.lib, self.lib.hp_state_restore(self.h), "hp_state_restore")
+        if self._probes:                                # the records read back already follow the library's count
+            saved = self._probes_saved
+            total = saved[1] if saved and saved[0] == self._probes_generation else 0
+            drained = np.concatenate(self._probes_drained, axis=0) if self._probes_drained else None
+            keep = max(0, total - self.probes_info()["pending"])
+            self._probes_drained = [drained[:keep]] if drained is not None and keep else []
 
     # ---- boundaries ----
     def add_uniform(self, definition, series, interval, length):

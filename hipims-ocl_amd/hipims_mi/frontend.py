@@ -24,6 +24,7 @@ import csv
 import os
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -113,6 +114,8 @@ class Configuration:
     closed_edges: set = field(default_factory=set)
     boundaries: list = field(default_factory=list)
     device_number: int = 1
+    gauges: list = field(default_factory=list)     # (name, x, y): <gauge> elements, cell indices (no reference counterpart)
+    sections: list = field(default_factory=list)   # (name, x0, y0, x1, y1): <section> elements, cell indices
 
 
 def _params(elem):
@@ -156,6 +159,11 @@ def parse_configuration(xml_path):
     for dt in data.findall("dataTarget"):
         cfg.targets.append(((dt.get("value") or "").lower(), dt.get("target")))
         cfg.target_formats.append((dt.get("format") or "").upper())
+    # the probe recorder's elements (no reference counterpart): cell indices, the convention of a cell boundary's mapFile
+    for k, g in enumerate(data.findall("gauge")):
+        cfg.gauges.append((g.get("name") or f"gauge{k}", int(g.get("x")), int(g.get("y"))))
+    for k, e in enumerate(data.findall("section")):
+        cfg.sections.append((e.get("name") or f"section{k}", int(e.get("x0")), int(e.get("y0")), int(e.get("x1")), int(e.get("y1"))))
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -346,6 +354,132 @@ class PeakTracker:
 
     def info(self):
         return dict(samples=self.samples, t_first=self.t_first, t_last=self.t_last)
+
+
+# ------------------------------------------------------------------------------------------------ probes (gauges and sections)
+class Section(NamedTuple):
+    """A cross-section: cells[m, 2] as (x, y) cell indices and one weight pair in {-1, 0, 1} per cell.  Its discharge is
+    dx * sum(wx * Qx + wy * Qy) over its counted, wet cells."""
+    cells: np.ndarray
+    wx: np.ndarray
+    wy: np.ndarray
+
+
+def rasterise_section(p0, p1):
+    """The cells of the straight cross-section from cell p0 = (x0, y0) to cell p1 = (x1, y1): a monotone, 4-connected path of
+    exactly |x1 - x0| + |y1 - y0| + 1 cells.  At every cell the next step is the one (along x or along y) that ends nearer the
+    straight line -- integer arithmetic on the cross product, a tie goes to x --, which keeps every cell centre within
+    (|dx| + |dy|) / (2 hypot(dx, dy)) <= 0.71 cell widths of the segment.  A step from cell k to cell k + 1 with direction
+    (tx, ty) belongs to cell k and carries the left normal (wx, wy) = (-ty, tx); the last cell carries (0, 0).  So the discharge is
+    positive when water crosses from the right of the direction of travel to its left, and for a uniform wet field Q = (a, b) it
+    is dx * (b * (x1 - x0) - a * (y1 - y0))."""
+    (x0, y0), (x1, y1) = (int(p0[0]), int(p0[1])), (int(p1[0]), int(p1[1]))
+    ax, ay = abs(x1 - x0), abs(y1 - y0)
+    sx, sy = (1 if x1 > x0 else -1), (1 if y1 > y0 else -1)
+    cells, wx, wy = [(x0, y0)], [], []
+    i = j = 0                                   # steps taken along x and along y
+    e = 0                                       # i * ay - j * ax: (ax, ay) x the offset from the line, in cell widths x hypot
+    while i < ax or j < ay:
+        along_x = j == ay or (i < ax and abs(e + ay) <= abs(e - ax))
+        if along_x:
+            i, e = i + 1, e + ay
+            wx.append(0); wy.append(sx)
+        else:
+            j, e = j + 1, e - ax
+            wx.append(-sy); wy.append(0)
+        cells.append((x0 + sx * i, y0 + sy * j))
+    wx.append(0); wy.append(0)
+    return Section(np.array(cells, np.int64).reshape(-1, 2), np.array(wx, np.int8), np.array(wy, np.int8))
+
+
+def fold_section_terms(terms, dx):
+    """A section's discharge from its terms, in exactly record_probes' order (csrc/hp_probes.hpp): 256 partial sums, partial j =
+    +0.0 + term[j] + term[j + 256] + ... in that order, folded by the halving tree part[i] = part[i] + part[i + s] for s = 128,
+    ..., 1, then dx * part[0].  (The list is padded with +0.0 to whole rows of 256: a partial sum that starts from +0.0 is never
+    -0.0, so adding +0.0 to it changes no bit.)"""
+    terms = np.asarray(terms, dtype=np.float64).reshape(-1)
+    rows = -(-terms.size // 256)
+    padded = np.zeros(rows * 256)
+    padded[:terms.size] = terms
+    part = np.zeros(256)
+    for row in padded.reshape(rows, 256):
+        part = part + row
+    s = 128
+    while s > 0:
+        part[:s] = part[:s] + part[s:2 * s]
+        s >>= 1
+    return float(dx) * part[0]
+
+
+def section_terms(wx, wy, depth, qx, qy, counted=True):
+    """(double)wx * Qx + (double)wy * Qy (two multiplies, one add) where the cell is counted and wet, +0.0 elsewhere."""
+    hit = np.asarray(counted) & (depth > 1e-8)
+    with np.errstate(all="ignore"):             # (cells that are not hit may hold anything)
+        return np.where(hit, np.asarray(wx).astype(np.float64) * qx + np.asarray(wy).astype(np.float64) * qy, 0.0)
+
+
+class ProbeRecorder:
+    """The probe recorder in NumPy, in exactly the device kernel's operation order (csrc/hp_probes.hpp: record_probes; strided
+    partial sums, then the halving tree): the reference the GPU tests compare against bit for bit, and the recorder of engines
+    without the device path.  All arithmetic in fp64; only add, multiply and compare.
+
+        ProbeRecorder(gauges, sections, dx)   gauges: (x, y) cell indices; sections: (cells, wx, wy) triples with cells as
+                                              (x, y) pairs, or rasterise_section's objects
+        record(state, bed, t)                 one sample: state[rows, cols, 4] = {Z, Zmax, Qx, Qy}, bed[rows, cols], t = the model time
+        series()                              {"t": [n], "gauges": [n, G, 4] (z, depth, qx, qy), "sections": [n, S]} so far
+    """
+
+    def __init__(self, gauges=(), sections=(), dx=1.0):
+        self.gauges = np.asarray(gauges, dtype=np.int64).reshape(-1, 2)
+        self.sections = [Section(np.asarray(s[0], dtype=np.int64).reshape(-1, 2), np.asarray(s[1], np.int8).reshape(-1),
+                                 np.asarray(s[2], np.int8).reshape(-1)) for s in sections]
+        for s in self.sections:
+            if not (len(s.cells) == len(s.wx) == len(s.wy) and len(s.cells) >= 2):
+                raise ValueError("a section needs at least 2 cells and one weight pair per cell")
+            if (np.abs(s.wx) > 1).any() or (np.abs(s.wy) > 1).any():
+                raise ValueError("section weights are -1, 0 or 1")
+        self.dx = float(dx)
+        self.records = []
+
+    @staticmethod
+    def _cells(state, bed, cells):
+        c = state[cells[:, 1], cells[:, 0]].astype(np.float64)
+        zb = np.asarray(bed)[cells[:, 1], cells[:, 0]].astype(np.float64)
+        z, zmax, qx, qy = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+        return z, z - zb, qx, qy, (zmax > -9999.0) & (zb <= 9999.0)           # counted as in domain_stats
+
+    def record(self, state, bed, t):
+        z, depth, qx, qy, counted = self._cells(state, bed, self.gauges)
+        g = np.where(counted[:, None], np.stack([z, depth, qx, qy], axis=1), NODATA).reshape(-1, 4)
+        q = []
+        for s in self.sections:
+            _, depth, qx, qy, counted = self._cells(state, bed, s.cells)
+            q.append(fold_section_terms(section_terms(s.wx, s.wy, depth, qx, qy, counted), self.dx))
+        self.records.append((float(t), g, np.array(q, np.float64)))
+
+    def series(self):
+        n, G, S = len(self.records), len(self.gauges), len(self.sections)
+        return dict(t=np.array([r[0] for r in self.records], np.float64),
+                    gauges=np.array([r[1] for r in self.records], np.float64).reshape(n, G, 4),
+                    sections=np.array([r[2] for r in self.records], np.float64).reshape(n, S))
+
+
+def write_probe_files(target_dir, series, gauge_names, section_names):
+    """gauges.csv (time,name,fsl,depth,qx,qy) and sections.csv (time,name,discharge): one line per sample and probe, every
+    number in its shortest exact decimal form (repr), so equal bits give equal bytes."""
+    os.makedirs(target_dir, exist_ok=True)
+    if gauge_names:
+        with open(os.path.join(target_dir, "gauges.csv"), "w") as f:
+            f.write("time,name,fsl,depth,qx,qy\n")
+            for t, rec in zip(series["t"], series["gauges"]):
+                for name, v in zip(gauge_names, rec):
+                    f.write(",".join([repr(float(t)), name] + [repr(float(x)) for x in v]) + "\n")
+    if section_names:
+        with open(os.path.join(target_dir, "sections.csv"), "w") as f:
+            f.write("time,name,discharge\n")
+            for t, rec in zip(series["t"], series["sections"]):
+                for name, v in zip(section_names, rec):
+                    f.write(f"{float(t)!r},{name},{float(v)!r}\n")
 
 
 def derive_output(what, state, bed, resolution=1.0):

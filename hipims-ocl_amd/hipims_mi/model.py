@@ -50,6 +50,7 @@ class SchemeDriver:
         self.rollback_limit = 999999999
         self.running = False
         self.peak_sampler = None                                   # Model's: called after every batch queued (the peak tracker)
+        self.samplers = []                                         # ... and these after it, in order (the probe recorder)
         self.prepare_simulation()
 
     # ---- adapters: Domain (HIP engine) and OracleSim spell a few things differently ----
@@ -153,6 +154,8 @@ class SchemeDriver:
                 self.cells_calculated += n * self.cells            # :1299: cols x rows per iteration, skipped or not
                 if self.peak_sampler is not None:                  # one sample per batch, queued behind it (no reference counterpart)
                     self.peak_sampler()
+                for sampler in self.samplers:
+                    sampler()
             self.read_key_statistics()                             # :1309-1313, blockUntilFinished, :1350
         finally:
             self.running = False
@@ -162,7 +165,8 @@ class Model:
     """CModel for one domain: `run()` is runModelMain."""
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
-                 clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01):
+                 clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
+                 probe_capacity=4096):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -215,12 +219,53 @@ class Model:
             else:
                 self.host_peaks = frontend.PeakTracker(self.rows, self.cols, peak_arrival_depth, t=self.scheme.current_time)
                 self.scheme.peak_sampler = self.sample_peaks_on_host
+        # The probe recorder (no reference counterpart): the model file's <gauge> and <section> elements and those of `gauges`
+        # ({name: (x, y)} or (name, x, y) tuples) and `sections` ({name: ((x0, y0), (x1, y1))} or (name, (x0, y0), (x1, y1))), in
+        # cell indices; one sample after every batch, gauges.csv and sections.csv rewritten at every output time and at the end.
+        # On the device (Domain.probes_*) wherever the output rasters are derived there; otherwise frontend.ProbeRecorder on the
+        # downloaded state with the front end's bed.
+        named = lambda extra: [(k,) + tuple(v) for k, v in extra.items()] if isinstance(extra, dict) else [tuple(e) for e in extra or []]
+        self.gauge_list = [(n, int(x), int(y)) for n, x, y in list(cfg.gauges) + named(gauges)]
+        self.section_list = []
+        for e in list(cfg.sections) + named(sections):
+            p0, p1 = ((e[1], e[2]), (e[3], e[4])) if len(e) == 5 else (e[1], e[2])
+            self.section_list.append((e[0], frontend.rasterise_section(p0, p1)))
+        for what, pts in [("gauge", [(n, x, y) for n, x, y in self.gauge_list])] + \
+                [("section", [(n, int(x), int(y)) for x, y in sec.cells]) for n, sec in self.section_list]:
+            for n, x, y in pts:
+                if not (0 <= x < self.cols and 0 <= y < self.rows):
+                    raise ValueError(f"{what} {n}: cell ({x}, {y}) lies outside the domain")
+        self.host_probes, self.device_probes = None, False
+        if self.gauge_list or self.section_list:
+            xy, secs = [(x, y) for _, x, y in self.gauge_list], [sec for _, sec in self.section_list]
+            self.device_probes = self.device_outputs and hasattr(sim, "probes_enable")
+            if self.device_probes:
+                sim.probes_enable(xy, secs, capacity=probe_capacity)
+                self.scheme.samplers.append(sim.probes_sample)
+            else:
+                self.host_probes = frontend.ProbeRecorder(xy, secs, self.res)
+                self.scheme.samplers.append(self.sample_probes_on_host)
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
 
     def sample_peaks_on_host(self):
         s = self.scheme._call("read_scalars", "scalars")()
         self.host_peaks.fold(self.sim.download(), self.bed, s["time"] if "time" in s else s["t"])
+
+    def sample_probes_on_host(self):
+        s = self.scheme._call("read_scalars", "scalars")()
+        self.host_probes.record(self.sim.download(), self.bed, s["time"] if "time" in s else s["t"])
+
+    def probes(self):
+        """{"t": [n], "gauges": [n, G, 4], "sections": [n, S]}: one entry per batch so far (None without gauges and sections)."""
+        if self.host_probes is not None:
+            return self.host_probes.series()
+        return self.sim.probes() if self.device_probes else None
+
+    def write_probes(self):
+        if (self.host_probes is not None or self.device_probes) and self.cfg.target_dir and self.output_format:
+            frontend.write_probe_files(self.cfg.target_dir, self.probes(), [n for n, _, _ in self.gauge_list],
+                                       [n for n, _ in self.section_list])
 
     def peaks(self):
         """{name: array} of the tracked peak values so far."""
@@ -267,6 +312,7 @@ class Model:
                 frontend.write_raster(os.path.join(self.cfg.target_dir, fname), arr, self.res)
         for name, arr in peaks.items():                            # (asked for through Model(peaks=...) only: no file)
             out.setdefault(name, arr)
+        self.write_probes()
         self.outputs.append((self.current_time, out))
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()
@@ -341,6 +387,7 @@ class Model:
         self.current_time = self.scheme.current_time
         if self.scheme.is_sync_ready(self.target_time):
             self.write_outputs()
+        self.write_probes()
         self.seconds = self.clock() - t0
         self.log_progress(self.seconds)
         return self.outputs

@@ -74,6 +74,44 @@ def combine_stats(parts, local_los, cols):
     return out
 
 
+def probe_points(gauges, sections):
+    """The probe recorder over strips.  A section's sum has a fixed order (csrc/hp_probes.hpp), which sums per rank would change.
+    So every POINT -- a gauge, or one cell of a section -- is recorded as a gauge by the rank that owns its row.
+    -> (gauges[G, 2], [frontend.Section], points[G + sum(m), 2]): the gauges, then every section's cells, as (x, y)."""
+    from . import frontend
+    g = np.asarray(gauges, dtype=np.int64).reshape(-1, 2)
+    secs = [frontend.Section(np.asarray(s[0], dtype=np.int64).reshape(-1, 2), np.asarray(s[1], np.int8).reshape(-1),
+                             np.asarray(s[2], np.int8).reshape(-1)) for s in sections]
+    points = np.concatenate([g] + [s.cells for s in secs], axis=0)
+    if not len(points):
+        raise ValueError("neither a gauge nor a section")
+    return g, secs, points
+
+
+def assemble_probes(parts, gauges, sections, dx):
+    """`parts`: per rank (indices into probe_points' list, t[n], values[n, k, 4]) of the points it owns, or None.  The gauges'
+    values are the ranks' own; a section's discharge is formed from its cells' values in the kernel's order
+    (frontend.section_terms, fold_section_terms: an uncounted cell's depth is NODATA, i.e. not wet), so the result equals the
+    single domain's record bit for bit.  -> {"t": [n], "gauges": [n, G, 4], "sections": [n, S]}"""
+    from . import frontend
+    parts = [p for p in parts if p is not None]
+    t = np.array(parts[0][1])
+    G = len(gauges)
+    values = np.empty((len(t), G + sum(len(s.cells) for s in sections), 4))
+    for idx, t_k, v in parts:
+        if not np.array_equal(t_k, t):
+            raise RuntimeError("the ranks' probe samples were taken at different model times")
+        values[:, idx] = v
+    q = np.empty((len(t), len(sections)))
+    at = G
+    for k, s in enumerate(sections):
+        v = values[:, at:at + len(s.cells)]
+        at += len(s.cells)
+        for n in range(len(t)):
+            q[n, k] = frontend.fold_section_terms(frontend.section_terms(s.wx, s.wy, v[n, :, 1], v[n, :, 2], v[n, :, 3]), dx)
+    return dict(t=t, gauges=values[:, :G].copy(), sections=q)
+
+
 class HipEngine:
     """The HIP domain of one strip + zero-copy torch views of its device buffers."""
 
@@ -154,6 +192,22 @@ class HipEngine:
 
     def peaks_info(self):
         return self.domain.peaks_info()
+
+    # the probe recorder (Domain.probes_*)
+    def probes_enable(self, gauges=(), sections=(), capacity=4096):
+        self.domain.probes_enable(gauges, sections, capacity=capacity)
+
+    def probes_disable(self):
+        self.domain.probes_disable()
+
+    def probes_sample(self):
+        self.domain.probes_sample()
+
+    def probes(self):
+        return self.domain.probes()
+
+    def probes_info(self):
+        return self.domain.probes_info()
 
     def set_target_time(self, t):
         self.domain.set_target_time(t)
@@ -321,11 +375,12 @@ class StripRunner:
         return st, bed, man
 
     def upload(self, st_local, bed_local, man_local):
+        self._bed_local = None if bed_local is None else np.array(bed_local)     # (the host-side probe recorder's bed)
         self.engine.upload(st_local, bed_local, man_local)
 
     def upload_global(self, st, bed, man):
         sl = self.local_slice()
-        self.engine.upload(st[sl], bed[sl], man[sl])
+        self.upload(st[sl], bed[sl], man[sl])
 
     def set_target_time(self, t):
         self.engine.set_target_time(t)
@@ -476,6 +531,47 @@ class StripRunner:
         parts = [None] * self.world if self.rank == 0 else None
         self.dist.gather_object(mine, parts, dst=0)
         return assemble_outputs(parts) if self.rank == 0 else None
+
+    # ---- the probe recorder: every rank records the points on the rows it owns as gauges (probe_points); rank 0 forms the
+    #      sections' discharges from the gathered values (assemble_probes) ----
+    def probes_enable(self, gauges=(), sections=(), capacity=4096, dx=None):
+        """`gauges`: (x, y) and `sections`: (cells, wx, wy) triples or frontend.rasterise_section's objects, in GLOBAL cell
+        indices.  `dx`: the cell size of the discharges (default: the HIP domain's; 1 with another engine)."""
+        self._probe_gauges, self._probe_sections, points = probe_points(gauges, sections)
+        if (points < 0).any() or (points[:, 0] >= self.cols).any() or (points[:, 1] >= self.rows).any():
+            raise ValueError("a probe cell lies outside the grid")
+        self._probe_dx = float(dx if dx is not None else (self.domain.desc.dx if self.domain is not None else 1.0))
+        self._probe_mine = np.flatnonzero((points[:, 1] >= self.own_lo) & (points[:, 1] < self.own_hi))
+        local = points[self._probe_mine] - np.array([0, self.local_lo])
+        self._probe_host = None
+        if not len(local):
+            return                                      # (no point on this rank's rows: nothing to record here)
+        if hasattr(self.engine, "probes_enable"):
+            self.engine.probes_enable(local, (), capacity=capacity)
+        else:                                           # an engine without the device path: the host recorder on the downloaded strip
+            from . import frontend
+            self._probe_host = frontend.ProbeRecorder(local, ())
+
+    def probes_sample(self):
+        if not len(self._probe_mine):
+            return
+        if self._probe_host is None:
+            self.engine.probes_sample()
+        else:
+            self._probe_host.record(self.engine.download(), self._bed_local, self.engine.scalars()["t"])
+
+    def gather_probes(self):
+        """The series of the whole grid: rank 0 gets {"t": [n], "gauges": [n, G, 4], "sections": [n, S]}, bit-identical to the
+        single domain's Domain.probes(); the other ranks None.  Pickled objects over the process group; collective."""
+        mine = None
+        if len(self._probe_mine):
+            series = self.engine.probes() if self._probe_host is None else self._probe_host.series()
+            mine = (self._probe_mine, series["t"], series["gauges"])
+        parts = [mine]
+        if self.world > 1:
+            parts = [None] * self.world if self.rank == 0 else None
+            self.dist.gather_object(mine, parts, dst=0)
+        return assemble_probes(parts, self._probe_gauges, self._probe_sections, self._probe_dx) if self.rank == 0 else None
 
     def gather_stats(self):
         """Domain.stats over the whole grid, on every rank (combine_stats); cell ids are global.  Collective."""

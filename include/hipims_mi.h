@@ -248,6 +248,61 @@ int hp_peaks_read(hp_domain_t* d, const int* values, int count, int element_byte
  * while there is none).  Any of the three pointers may be NULL.  BLOCKS. */
 int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_last);
 
+/* ---- the probe recorder: time series at gauge cells and through cross-sections ("probes" = gauges + sections;
+ *      no reference counterpart: HiPIMS-OCL writes rasters only, and a hydrograph from it means a raster per sample).
+ *      Opt-in.  One kernel launch per sample (csrc/hp_probes.hpp: record_probes) writes one RECORD of
+ *      stride = 1 + 4 * gauge_count + section_count fp64 words into a buffer of `capacity` records in device memory:
+ *          [t, g0.z, g0.depth, g0.qx, g0.qy, g1.z, ..., s0.discharge, s1.discharge, ...]
+ *      A sample reads the buffer hp_domain_download(HP_ARRAY_STATE) reads, the bed and the device's own "Time" scalar, in stream
+ *      order behind whatever is queued, without any host synchronisation, and changes nothing the steps depend on: a recorded
+ *      run's state, scalars, launch counts and pair statistics are the unrecorded run's, bit for bit.  With the recorder off
+ *      nothing is allocated or launched.  A sample can only be taken between batches, never per iteration inside one: inside
+ *      hp_step_batch every iteration but the last carries its successor's rain, and an iteration pair never materialises its
+ *      middle state -- there is no state "at iteration k" to read (the peak tracker's rule).
+ *      Conventions of the output stage: all arithmetic in fp64 whatever the domain's precision (an fp32 domain's values are
+ *      widened first), correctly rounded add, multiply and compare only, NODATA = -9999, wet = Z - bed > 1e-8.  A cell is counted
+ *      exactly as in hp_domain_stats (Zmax > -9999 and bed <= 9999).
+ *        gauge     counted: z = Z, depth = Z - bed (raw: not clamped, no wet test), qx = Qx, qy = Qy (m2/s); not counted: NODATA
+ *                  in all four.  The same cell may be listed more than once.
+ *        section   a list of m >= 2 cells with one weight pair (wx, wy) in {-1, 0, 1} each.  The term of entry k is
+ *                  (double)wx_k * Qx_k + (double)wy_k * Qy_k (two multiplies, one add, not fused) if its cell is counted and wet,
+ *                  +0.0 otherwise.  THE ORDER OF THE SUM IS PART OF THE CONTRACT: 256 partial sums, partial j = +0.0 + term_j +
+ *                  term_(j+256) + term_(j+512) + ... in that order; then for s = 128, 64, ..., 1: part[i] = part[i] + part[i+s]
+ *                  for i < s (the halving tree of hp_domain_stats); discharge = dx * part[0] in m3/s, one multiply.  No atomics:
+ *                  the same state gives the same bits, on any launch shape, and frontend.ProbeRecorder restates it in NumPy.
+ *                  A cell may appear more than once in a section. ---- */
+typedef struct {
+	uint32_t struct_size;              /* = sizeof(hp_probes_desc_t) */
+	uint32_t capacity;                 /* samples the device buffer holds; >= 1; capacity * stride * 8 <= 256 MiB */
+	uint64_t gauge_count;              /* <= 65536 */
+	const uint64_t* gauge_cells;       /* flat ids y * cols + x in the LOCAL array */
+	uint32_t section_count;            /* <= 1024; gauge_count + section_count >= 1 */
+	const uint64_t* section_offsets;   /* section_count + 1 entries into the three arrays below, from 0; each section >= 2 entries */
+	const uint64_t* section_cells;     /* LOCAL flat ids */
+	const int8_t*   section_wx;        /* -1, 0, 1 */
+	const int8_t*   section_wy;
+} hp_probes_desc_t;
+/* Copies the lists to the device (the caller's arrays are free again on return) and allocates the record buffer; sample count 0.
+ * On a domain that is already recording, the old recorder is freed first.  Argument errors -- a bad struct_size, a cell id
+ * >= cols * rows, a weight outside {-1, 0, 1}, a section shorter than 2 entries, a count over its limit, a record buffer over
+ * 256 MiB -- are HP_ERR_INVALID before any device call.  If an allocation fails the call returns HP_ERR_HIP and the domain
+ * stays usable with the recorder off. */
+int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc);
+int hp_probes_disable(hp_domain_t* d);                 /* frees; idempotent (also done by hp_domain_destroy) */
+/* Sample count 0; the buffer is not cleared.  Reads queued before the call still deliver the old records (stream order). */
+int hp_probes_reset(hp_domain_t* d);
+/* One sample: enqueued on the domain's stream, never blocks.  HP_ERR_STATE before hp_probes_enable, between hp_step_begin and
+ * hp_step_end, and when samples == capacity: nothing is enqueued then and the count is unchanged -- the host reads the records
+ * and calls hp_probes_reset. */
+int hp_probes_sample(hp_domain_t* d);
+/* Records [first, first + count) into records[count * stride]: a device-to-host copy enqueued behind the queued samples; the host
+ * memory must stay alive until hp_sync().  first + count beyond the samples taken is HP_ERR_INVALID; a read before
+ * hp_probes_enable or inside a split step is HP_ERR_STATE; count == 0 is HP_OK. */
+int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records);
+/* Samples taken since enable / reset, the capacity and the record stride in fp64 words.  Host-side counters: does not block.  Any
+ * of the three pointers may be NULL.  HP_ERR_STATE before hp_probes_enable. */
+int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride);
+
 /* Device-side checkpoint: what saveCurrentState + rollbackSimulation do through host memory (CSchemeGodunov.cpp:1720-1736,
  * :1474-1518), kept in HBM instead (two more copies of a 4096^2 fp64 state are 1 GB of 288).  hp_state_save copies BOTH
  * ping-pong buffers and the time-control block; hp_state_restore puts each buffer, the time-control block, the ping-pong phase
@@ -258,7 +313,10 @@ int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_
  * below, exactly as the reference's rollback sequence does.
  * While the peak tracker is on, hp_state_save also snapshots its accumulators and its own block and hp_state_restore puts
  * them back: the samples that follow repeat the original ones bit for bit.  A snapshot taken before the tracker was enabled,
- * disabled or re-enabled holds no peaks: hp_state_restore then resets them and sends one HP_LOG_WARNING to the log sink. */
+ * disabled or re-enabled holds no peaks: hp_state_restore then resets them and sends one HP_LOG_WARNING to the log sink.
+ * While the probe recorder is on, hp_state_save remembers its sample count and hp_state_restore puts it back: the records taken
+ * since then are re-recorded by the samples that are repeated.  If the recorder was enabled, disabled, re-enabled or reset since
+ * the snapshot, hp_state_restore sets the count to 0 and sends one HP_LOG_WARNING to the log sink. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
