@@ -1,0 +1,240 @@
+// hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain
+// and the map of its pinned host block.  Internal to the library's one translation unit: hp_engine.hip includes it, then
+// hp_observers.hpp (the code of the three observers whose state is declared here).
+#pragma once
+#include "../../include/hipims_mi.h"
+#include "hp_kernels.hpp"
+#include "hp_peaks.hpp"
+#include "hp_probes.hpp"
+#include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
+
+#include <atomic>
+#include <string>
+#include <vector>
+
+using namespace hp;
+
+namespace {
+
+thread_local std::string g_last_error;
+
+std::atomic<hp_log_sink_t> g_log_sink{nullptr};
+std::atomic<void*>         g_log_user{nullptr};
+
+int fail(int code, const std::string& msg)
+{
+	g_last_error = msg;
+	if (hp_log_sink_t sink = g_log_sink.load(std::memory_order_acquire))
+		sink(HP_LOG_MODEL_STOP, g_last_error.c_str(), g_log_user.load(std::memory_order_acquire));
+	return code;
+}
+
+void log_line(int level, const std::string& msg)
+{
+	if (hp_log_sink_t sink = g_log_sink.load(std::memory_order_acquire))
+		sink(level, msg.c_str(), g_log_user.load(std::memory_order_acquire));
+}
+
+#define HIP_TRY(expr)                                                                                  \
+	do {                                                                                               \
+		hipError_t e_ = (expr);                                                                        \
+		if (e_ != hipSuccess)                                                                          \
+			return fail(HP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
+	} while (0)
+
+struct Boundary {
+	int      kind;         // 0 uniform, 1 gridded, 2 cell
+	int      definition;
+	int      discharge_def;
+	void*    cells;        // device: global cell ids (cell boundaries)
+	uint64_t count;
+	void*    data;         // device
+	uint64_t entries, grows, gcols;
+	double   interval, length, resolution, off_x, off_y;
+};
+
+// ---- the observers' state (their code: hp_observers.hpp) ----
+// the output stage (hp_output.hpp; hp_domain_derive / hp_domain_stats): allocated on first use
+struct OutputStage {
+	void*            scratch = nullptr;               // rasters of one block of rows, value after value (at most OUT_SCRATCH_CAP bytes)
+	size_t           scratch_bytes = 0;
+	void*            stats = nullptr;                 // STATS_MAX_BLOCKS block partials + the folded result
+	void*            stats_host = nullptr;            // pinned: the folded result
+};
+// the peak tracker (hp_peaks.hpp; hp_peaks_*): nothing of it exists while tracking is off
+struct PeakTracker {
+	bool             on = false;
+	unsigned         mask = 0;                        // HP_PEAK_* bits enabled
+	int              count = 0;                       // ... how many: the accumulators lie one after the other in acc, in code order
+	double           arrival = 0.0;
+	double*          acc = nullptr;                   // count x cells fp64, followed by the PeakBlock
+	uint64_t         samples = 0;                     // samples queued since enable / reset (its parity picks the time slot)
+	uint64_t         epoch = 0;                       // counts enable / disable: a checkpoint's peaks belong to one epoch
+	void*            saved = nullptr;                 // hp_state_save's copy of acc (accumulators + block)
+	bool             saved_valid = false;
+	uint64_t         saved_epoch = 0, saved_samples = 0;
+};
+// the probe recorder (hp_probes.hpp; hp_probes_*): nothing of it exists while recording is off
+struct ProbeRecorder {
+	bool             on = false;
+	void*            mem = nullptr;                   // the lists (`lists` points into it)
+	double*          records = nullptr;               // capacity records of stride fp64 words
+	ProbeLists       lists = {};
+	uint64_t         capacity = 0, stride = 0;
+	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
+	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
+	bool             saved_valid = false;
+	uint64_t         saved_epoch = 0, saved_samples = 0;
+};
+
+} // namespace
+
+struct hp_domain {
+	hp_domain_desc_t desc;
+	hipStream_t      stream = nullptr;
+	size_t           cells = 0, esize = 0;
+	void*            state[2] = {nullptr, nullptr};   // [0] = primary "Cell states", [1] = "Cell states (alternate)"
+	void*            bed = nullptr;
+	void*            manning = nullptr;
+	void*            scalars = nullptr;               // Scalars<T> on the device
+	void*            cfl_slot = nullptr;              // CFL_SLOT_BYTES: running max | SLOT_SAVED last used max | SLOT_EDGE ring maxima of [0], [1]
+	bool             manning_uniform = false;         // found at upload: one value everywhere -> kernels skip the array
+	double           manning_value = 0.0;
+	bool             need_full_reduce = true;         // the remembered maximum is stale (upload / link import)
+	bool             edge_dirty = true;               // edge-ring maxima must be re-priced
+	bool             bdy_on_ring = false;             // a cell boundary imposes values on never-written ring cells: re-price every iteration
+	int              adv_fresh = 1;                   // does hp_step_end's advance kernel read a new maximum?
+	Tiling           tiling;                          // tile heights and row bands of its launches (hp_tiling.hpp: choose_tiling)
+	int              sweep_flip = 0;                  // parity of the whole-domain flux launches: every other one visits each band's tiles from
+	                                                  // the top down, so that it starts on the rows its predecessor wrote last (sweep_alternates)
+	void*            host_scalars = nullptr;          // pinned mirror
+	int              use_alt = 0;                     // bUseAlternateKernel
+	bool             in_step = false;
+	std::vector<Boundary> bdy;
+	// area boundaries carried by the flux kernel's fused epilogue (K1, FUSED): device copy of their descriptors
+	void*            fused_list = nullptr;
+	bool             fusable = false;                 // Godunov, tuned kernel, 1..FUSED_BDY_MAX uniform / coarse gridded boundaries, no cell boundary
+	int              fuse_next = 0;                   // this iteration is followed by another one of the same batch
+	uint64_t         cells_calculated = 0, iterations = 0;
+	hipEvent_t       ev_start = nullptr, ev_stop = nullptr;
+	// flux-kernel timing samples
+	int              timing_stride = 0;
+	uint64_t         timing_counter = 0;
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_events;   // pool, created by hp_kernel_timing
+	size_t           timing_used = 0;
+	double           timing_overhead_ms = 0.0;        // an empty event pair's own time (taken off every sample)
+	long             own_lo = 0, own_hi = 0;          // rows this rank owns (CFL reduction range)
+	// ghost rows of a strip: `ghost_rows` stored per interior side (g or 2g, g = the scheme's stencil reach), of which
+	// `ghost_valid` currently hold their owners' values; an iteration consumes g of them, the exchange refills them all
+	long             ghost_rows = 0, ghost_valid = 0, saved_ghost_valid = 0;
+	bool             split_now = false;               // this iteration is followed by an exchange: halo part on its own stream
+	// what the ranks told each other at the start of the batch (hp_strip_step_batch): which of them price a new maximum on
+	// the iterations that the ping-pong phase alone would not make them price
+	bool             strip_any_bdy = false, strip_any_full = false;
+	bool             strip_pairs = false;             // the batch's handshake: every rank can run iteration pairs (godunov_march2 over two-reach ghost rows)
+	// halo overlap (strip decomposition): the row segments next to the ghost rows run on their own stream so the
+	// neighbours' halo transfer can start while the interior segments are still being computed
+	bool             halo_overlap = false;
+	bool             halo_overlap_set = false;        // the host chose explicitly (hp_set_halo_overlap): comm_init keeps it
+	hipStream_t      stream_halo = nullptr;
+	hipEvent_t       ev_fork = nullptr, ev_halo = nullptr;
+	bool             fork_is_advance = false;         // ev_fork was recorded BY the last advance_time launch
+	// strip decomposition driven from C++ (hp_strip_*): one RCCL communicator over the ranks, strip neighbours = rank +- 1
+	// device-side checkpoint (hp_state_save / hp_state_restore)
+	void*            saved_state = nullptr;
+	void*            saved_scalars = nullptr;         // Scalars<T> + the four CFL slots
+	bool             saved_valid = false;
+	bool             saved_full_reduce = true, saved_edge_dirty = true;
+	int              saved_use_alt = 0;
+	ncclComm_t       comm = nullptr;
+	int              comm_rank = 0, comm_world = 1;
+	hipEvent_t       ev_xchg = nullptr;               // ghost rows of the iteration in flight have arrived
+	// the maximum over all strips through peer-written mailboxes (hp_strip_peer_*; PeerBox in hp_kernels.hpp)
+	unsigned long long*  peer_mine = nullptr;         // this rank's mailbox (uncached device memory)
+	unsigned long long** peer_table = nullptr;        // device: every rank's mailbox as this device addresses it
+	std::vector<void*>   peer_mapped;                 // IPC mappings to close
+	int              peer_world = 0, peer_rank = 0;
+	bool             peer_agreed = false;             // every rank of the communicator passed the connection test: the strip loop uses them
+	uint64_t         peer_rounds = 0;                 // reductions so far (its parity picks the mailbox set; the same on every rank)
+	// ghost rows written straight into the neighbours' state buffers (PeerPush): [side: 0 south, 1 north][ping-pong buffer]
+	void*            peer_state[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+	long             peer_rows[2] = {0, 0};           // the neighbours' local row counts
+	unsigned*        push_arrived = nullptr;          // device counter of the push blocks
+	bool             peer_direct = false;             // every rank reached its neighbours' buffers: no transfer library inside an iteration
+	bool             push_now = false;                // this iteration's advance kernel carries the ghost rows
+	// the flux launch's own tail block instead of a separate advance launch (LaunchTail, hp_kernels.hpp): small launches only
+	unsigned long long* tail_words = nullptr;         // one word per flux block (EMPTY between launches)
+	bool             rings_differ = false;            // a partial state upload went into ONE buffer: the edge rings of the two may differ -- no iteration pairs until the next full upload (pair_eligible)
+	bool             saved_rings_differ = false;
+	bool             rings_checked = false;           // ... and have been compared since (rings_really_differ): the flag is a fact, not a maybe
+	bool             fill_now = false;                // this iteration's K1 launch stores the cells the reference leaves untouched as well (dispatch_begin)
+	bool             other_stale = false;             // pairs (godunov_march2) ran since the non-current state buffer last held a state the single-iteration kernels can build on
+	// quirk Q3 across pair launches, exactly (hp_kernels.hpp: PairAux): stamps of the cells whose first-step stale value the next launch needs
+	void*            z_state = nullptr;               // stamp records, one per cell: State4<T> + the number of the pair launch that wrote it (allocated with the first pair)
+	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
+	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while other_stale holds
+	// still records of the FAST fp64 pair kernel (hp_kernels.hpp: StillRec; round 8): two halves of windows x rows records, the last launch's
+	// in half still_rec_half, then two counters (hp_pair_stats).  Valid while no writer of either state buffer has run since that launch
+	// other than such launches themselves (still_rec_forget)
+	void*            still_rec = nullptr;
+	size_t           still_rec_slots = 0;             // records per half
+	int              still_rec_half = 0;
+	bool             still_rec_valid = false;
+	bool             still_rec_last = false;          // the last pair launch wrote records (hp_pair_stats)
+	bool             saved_m1_valid = false;
+	bool             pair_fused_next = false;         // the last pair stored its state with the next iteration's boundaries applied (SLOT_BDY = 1)
+	bool             m1_valid = false;                // area boundaries: cfl_slot[SLOT_M1] prices the primary buffer with the next iteration's boundaries (left by the last pair)
+	uint64_t         pair_cold_starts = 0;
+	// STRICT: pairs or single iterations, by measurement (pair_tuner: the two are the same bits; which is faster depends on how much of
+	// the water stands still)
+	hipEvent_t       tune_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	int              tune_phase = 0;                  // 0: sample at the next opportunity, 1: a sample is in flight, 2: decided
+	bool             tune_prefer_pairs = true;
+	uint64_t         tune_next = 0;                   // iteration count from which the next sample is due
+	uint64_t         tune_samples = 0, tune_switches = 0;
+	float            tune_pair_ms = 0.f, tune_single_ms = 0.f;
+	uint64_t         pairs = 0;                       // iteration pairs run by it
+	unsigned         single_streak = 0;               // single iterations since the last pair (step_begin_impl: which launches hp_kernel_timing samples)
+	uint64_t         flux_launches = 0, flux_launches_tailed = 0;   // whole-domain flux launches of hp_step_batch / hp_strip_step_batch, and how many carried their own tail block
+	bool             tail_failed = false;             // a tail block gave up waiting (SLOT_TAIL_ERR seen by the host): the domain is unusable
+	bool             strip_first = false;             // hp_strip_step_batch: the batch's first iteration
+	bool             tail_allowed = false;            // inside hp_step_batch / hp_strip_step_batch (the host-driven split step has work in between)
+	bool             tail_want = false;               // step_begin_impl: this iteration qualifies, if the launch is small enough
+	int              tail_fresh = 0;                  // ... and this is what its advance would be told
+	bool             tail_done = false;               // launch_march: the launch carried it -- hp_step_end launches nothing
+	// speculative STRICT fp64 batches (hp_math.hpp: div_shared; spec_begin / spec_resolve below)
+	bool             spec_now = false;                // the flux launches queued now are the shared-reciprocal instantiations
+	uint32_t         spec_pending = 0;                // iterations of a speculative batch whose flag word has not been looked at yet
+	void*            spec_state = nullptr;            // snapshot in front of the batch: both state buffers ...
+	void*            spec_scalars = nullptr;          // ... Scalars<T> + the slot block
+	struct { int use_alt, adv_fresh; bool need_full_reduce, edge_dirty; long ghost_valid; uint64_t cells_calculated, iterations; } spec_host;
+	uint64_t         spec_batches = 0, spec_replays = 0;
+	OutputStage      out;
+	PeakTracker      peaks;
+	ProbeRecorder    probes;
+};
+
+namespace {
+
+// The pinned host block (hp_domain::host_scalars): byte offsets of its regions, each up to the next one's
+constexpr size_t HOST_PEAKS      = 128;     // the PeakBlock read back by hp_peaks_info
+constexpr size_t HOST_HANDSHAKE  = 256;     // the strips' handshakes: 8 elements out, and at + 128 the 8 that came back
+constexpr size_t HOST_TAIL_ERR   = 448;     // the sticky word of a tail block that gave up (tail_error_queue)
+constexpr size_t HOST_SPEC_FLAG  = 464;     // the flag word of a speculative STRICT batch (spec_resolve)
+constexpr size_t HOST_READBACK   = 480;     // the mailboxes' error word and the result of a round (peer_error_check, peer_round_now)
+constexpr size_t HOST_RINGS      = 496;     // the verdict of rings_really_differ
+constexpr size_t HOST_SCALARS_BYTES = 128, HOST_BLOCK_BYTES = 512;    // Scalars<T> as hp_read_scalars reads them back, at 0; the whole block
+static_assert(sizeof(Scalars<double>) <= HOST_SCALARS_BYTES && sizeof(Scalars<float>) <= HOST_SCALARS_BYTES, "Scalars<T> outgrew its region");
+static_assert(HOST_SCALARS_BYTES <= HOST_PEAKS && HOST_PEAKS + sizeof(PeakBlock) <= HOST_HANDSHAKE, "pinned block: scalars / peaks");
+static_assert(HOST_HANDSHAKE + 128 + 8 * sizeof(double) <= HOST_TAIL_ERR && HOST_TAIL_ERR + sizeof(double) <= HOST_SPEC_FLAG, "pinned block: handshake / tail word");
+static_assert(HOST_SPEC_FLAG + 8 <= HOST_READBACK && HOST_READBACK + 16 <= HOST_RINGS && HOST_RINGS + 8 <= HOST_BLOCK_BYTES, "pinned block: flag / read-backs / rings");
+
+int check_domain(hp_domain* d);           // (hp_engine.hip: every entry point that touches the device comes through it)
+
+inline int check_rows(const hp_domain* d, const int64_t row0, const int64_t nrows)
+{
+	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
+	return HP_OK;
+}
+
+} // namespace

@@ -3,19 +3,14 @@
 // Mirrors what the reference's CSchemeGodunov / CSchemeMUSCLHancock do against COCLDevice/COCLBuffer/COCLKernel
 // (buffers: CSchemeGodunov.cpp:789-892; iteration graph: :1617-1666) -- one HIP stream per domain stands in for
 // the reference's per-device command queue, stream order for its explicit queueBarrier() calls.
-#include "../../include/hipims_mi.h"
-#include "hp_kernels.hpp"
-#include "hp_output.hpp"
-#include "hp_peaks.hpp"
-#include "hp_probes.hpp"
+#include "hp_domain.hpp"        // fail / HIP_TRY, struct hp_domain, the map of its pinned block
+#include "hp_observers.hpp"     // output stage, peak tracker, probe recorder: their entry points and what a checkpoint does for them
 #include <hip/hip_ext.h>
-#include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <random>
@@ -23,11 +18,7 @@
 #include <vector>
 #include <unistd.h>
 
-using namespace hp;
-
 namespace {
-
-thread_local std::string g_last_error;
 
 constexpr size_t CFL_SLOT_BYTES = 1024;        // hp_math.hpp: SLOT_* elements, each on its own 256-B line
 
@@ -46,193 +37,6 @@ struct Rccl {
 	decltype(&ncclCommCount)     CommCount = nullptr;        // optional (reporting only)
 	std::string path;                                        // what the dynamic loader resolved the library to
 } g_rccl;
-
-std::atomic<hp_log_sink_t> g_log_sink{nullptr};
-std::atomic<void*>         g_log_user{nullptr};
-
-int fail(int code, const std::string& msg)
-{
-	g_last_error = msg;
-	if (hp_log_sink_t sink = g_log_sink.load(std::memory_order_acquire))
-		sink(HP_LOG_MODEL_STOP, g_last_error.c_str(), g_log_user.load(std::memory_order_acquire));
-	return code;
-}
-
-void log_line(int level, const std::string& msg)
-{
-	if (hp_log_sink_t sink = g_log_sink.load(std::memory_order_acquire))
-		sink(level, msg.c_str(), g_log_user.load(std::memory_order_acquire));
-}
-
-#define HIP_TRY(expr)                                                                                  \
-	do {                                                                                               \
-		hipError_t e_ = (expr);                                                                        \
-		if (e_ != hipSuccess)                                                                          \
-			return fail(HP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
-	} while (0)
-
-struct Boundary {
-	int      kind;         // 0 uniform, 1 gridded, 2 cell
-	int      definition;
-	int      discharge_def;
-	void*    cells;        // device: global cell ids (cell boundaries)
-	uint64_t count;
-	void*    data;         // device
-	uint64_t entries, grows, gcols;
-	double   interval, length, resolution, off_x, off_y;
-};
-
-} // namespace
-
-struct hp_domain {
-	hp_domain_desc_t desc;
-	hipStream_t      stream = nullptr;
-	size_t           cells = 0, esize = 0;
-	void*            state[2] = {nullptr, nullptr};   // [0] = primary "Cell states", [1] = "Cell states (alternate)"
-	void*            bed = nullptr;
-	void*            manning = nullptr;
-	void*            scalars = nullptr;               // Scalars<T> on the device
-	void*            cfl_slot = nullptr;              // CFL_SLOT_BYTES: running max | SLOT_SAVED last used max | SLOT_EDGE ring maxima of [0], [1]
-	bool             manning_uniform = false;         // found at upload: one value everywhere -> kernels skip the array
-	double           manning_value = 0.0;
-	bool             need_full_reduce = true;         // the remembered maximum is stale (upload / link import)
-	bool             edge_dirty = true;               // edge-ring maxima must be re-priced
-	bool             bdy_on_ring = false;             // a cell boundary imposes values on never-written ring cells: re-price every iteration
-	int              adv_fresh = 1;                   // does hp_step_end's advance kernel read a new maximum?
-	Tiling           tiling;                          // tile heights and row bands of its launches (hp_tiling.hpp: choose_tiling)
-	int              sweep_flip = 0;                  // parity of the whole-domain flux launches: every other one visits each band's tiles from
-	                                                  // the top down, so that it starts on the rows its predecessor wrote last (sweep_alternates)
-	void*            host_scalars = nullptr;          // pinned mirror
-	int              use_alt = 0;                     // bUseAlternateKernel
-	bool             in_step = false;
-	std::vector<Boundary> bdy;
-	// area boundaries carried by the flux kernel's fused epilogue (K1, FUSED): device copy of their descriptors
-	void*            fused_list = nullptr;
-	bool             fusable = false;                 // Godunov, tuned kernel, 1..FUSED_BDY_MAX uniform / coarse gridded boundaries, no cell boundary
-	int              fuse_next = 0;                   // this iteration is followed by another one of the same batch
-	uint64_t         cells_calculated = 0, iterations = 0;
-	hipEvent_t       ev_start = nullptr, ev_stop = nullptr;
-	// flux-kernel timing samples
-	int              timing_stride = 0;
-	uint64_t         timing_counter = 0;
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_events;   // pool, created by hp_kernel_timing
-	size_t           timing_used = 0;
-	double           timing_overhead_ms = 0.0;        // an empty event pair's own time (taken off every sample)
-	long             own_lo = 0, own_hi = 0;          // rows this rank owns (CFL reduction range)
-	// ghost rows of a strip: `ghost_rows` stored per interior side (g or 2g, g = the scheme's stencil reach), of which
-	// `ghost_valid` currently hold their owners' values; an iteration consumes g of them, the exchange refills them all
-	long             ghost_rows = 0, ghost_valid = 0, saved_ghost_valid = 0;
-	bool             split_now = false;               // this iteration is followed by an exchange: halo part on its own stream
-	// what the ranks told each other at the start of the batch (hp_strip_step_batch): which of them price a new maximum on
-	// the iterations that the ping-pong phase alone would not make them price
-	bool             strip_any_bdy = false, strip_any_full = false;
-	bool             strip_pairs = false;             // the batch's handshake: every rank can run iteration pairs (godunov_march2 over two-reach ghost rows)
-	// halo overlap (strip decomposition): the row segments next to the ghost rows run on their own stream so the
-	// neighbours' halo transfer can start while the interior segments are still being computed
-	bool             halo_overlap = false;
-	bool             halo_overlap_set = false;        // the host chose explicitly (hp_set_halo_overlap): comm_init keeps it
-	hipStream_t      stream_halo = nullptr;
-	hipEvent_t       ev_fork = nullptr, ev_halo = nullptr;
-	bool             fork_is_advance = false;         // ev_fork was recorded BY the last advance_time launch
-	// strip decomposition driven from C++ (hp_strip_*): one RCCL communicator over the ranks, strip neighbours = rank +- 1
-	// device-side checkpoint (hp_state_save / hp_state_restore)
-	void*            saved_state = nullptr;
-	void*            saved_scalars = nullptr;         // Scalars<T> + the four CFL slots
-	bool             saved_valid = false;
-	bool             saved_full_reduce = true, saved_edge_dirty = true;
-	int              saved_use_alt = 0;
-	ncclComm_t       comm = nullptr;
-	int              comm_rank = 0, comm_world = 1;
-	hipEvent_t       ev_xchg = nullptr;               // ghost rows of the iteration in flight have arrived
-	// the maximum over all strips through peer-written mailboxes (hp_strip_peer_*; PeerBox in hp_kernels.hpp)
-	unsigned long long*  peer_mine = nullptr;         // this rank's mailbox (uncached device memory)
-	unsigned long long** peer_table = nullptr;        // device: every rank's mailbox as this device addresses it
-	std::vector<void*>   peer_mapped;                 // IPC mappings to close
-	int              peer_world = 0, peer_rank = 0;
-	bool             peer_agreed = false;             // every rank of the communicator passed the connection test: the strip loop uses them
-	uint64_t         peer_rounds = 0;                 // reductions so far (its parity picks the mailbox set; the same on every rank)
-	// ghost rows written straight into the neighbours' state buffers (PeerPush): [side: 0 south, 1 north][ping-pong buffer]
-	void*            peer_state[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-	long             peer_rows[2] = {0, 0};           // the neighbours' local row counts
-	unsigned*        push_arrived = nullptr;          // device counter of the push blocks
-	bool             peer_direct = false;             // every rank reached its neighbours' buffers: no transfer library inside an iteration
-	bool             push_now = false;                // this iteration's advance kernel carries the ghost rows
-	// the flux launch's own tail block instead of a separate advance launch (LaunchTail, hp_kernels.hpp): small launches only
-	unsigned long long* tail_words = nullptr;         // one word per flux block (EMPTY between launches)
-	bool             rings_differ = false;            // a partial state upload went into ONE buffer: the edge rings of the two may differ -- no iteration pairs until the next full upload (pair_eligible)
-	bool             saved_rings_differ = false;
-	bool             rings_checked = false;           // ... and have been compared since (rings_really_differ): the flag is a fact, not a maybe
-	bool             fill_now = false;                // this iteration's K1 launch stores the cells the reference leaves untouched as well (dispatch_begin)
-	bool             other_stale = false;             // pairs (godunov_march2) ran since the non-current state buffer last held a state the single-iteration kernels can build on
-	// quirk Q3 across pair launches, exactly (hp_kernels.hpp: PairAux): stamps of the cells whose first-step stale value the next launch needs
-	void*            z_state = nullptr;               // stamp records, one per cell: State4<T> + the number of the pair launch that wrote it (allocated with the first pair)
-	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
-	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while other_stale holds
-	// still records of the FAST fp64 pair kernel (hp_kernels.hpp: StillRec; round 8): two halves of windows x rows records, the last launch's
-	// in half still_rec_half, then two counters (hp_pair_stats).  Valid while no writer of either state buffer has run since that launch
-	// other than such launches themselves (still_rec_forget)
-	void*            still_rec = nullptr;
-	size_t           still_rec_slots = 0;             // records per half
-	int              still_rec_half = 0;
-	bool             still_rec_valid = false;
-	bool             still_rec_last = false;          // the last pair launch wrote records (hp_pair_stats)
-	bool             saved_m1_valid = false;
-	bool             pair_fused_next = false;         // the last pair stored its state with the next iteration's boundaries applied (SLOT_BDY = 1)
-	bool             m1_valid = false;                // area boundaries: cfl_slot[SLOT_M1] prices the primary buffer with the next iteration's boundaries (left by the last pair)
-	uint64_t         pair_cold_starts = 0;
-	// STRICT: pairs or single iterations, by measurement (pair_tuner: the two are the same bits; which is faster depends on how much of
-	// the water stands still)
-	hipEvent_t       tune_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	int              tune_phase = 0;                  // 0: sample at the next opportunity, 1: a sample is in flight, 2: decided
-	bool             tune_prefer_pairs = true;
-	uint64_t         tune_next = 0;                   // iteration count from which the next sample is due
-	uint64_t         tune_samples = 0, tune_switches = 0;
-	float            tune_pair_ms = 0.f, tune_single_ms = 0.f;
-	uint64_t         pairs = 0;                       // iteration pairs run by it
-	unsigned         single_streak = 0;               // single iterations since the last pair (step_begin_impl: which launches hp_kernel_timing samples)
-	uint64_t         flux_launches = 0, flux_launches_tailed = 0;   // whole-domain flux launches of hp_step_batch / hp_strip_step_batch, and how many carried their own tail block
-	bool             tail_failed = false;             // a tail block gave up waiting (SLOT_TAIL_ERR seen by the host): the domain is unusable
-	bool             strip_first = false;             // hp_strip_step_batch: the batch's first iteration
-	bool             tail_allowed = false;            // inside hp_step_batch / hp_strip_step_batch (the host-driven split step has work in between)
-	bool             tail_want = false;               // step_begin_impl: this iteration qualifies, if the launch is small enough
-	int              tail_fresh = 0;                  // ... and this is what its advance would be told
-	bool             tail_done = false;               // launch_march: the launch carried it -- hp_step_end launches nothing
-	// speculative STRICT fp64 batches (hp_math.hpp: div_shared; spec_begin / spec_resolve below)
-	bool             spec_now = false;                // the flux launches queued now are the shared-reciprocal instantiations
-	uint32_t         spec_pending = 0;                // iterations of a speculative batch whose flag word has not been looked at yet
-	void*            spec_state = nullptr;            // snapshot in front of the batch: both state buffers ...
-	void*            spec_scalars = nullptr;          // ... Scalars<T> + the slot block
-	struct { int use_alt, adv_fresh; bool need_full_reduce, edge_dirty; long ghost_valid; uint64_t cells_calculated, iterations; } spec_host;
-	uint64_t         spec_batches = 0, spec_replays = 0;
-	// the output stage (hp_output.hpp; hp_domain_derive / hp_domain_stats): allocated on first use
-	void*            out_scratch = nullptr;           // rasters of one block of rows, value after value (at most OUT_SCRATCH_CAP bytes)
-	size_t           out_scratch_bytes = 0;
-	void*            out_stats = nullptr;             // STATS_MAX_BLOCKS block partials + the folded result
-	void*            out_stats_host = nullptr;        // pinned: the folded result
-	// the peak tracker (hp_peaks.hpp; hp_peaks_*): nothing of it exists while tracking is off
-	bool             peaks_on = false;
-	unsigned         peaks_mask = 0;                  // HP_PEAK_* bits enabled
-	int              peaks_count = 0;                 // ... how many: the accumulators lie one after the other in peaks_acc, in code order
-	double           peaks_arrival = 0.0;
-	double*          peaks_acc = nullptr;             // peaks_count x cells fp64, followed by the PeakBlock
-	uint64_t         peaks_samples = 0;               // samples queued since enable / reset (its parity picks the time slot)
-	uint64_t         peaks_epoch = 0;                 // counts enable / disable: a checkpoint's peaks belong to one epoch
-	void*            saved_peaks = nullptr;           // hp_state_save's copy of peaks_acc (accumulators + block)
-	bool             saved_peaks_valid = false;
-	uint64_t         saved_peaks_epoch = 0, saved_peaks_samples = 0;
-	// the probe recorder (hp_probes.hpp; hp_probes_*): nothing of it exists while recording is off
-	bool             probes_on = false;
-	void*            probes_mem = nullptr;            // the lists (probes_lists points into it)
-	double*          probes_records = nullptr;        // probes_capacity records of probes_stride fp64 words
-	ProbeLists       probes_lists = {};
-	uint64_t         probes_capacity = 0, probes_stride = 0;
-	uint64_t         probes_samples = 0;              // records queued since enable / reset: the next sample's index
-	uint64_t         probes_epoch = 0;                // counts enable / disable / reset: a checkpoint's count belongs to one epoch
-	bool             saved_probes_valid = false;
-	uint64_t         saved_probes_epoch = 0, saved_probes_samples = 0;
-};
-
-namespace {
 
 void peer_release(hp_domain* d);      // (mailboxes of the peer-written maximum, further down)
 PeerBox peer_box(hp_domain* d, bool use, long timeout_ms = 0);
@@ -863,7 +667,6 @@ static bool pairs_possible(const hp_domain* d)          // a single domain
 // After partial uploads (rings_differ: the two buffers' edge rings MAY differ) the rings are compared once, the first time pairs are
 // wanted: block-wise loads of a whole grid (hp_domain_upload_rows over all rows: how grids too big for one host array arrive) leave
 // them equal to the zero-filled other buffer's wherever the ring is the usual closed wall (state 0), and such domains pair.  Blocks.
-constexpr size_t HOST_RINGS = 496;          // byte offset in the pinned block
 static int rings_really_differ(hp_domain* d)
 {
 	if (!d->rings_differ || d->rings_checked) return HP_OK;
@@ -1199,127 +1002,6 @@ int check_domain(hp_domain* d)
 
 } // namespace
 
-// ---- the output stage on the device (hp_output.hpp) ----
-namespace {
-
-static_assert(OUT_VALUES == HP_OUT_COUNT && OUT_FROUDE == HP_OUT_FROUDE && OUT_DEPTH == HP_OUT_DEPTH, "hp_output.hpp and hipims_mi.h disagree");
-static_assert(sizeof(hp_domain_stats_t) == 64, "hp_domain_stats_t layout");
-
-// Cap of the raster scratch.  A request that needs more is worked through in blocks of rows; the kernel of a block runs in
-// well under a hundredth of the time its rasters take to cross the host link, so blocks are queued one after the other on the
-// domain's stream and nothing would be won by overlapping them.
-constexpr size_t OUT_SCRATCH_CAP = (size_t)256 << 20;
-
-template <typename T, typename O>
-int derive_blocks(hp_domain* d, const int* values, const int count, void* const* rasters, const int64_t row0, const int64_t nrows,
-                  const int64_t block_rows)
-{
-	const size_t cols = (size_t)d->desc.cols;
-	const State4<T>* state = (const State4<T>*)d->state[d->use_alt];      // what hp_domain_download(HP_ARRAY_STATE) reads
-	for (int64_t r = 0; r < nrows; r += block_rows) {
-		const int64_t rows_now = std::min<int64_t>(block_rows, nrows - r);
-		const size_t n = (size_t)rows_now * cols;
-		DeriveTargets t = {};
-		for (int k = 0; k < count; ++k) {
-			t.raster[values[k]] = (char*)d->out_scratch + (size_t)k * n * sizeof(O);
-			t.mask |= 1u << values[k];
-		}
-		const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
-		hipLaunchKernelGGL((derive_rasters<T, O>), dim3(blocks), dim3(256), 0, d->stream, state, (const T*)d->bed,
-		                   (size_t)(row0 + r) * cols, n, d->desc.dx, t);
-		HIP_TRY(hipGetLastError());
-		for (int k = 0; k < count; ++k)
-			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)r * cols * sizeof(O), t.raster[values[k]], n * sizeof(O),
-			                       hipMemcpyDeviceToHost, d->stream));
-	}
-	return HP_OK;
-}
-
-// The raster scratch of the output stage, at least `need` bytes.  The new block first: if it cannot be had, the smaller one
-// that served so far stays.
-int out_scratch_reserve(hp_domain* d, const size_t need, const char* who)
-{
-	if (need <= d->out_scratch_bytes) return HP_OK;
-	void* grown = nullptr;
-	const hipError_t e = hipMalloc(&grown, need);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();                                      // (the launches of later steps ask for the last error: this one is dealt with here)
-		return fail(HP_ERR_HIP, std::string(who) + ": cannot allocate " + std::to_string(need) + " bytes of raster scratch: " + hipGetErrorString(e));
-	}
-	if (d->out_scratch) {
-		hipError_t e2 = hipStreamSynchronize(d->stream);              // (an earlier call's copies may still be reading the old block)
-		if (e2 == hipSuccess) e2 = hipFree(d->out_scratch);
-		if (e2 != hipSuccess) { hipFree(grown); return fail(HP_ERR_HIP, std::string(who) + ": releasing the raster scratch: " + hipGetErrorString(e2)); }
-	}
-	d->out_scratch = grown;
-	d->out_scratch_bytes = need;
-	return HP_OK;
-}
-
-// ---- the peak tracker (hp_peaks.hpp) ----
-static_assert(PEAK_VALUES == HP_PEAK_COUNT && PEAK_SPEED == HP_PEAK_SPEED && PEAK_UNIT_DISCHARGE == HP_PEAK_UNIT_DISCHARGE &&
-              PEAK_HAZARD == HP_PEAK_HAZARD && PEAK_ARRIVAL_TIME == HP_PEAK_ARRIVAL_TIME && PEAK_WET_DURATION == HP_PEAK_WET_DURATION,
-              "hp_peaks.hpp and hipims_mi.h disagree");
-static_assert(sizeof(hp_peaks_desc_t) == 16, "hp_peaks_desc_t layout");
-constexpr size_t HOST_PEAKS = 128;           // byte offset in the pinned block: the PeakBlock read back by hp_peaks_info
-
-inline size_t peaks_bytes(const hp_domain* d) { return (size_t)d->peaks_count * d->cells * sizeof(double) + sizeof(PeakBlock); }
-inline PeakBlock* peaks_block(const hp_domain* d) { return (PeakBlock*)(d->peaks_acc + (size_t)d->peaks_count * d->cells); }
-// accumulator raster of an enabled value: they lie in code order
-inline double* peaks_raster(const hp_domain* d, const int value)
-{
-	return d->peaks_acc + (size_t)__builtin_popcount(d->peaks_mask & ((1u << value) - 1u)) * d->cells;
-}
-// a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
-inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
-
-int peaks_reset_queue(hp_domain* d)
-{
-	const size_t n = (size_t)d->peaks_count * d->cells;
-	if (d->desc.precision == 8)
-		hipLaunchKernelGGL((peaks_reset<double>), dim3(stream_blocks(n)), dim3(256), 0, d->stream, d->peaks_acc, n, (const Scalars<double>*)d->scalars, peaks_block(d));
-	else
-		hipLaunchKernelGGL((peaks_reset<float>), dim3(stream_blocks(n)), dim3(256), 0, d->stream, d->peaks_acc, n, (const Scalars<float>*)d->scalars, peaks_block(d));
-	HIP_TRY(hipGetLastError());
-	d->peaks_samples = 0;
-	return HP_OK;
-}
-
-// frees the tracker (the stream is drained first: queued samples and reads still use the accumulators)
-int peaks_release(hp_domain* d)
-{
-	if (!d->peaks_on && !d->saved_peaks) return HP_OK;
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	hipFree(d->peaks_acc); hipFree(d->saved_peaks);
-	d->peaks_acc = nullptr; d->saved_peaks = nullptr;
-	d->saved_peaks_valid = false;
-	if (d->peaks_on) ++d->peaks_epoch;
-	d->peaks_on = false;
-	d->peaks_mask = 0; d->peaks_count = 0; d->peaks_samples = 0;
-	return HP_OK;
-}
-
-// ---- the probe recorder (hp_probes.hpp) ----
-static_assert(sizeof(hp_probes_desc_t) == 64, "hp_probes_desc_t layout");
-constexpr uint64_t PROBES_MAX_GAUGES = 65536, PROBES_MAX_SECTIONS = 1024;
-constexpr uint64_t PROBES_MAX_BYTES = 256ull << 20;                        // of the record buffer
-
-// frees the recorder (the stream is drained first: queued samples and reads still use the lists and the records)
-int probes_release(hp_domain* d)
-{
-	if (!d->probes_on) return HP_OK;
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	hipFree(d->probes_mem); hipFree(d->probes_records);
-	d->probes_mem = nullptr; d->probes_records = nullptr;
-	d->probes_lists = ProbeLists{};
-	d->probes_on = false;
-	d->probes_capacity = d->probes_stride = d->probes_samples = 0;
-	++d->probes_epoch;
-	return HP_OK;
-}
-
-} // namespace
-
 // =================================================================================================
 extern "C" {
 
@@ -1462,7 +1144,7 @@ int hp_domain_create(const hp_domain_desc_t* desc, hp_domain_t** out)
 
 	HIP_TRY_C(hipMalloc((void**)&d->tail_words, 2 * (TAIL_MAX_BLOCKS + 8) * sizeof(unsigned long long)));
 	HIP_TRY_C(hipMemset(d->tail_words, 0xff, 2 * (TAIL_MAX_BLOCKS + 8) * sizeof(unsigned long long)));      // every word EMPTY (two arrays: LaunchTail::done, done1)
-	HIP_TRY_C(hipHostMalloc(&d->host_scalars, 512, hipHostMallocDefault));
+	HIP_TRY_C(hipHostMalloc(&d->host_scalars, HOST_BLOCK_BYTES, hipHostMallocDefault));
 	HIP_TRY_C(hipMemset(d->state[0], 0, d->cells * 4 * d->esize));
 	HIP_TRY_C(hipMemset(d->state[1], 0, d->cells * 4 * d->esize));
 	HIP_TRY_C(hipMemset(d->bed, 0, d->cells * d->esize));
@@ -1500,10 +1182,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	hipFree(d->out_scratch); hipFree(d->out_stats);
-	hipFree(d->peaks_acc); hipFree(d->saved_peaks);
-	hipFree(d->probes_mem); hipFree(d->probes_records);
-	if (d->out_stats_host) hipHostFree(d->out_stats_host);
+	out_destroy(d); peaks_destroy(d); probes_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1576,15 +1255,7 @@ int hp_state_save(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_save between hp_step_begin and hp_step_end");
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
-	// the copy of the peak accumulators first: if it cannot be had the call fails with the checkpoint before it, state and peaks, untouched
-	if (d->peaks_on && !d->saved_peaks) {
-		const hipError_t e = hipMalloc(&d->saved_peaks, peaks_bytes(d));
-		if (e != hipSuccess) {
-			d->saved_peaks = nullptr;
-			(void)hipGetLastError();
-			return fail(HP_ERR_HIP, std::string("hp_state_save: cannot allocate the copy of the peak accumulators: ") + hipGetErrorString(e));
-		}
-	}
+	if ((rc = peaks_save_reserve(d)) != HP_OK) return rc;            // (first: a failure leaves the checkpoint before it untouched)
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1605,18 +1276,8 @@ int hp_state_save(hp_domain_t* d)
 	d->saved_m1_valid = d->m1_valid;
 	d->saved_ghost_valid = d->ghost_valid;
 	d->saved_valid = true;
-	// the peak tracker, while it is on: accumulators and block in one copy
-	d->saved_peaks_valid = false;
-	if (d->peaks_on) {
-		HIP_TRY(hipMemcpyAsync(d->saved_peaks, d->peaks_acc, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
-		d->saved_peaks_epoch = d->peaks_epoch;
-		d->saved_peaks_samples = d->peaks_samples;
-		d->saved_peaks_valid = true;
-	}
-	// the probe recorder: the sample count only (the records taken after it are re-recorded by the samples a restore repeats)
-	d->saved_probes_valid = d->probes_on;
-	d->saved_probes_epoch = d->probes_epoch;
-	d->saved_probes_samples = d->probes_samples;
+	if ((rc = peaks_save(d)) != HP_OK) return rc;
+	probes_save(d);
 	return HP_OK;
 }
 
@@ -1658,24 +1319,8 @@ int hp_state_restore(hp_domain_t* d)
 	d->need_full_reduce = d->need_full_reduce || d->saved_full_reduce;
 	d->edge_dirty = d->edge_dirty || d->saved_edge_dirty;
 	d->fork_is_advance = false;
-	if (d->peaks_on) {
-		if (d->saved_peaks_valid && d->saved_peaks_epoch == d->peaks_epoch) {
-			HIP_TRY(hipMemcpyAsync(d->peaks_acc, d->saved_peaks, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
-			d->peaks_samples = d->saved_peaks_samples;
-		} else {
-			// (the time block has come back above: t_previous is the restored time)
-			if ((rc = peaks_reset_queue(d)) != HP_OK) return rc;
-			log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no peaks (the tracker was enabled after it was taken): the peaks are reset");
-		}
-	}
-	if (d->probes_on) {
-		if (d->saved_probes_valid && d->saved_probes_epoch == d->probes_epoch) {
-			d->probes_samples = d->saved_probes_samples;
-		} else {
-			d->probes_samples = 0;
-			log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no probe sample count (the recorder was enabled or reset after it was taken): the count is 0");
-		}
-	}
+	if ((rc = peaks_restore(d)) != HP_OK) return rc;
+	probes_restore(d);
 	return HP_OK;
 }
 
@@ -1684,7 +1329,7 @@ int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int6
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
-	if (row0 < 0 || nrows < 0 || row0 + nrows > d->desc.rows) return fail(HP_ERR_INVALID, "row range out of bounds");
+	if ((rc = check_rows(d, row0, nrows)) != HP_OK) return rc;
 	const size_t per_row = (size_t)d->desc.cols * d->esize * (which == HP_ARRAY_STATE ? 4 : 1);
 	const void* base;
 	switch (which) {
@@ -1698,362 +1343,6 @@ int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int6
 	return HP_OK;
 }
 
-// ---- the output stage on the device (hp_output.hpp: derive_blocks above) ----
-int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
-{
-	// argument checks first: none of them touches the device, and those that do not need the domain come before it
-	if (count < 1 || count > HP_OUT_COUNT) return fail(HP_ERR_INVALID, "hp_domain_derive: count outside 1..HP_OUT_COUNT");
-	if (!values || !rasters) return fail(HP_ERR_INVALID, "hp_domain_derive: values / rasters == NULL");
-	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, "hp_domain_derive: element_bytes must be 4 or 8");
-	unsigned seen = 0;
-	for (int k = 0; k < count; ++k) {
-		if (values[k] < 0 || values[k] >= HP_OUT_COUNT) return fail(HP_ERR_INVALID, "hp_domain_derive: unknown value " + std::to_string(values[k]));
-		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, "hp_domain_derive: value " + std::to_string(values[k]) + " listed twice");
-		seen |= 1u << values[k];
-		if (!rasters[k]) return fail(HP_ERR_INVALID, "hp_domain_derive: rasters[" + std::to_string(k) + "] == NULL");
-	}
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
-	if (nrows == 0) return HP_OK;
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	const size_t row_bytes = (size_t)d->desc.cols * (size_t)count * (size_t)element_bytes;      // of all requested rasters together
-	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
-	const size_t need = (size_t)block_rows * row_bytes;
-	if ((rc = out_scratch_reserve(d, need, "hp_domain_derive")) != HP_OK) return rc;
-	if (d->desc.precision == 8)
-		return element_bytes == 8 ? derive_blocks<double, double>(d, values, count, rasters, row0, nrows, block_rows)
-		                          : derive_blocks<double, float>(d, values, count, rasters, row0, nrows, block_rows);
-	return element_bytes == 8 ? derive_blocks<float, double>(d, values, count, rasters, row0, nrows, block_rows)
-	                          : derive_blocks<float, float>(d, values, count, rasters, row0, nrows, block_rows);
-}
-
-int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats_t* out)
-{
-	if (!out) return fail(HP_ERR_INVALID, "hp_domain_stats: out == NULL");
-	if (out->struct_size != sizeof(hp_domain_stats_t)) return fail(HP_ERR_INVALID, "hp_domain_stats_t size mismatch (ABI)");
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
-	out->reserved = 0;
-	out->cells = out->cells_wet = 0;
-	out->volume = out->max_depth = out->max_speed = 0.0;
-	out->max_depth_cell = out->max_speed_cell = UINT64_MAX;
-	if (nrows == 0) return HP_OK;
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->out_stats) {
-		const hipError_t e = hipMalloc(&d->out_stats, (STATS_MAX_BLOCKS + 1) * sizeof(StatsPart));
-		if (e != hipSuccess) {
-			d->out_stats = nullptr;
-			(void)hipGetLastError();
-			return fail(HP_ERR_HIP, std::string("hp_domain_stats: cannot allocate the block partials: ") + hipGetErrorString(e));
-		}
-	}
-	if (!d->out_stats_host) {
-		const hipError_t e = hipHostMalloc(&d->out_stats_host, sizeof(StatsPart), hipHostMallocDefault);
-		if (e != hipSuccess) {
-			d->out_stats_host = nullptr;
-			(void)hipGetLastError();
-			return fail(HP_ERR_HIP, std::string("hp_domain_stats: cannot allocate pinned memory: ") + hipGetErrorString(e));
-		}
-	}
-	const size_t cols = (size_t)d->desc.cols, n = (size_t)nrows * cols, first = (size_t)row0 * cols;
-	// the launch shape is a function of the range alone: the same range is always summed in the same order
-	const int blocks = (int)std::min<size_t>((n + 255) / 256, STATS_MAX_BLOCKS);
-	StatsPart* partial = (StatsPart*)d->out_stats;
-	if (d->desc.precision == 8)
-		hipLaunchKernelGGL((domain_stats<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed, first, n, partial);
-	else
-		hipLaunchKernelGGL((domain_stats<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed, first, n, partial);
-	HIP_TRY(hipGetLastError());
-	hipLaunchKernelGGL(domain_stats_fold, dim3(1), dim3(256), 0, d->stream, partial, blocks, partial + STATS_MAX_BLOCKS);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(d->out_stats_host, partial + STATS_MAX_BLOCKS, sizeof(StatsPart), hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	const StatsPart& s = *(const StatsPart*)d->out_stats_host;
-	out->cells = s.cells; out->cells_wet = s.wet;
-	out->volume = d->desc.dx * d->desc.dx * s.sum;
-	if (s.depth_cell != ~0ull) { out->max_depth = s.max_depth; out->max_depth_cell = s.depth_cell; }
-	if (s.speed_cell != ~0ull) { out->max_speed = s.max_speed; out->max_speed_cell = s.speed_cell; }
-	return HP_OK;
-}
-
-// ---- the peak tracker (hp_peaks.hpp) ----
-int hp_peaks_enable(hp_domain_t* d, const hp_peaks_desc_t* desc)
-{
-	if (!desc) return fail(HP_ERR_INVALID, "hp_peaks_enable: desc == NULL");
-	if (desc->struct_size != sizeof(hp_peaks_desc_t)) return fail(HP_ERR_INVALID, "hp_peaks_desc_t size mismatch (ABI)");
-	if (desc->values_mask == 0) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask is empty");
-	if (desc->values_mask >> HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask names an unknown value");
-	if (!(desc->arrival_depth >= OUT_WET)) return fail(HP_ERR_INVALID, "hp_peaks_enable: arrival_depth must be at least 1e-8");
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_enable between hp_step_begin and hp_step_end");
-	if ((rc = peaks_release(d)) != HP_OK) return rc;
-	d->peaks_count = __builtin_popcount(desc->values_mask);
-	const hipError_t e = hipMalloc((void**)&d->peaks_acc, peaks_bytes(d));
-	if (e != hipSuccess) {
-		d->peaks_acc = nullptr; d->peaks_count = 0;
-		(void)hipGetLastError();
-		return fail(HP_ERR_HIP, std::string("hp_peaks_enable: cannot allocate the accumulators: ") + hipGetErrorString(e));
-	}
-	d->peaks_mask = desc->values_mask;
-	d->peaks_arrival = desc->arrival_depth;
-	d->peaks_on = true;
-	++d->peaks_epoch;
-	if ((rc = peaks_reset_queue(d)) != HP_OK) { peaks_release(d); return rc; }
-	return HP_OK;
-}
-
-int hp_peaks_disable(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	return peaks_release(d);
-}
-
-int hp_peaks_reset(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_reset before hp_peaks_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_reset between hp_step_begin and hp_step_end");
-	return peaks_reset_queue(d);
-}
-
-int hp_peaks_sample(hp_domain_t* d)
-{
-	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
-	if (rc != HP_OK) return rc;
-	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_sample before hp_peaks_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_sample between hp_step_begin and hp_step_end");
-	PeakTargets t = {};
-	for (int v = 0; v < HP_PEAK_COUNT; ++v)
-		if (d->peaks_mask & (1u << v)) t.acc[v] = peaks_raster(d, v);
-	t.mask = d->peaks_mask;
-	t.arrival_depth = d->peaks_arrival;
-	const unsigned sample = (unsigned)(d->peaks_samples & 1u);          // picks the time slot; `first`: the first sample since enable / reset
-	const int first = d->peaks_samples == 0;
-	const unsigned blocks = stream_blocks(d->cells);
-	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
-	if (d->desc.precision == 8)
-		hipLaunchKernelGGL((track_peaks<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed,
-		                   (const Scalars<double>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
-	else
-		hipLaunchKernelGGL((track_peaks<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed,
-		                   (const Scalars<float>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
-	HIP_TRY(hipGetLastError());
-	++d->peaks_samples;
-	return HP_OK;
-}
-
-int hp_peaks_read(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
-{
-	// argument checks first, as in hp_domain_derive: none of them touches the device
-	if (count < 1 || count > HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_read: count outside 1..HP_PEAK_COUNT");
-	if (!values || !rasters) return fail(HP_ERR_INVALID, "hp_peaks_read: values / rasters == NULL");
-	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, "hp_peaks_read: element_bytes must be 4 or 8");
-	unsigned seen = 0;
-	for (int k = 0; k < count; ++k) {
-		if (values[k] < 0 || values[k] >= HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_read: unknown value " + std::to_string(values[k]));
-		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, "hp_peaks_read: value " + std::to_string(values[k]) + " listed twice");
-		seen |= 1u << values[k];
-		if (!rasters[k]) return fail(HP_ERR_INVALID, "hp_peaks_read: rasters[" + std::to_string(k) + "] == NULL");
-	}
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_read before hp_peaks_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_read between hp_step_begin and hp_step_end");
-	if (seen & ~d->peaks_mask) return fail(HP_ERR_INVALID, "hp_peaks_read: a value that hp_peaks_enable's values_mask does not track");
-	if (row0 < 0 || nrows < 0 || row0 > d->desc.rows || nrows > d->desc.rows - row0) return fail(HP_ERR_INVALID, "row range out of bounds");
-	if (nrows == 0) return HP_OK;
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	const size_t cols = (size_t)d->desc.cols;
-	if (element_bytes == 8) {                                             // whole rows are contiguous: the accumulators themselves
-		for (int k = 0; k < count; ++k)
-			HIP_TRY(hipMemcpyAsync(rasters[k], peaks_raster(d, values[k]) + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double),
-			                       hipMemcpyDeviceToHost, d->stream));
-		return HP_OK;
-	}
-	const size_t row_bytes = cols * (size_t)count * sizeof(float);
-	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
-	if ((rc = out_scratch_reserve(d, (size_t)block_rows * row_bytes, "hp_peaks_read")) != HP_OK) return rc;
-	for (int64_t r = 0; r < nrows; r += block_rows) {
-		const size_t n = (size_t)std::min<int64_t>(block_rows, nrows - r) * cols;
-		for (int k = 0; k < count; ++k) {
-			float* out = (float*)d->out_scratch + (size_t)k * n;
-			hipLaunchKernelGGL(peaks_round, dim3(stream_blocks(n)), dim3(256), 0, d->stream,
-			                   (const double*)(peaks_raster(d, values[k]) + (size_t)(row0 + r) * cols), out, n);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)r * cols * sizeof(float), out, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-		}
-	}
-	return HP_OK;
-}
-
-int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_last)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->peaks_on) return fail(HP_ERR_STATE, "hp_peaks_info before hp_peaks_enable");
-	PeakBlock* host = (PeakBlock*)((char*)d->host_scalars + HOST_PEAKS);
-	HIP_TRY(hipMemcpyAsync(host, peaks_block(d), sizeof(PeakBlock), hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	if (samples) *samples = d->peaks_samples;
-	if (t_first) *t_first = host->t_first;
-	if (t_last) *t_last = host->slot[d->peaks_samples & 1u];                 // (sample n - 1 stored its time into slot n & 1)
-	return HP_OK;
-}
-
-// ---- the probe recorder (hp_probes.hpp) ----
-int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
-{
-	// argument checks first: none of them touches the device
-	if (!desc) return fail(HP_ERR_INVALID, "hp_probes_enable: desc == NULL");
-	if (desc->struct_size != sizeof(hp_probes_desc_t)) return fail(HP_ERR_INVALID, "hp_probes_desc_t size mismatch (ABI)");
-	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: capacity must be at least 1");
-	const uint64_t G = desc->gauge_count, S = desc->section_count;
-	if (G > PROBES_MAX_GAUGES) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 65536 gauges");
-	if (S > PROBES_MAX_SECTIONS) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 1024 sections");
-	if (G + S < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: neither a gauge nor a section");
-	if (G && !desc->gauge_cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge_cells == NULL");
-	if (S && (!desc->section_offsets || !desc->section_cells || !desc->section_wx || !desc->section_wy))
-		return fail(HP_ERR_INVALID, "hp_probes_enable: a section array == NULL");
-	const uint64_t stride = 1 + PROBE_GAUGE_WORDS * G + S;
-	if ((uint64_t)desc->capacity * stride * sizeof(double) > PROBES_MAX_BYTES)
-		return fail(HP_ERR_INVALID, "hp_probes_enable: capacity x stride x 8 exceeds 256 MiB");
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	const uint64_t cells = d->cells;
-	for (uint64_t g = 0; g < G; ++g)
-		if (desc->gauge_cells[g] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge " + std::to_string(g) + ": cell id outside the local array");
-	uint64_t M = 0;
-	if (S) {
-		if (desc->section_offsets[0] != 0) return fail(HP_ERR_INVALID, "hp_probes_enable: section_offsets[0] must be 0");
-		for (uint64_t s = 0; s < S; ++s) {
-			const uint64_t lo = desc->section_offsets[s], hi = desc->section_offsets[s + 1];
-			if (hi < lo || hi - lo < 2) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + " is shorter than 2 entries");
-			if (hi > (1ull << 32)) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + ": offsets out of range");
-		}
-		M = desc->section_offsets[S];
-		for (uint64_t e = 0; e < M; ++e) {
-			if (desc->section_cells[e] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": cell id outside the local array");
-			if (desc->section_wx[e] < -1 || desc->section_wx[e] > 1 || desc->section_wy[e] < -1 || desc->section_wy[e] > 1)
-				return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": weight outside {-1, 0, 1}");
-		}
-	}
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_enable between hp_step_begin and hp_step_end");
-	if ((rc = probes_release(d)) != HP_OK) return rc;
-	// one block for the lists: [gauge cells | section offsets | section cells | wx | wy], the 8-byte arrays first
-	const size_t words = (size_t)(G + (S ? S + 1 : 0) + M);
-	const size_t list_bytes = words * 8 + 2 * (size_t)M;
-	std::vector<unsigned char> host(list_bytes);
-	uint64_t* w = (uint64_t*)host.data();
-	if (G) std::memcpy(w, desc->gauge_cells, G * 8);
-	if (S) {
-		std::memcpy(w + G, desc->section_offsets, (S + 1) * 8);
-		std::memcpy(w + G + S + 1, desc->section_cells, M * 8);
-		std::memcpy(host.data() + words * 8, desc->section_wx, M);
-		std::memcpy(host.data() + words * 8 + M, desc->section_wy, M);
-	}
-	hipError_t e = hipMalloc(&d->probes_mem, list_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&d->probes_records, (size_t)desc->capacity * stride * sizeof(double));
-	if (e == hipSuccess) e = hipMemcpyAsync(d->probes_mem, host.data(), list_bytes, hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (`host` goes away with this call)
-	if (e != hipSuccess) {
-		hipFree(d->probes_mem); hipFree(d->probes_records);
-		d->probes_mem = nullptr; d->probes_records = nullptr;
-		(void)hipGetLastError();
-		return fail(HP_ERR_HIP, std::string("hp_probes_enable: cannot allocate the lists and the record buffer: ") + hipGetErrorString(e));
-	}
-	const unsigned long long* dw = (const unsigned long long*)d->probes_mem;
-	ProbeLists& p = d->probes_lists;
-	p.gauge_cells = dw;
-	p.section_offsets = dw + G;
-	p.section_cells = dw + G + (S ? S + 1 : 0);
-	p.section_wx = (const signed char*)d->probes_mem + words * 8;
-	p.section_wy = p.section_wx + M;
-	p.gauges = G;
-	p.gauge_blocks = (unsigned)((G + 255) / 256);
-	p.sections = (unsigned)S;
-	d->probes_capacity = desc->capacity;
-	d->probes_stride = stride;
-	d->probes_samples = 0;
-	d->probes_on = true;
-	++d->probes_epoch;
-	return HP_OK;
-}
-
-int hp_probes_disable(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	return probes_release(d);
-}
-
-int hp_probes_reset(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_reset before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_reset between hp_step_begin and hp_step_end");
-	d->probes_samples = 0;                   // (stream order: a read queued before this call has its records before a later sample overwrites them)
-	++d->probes_epoch;
-	return HP_OK;
-}
-
-int hp_probes_sample(hp_domain_t* d)
-{
-	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
-	if (rc != HP_OK) return rc;
-	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_sample before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_sample between hp_step_begin and hp_step_end");
-	if (d->probes_samples >= d->probes_capacity)
-		return fail(HP_ERR_STATE, "hp_probes_sample: the record buffer is full (read the records, then hp_probes_reset)");
-	const ProbeLists& p = d->probes_lists;
-	const unsigned blocks = p.gauge_blocks + p.sections;
-	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
-	if (d->desc.precision == 8)
-		hipLaunchKernelGGL((record_probes<double>), dim3(blocks), dim3(256), 0, d->stream, (const State4<double>*)d->state[d->use_alt], (const double*)d->bed,
-		                   (const Scalars<double>*)d->scalars, p, d->probes_records, (unsigned long long)d->probes_samples,
-		                   (unsigned long long)d->probes_stride, d->desc.dx);
-	else
-		hipLaunchKernelGGL((record_probes<float>), dim3(blocks), dim3(256), 0, d->stream, (const State4<float>*)d->state[d->use_alt], (const float*)d->bed,
-		                   (const Scalars<float>*)d->scalars, p, d->probes_records, (unsigned long long)d->probes_samples,
-		                   (unsigned long long)d->probes_stride, d->desc.dx);
-	HIP_TRY(hipGetLastError());
-	++d->probes_samples;
-	return HP_OK;
-}
-
-int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_read before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_read between hp_step_begin and hp_step_end");
-	if (first > d->probes_samples || count > d->probes_samples - first)
-		return fail(HP_ERR_INVALID, "hp_probes_read: first + count beyond the samples taken");
-	if (count == 0) return HP_OK;
-	if (!records) return fail(HP_ERR_INVALID, "hp_probes_read: records == NULL");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	HIP_TRY(hipMemcpyAsync(records, d->probes_records + first * d->probes_stride, (size_t)(count * d->probes_stride) * sizeof(double),
-	                       hipMemcpyDeviceToHost, d->stream));
-	return HP_OK;
-}
-
-int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->probes_on) return fail(HP_ERR_STATE, "hp_probes_info before hp_probes_enable");
-	if (samples) *samples = d->probes_samples;
-	if (capacity) *capacity = d->probes_capacity;
-	if (stride) *stride = d->probes_stride;
-	return HP_OK;
-}
-
 int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_t nrows)
 {
 	int rc = check_domain(d);
@@ -2061,7 +1350,7 @@ int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_
 	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
 	still_rec_forget(d);
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
-	if (row0 < 0 || nrows < 0 || row0 + nrows > d->desc.rows) return fail(HP_ERR_INVALID, "row range out of bounds");
+	if ((rc = check_rows(d, row0, nrows)) != HP_OK) return rc;
 	const size_t per_row = (size_t)d->desc.cols * d->esize * 4;
 	// queueWritePartial goes to the CURRENT buffer only: the other one keeps what it held -- after iteration pairs it has to be
 	// brought up to date first, or the rows written now would reach it with the next single iteration's FILL
@@ -2285,7 +1574,6 @@ namespace {
 // one iteration's worth per batch); HP_STRICT_SPECULATE=1 switches it on (see spec_wanted for why it is off by default),
 // HP_STRICT_SPEC_FORCE=k pretends every k-th batch raised the word (tests).
 constexpr uint32_t SPEC_MIN = 8;
-constexpr size_t HOST_SPEC_FLAG = 464;      // byte offset in the pinned block (0..127 scalars, 256..447 handshake, 480..495 read-backs)
 bool spec_wanted(const hp_domain* d, uint32_t n)
 {
 	// OPT-IN (HP_STRICT_SPECULATE=1).  Measured with the rigorous flag (profiles/r04j_strict_lines_*): the Godunov kernel gains 2-3 %
@@ -2463,7 +1751,7 @@ int hp_step_batch(hp_domain_t* d, uint32_t n_iterations)
 static int peer_error_check(hp_domain* d)
 {
 	if (!d->peer_agreed || !d->peer_mine) return HP_OK;
-	uint64_t* peer_error = (uint64_t*)((char*)d->host_scalars + 480);
+	uint64_t* peer_error = (uint64_t*)((char*)d->host_scalars + HOST_READBACK);
 	*peer_error = 0;
 	HIP_TRY(hipMemcpyAsync(peer_error, d->peer_mine + PEER_WORD_ERROR, 8, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(hipStreamSynchronize(d->stream));
@@ -2477,7 +1765,6 @@ static int peer_error_check(hp_domain* d)
 // were left frozen from that launch on).  Read wherever the host blocks on the domain's stream anyway; once seen, every later call
 // on the domain fails with HP_ERR_STATE (check_domain) -- its state is not a state of the model.  `queued`: the read-back has been
 // queued by the caller (hp_read_scalars), only the verdict is left.
-constexpr size_t HOST_TAIL_ERR = 448;       // byte offset in the pinned block (next to HOST_SPEC_FLAG)
 static int tail_error_queue(hp_domain* d)
 {
 	*(volatile double*)((char*)d->host_scalars + HOST_TAIL_ERR) = 0.0;
@@ -2500,9 +1787,9 @@ int hp_read_scalars(hp_domain_t* d, hp_scalars_t* out)
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	if (!out) return fail(HP_ERR_INVALID, "out == NULL");
-	HIP_TRY(hipMemcpyAsync(d->host_scalars, d->scalars, 128, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipMemcpyAsync(d->host_scalars, d->scalars, HOST_SCALARS_BYTES, hipMemcpyDeviceToHost, d->stream));
 	if ((rc = tail_error_queue(d)) != HP_OK) return rc;
-	uint64_t* peer_error = (uint64_t*)((char*)d->host_scalars + 480);
+	uint64_t* peer_error = (uint64_t*)((char*)d->host_scalars + HOST_READBACK);
 	*peer_error = 0;
 	if (d->peer_agreed)                      // the mailboxes' sticky error word: a strip that was not heard from in time
 		HIP_TRY(hipMemcpyAsync(peer_error, d->peer_mine + PEER_WORD_ERROR, 8, hipMemcpyDeviceToHost, d->stream));
@@ -2707,9 +1994,9 @@ int strip_handshake(hp_domain* d)
 	double all[8];
 	char* slot = (char*)d->cfl_slot + (size_t)SLOT_HANDSHAKE * d->esize;
 	const ncclDataType_t type = d->desc.precision == 8 ? ncclDouble : ncclFloat;
-	// staged through the domain's pinned block (bytes 256..511; hp_read_scalars uses the first 128): an asynchronous copy
+	// staged through the domain's pinned block (HOST_HANDSHAKE, hp_domain.hpp): an asynchronous copy
 	// must not read from, or land in, this function's stack
-	char* pinned = (char*)d->host_scalars + 256;
+	char* pinned = (char*)d->host_scalars + HOST_HANDSHAKE;
 	HIP_TRY(hipStreamSynchronize(d->stream));                           // nothing of an earlier handshake is still in flight
 	if (d->desc.precision == 8) std::memcpy(pinned, mine, sizeof mine);
 	else { float* f = (float*)pinned; for (int i = 0; i < 8; ++i) f[i] = (float)mine[i]; }
@@ -2776,7 +2063,7 @@ int peer_round_now(hp_domain* d, double value, long timeout_ms, double* result, 
 	const PeerBox box = peer_box(d, true, timeout_ms);
 	hipLaunchKernelGGL(peer_round, dim3(1), dim3(64), 0, d->stream, box, value);
 	HIP_TRY(hipGetLastError());
-	uint64_t* pinned = (uint64_t*)((char*)d->host_scalars + 480);
+	uint64_t* pinned = (uint64_t*)((char*)d->host_scalars + HOST_READBACK);
 	HIP_TRY(hipMemcpyAsync(pinned, d->peer_mine + PEER_WORD_ERROR, 16, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(hipStreamSynchronize(d->stream));
 	*error = pinned[0];
@@ -3026,7 +2313,7 @@ int hp_strip_peer_connect(hp_domain_t* d, const void* tickets, int count, int ra
 		double verdict[2] = {error ? 1.0 : 0.0, direct ? 0.0 : 1.0};
 		if (d->comm_world > 1) {
 			char* slot = (char*)d->cfl_slot + (size_t)SLOT_HANDSHAKE * d->esize;
-			char* pinned = (char*)d->host_scalars + 256;
+			char* pinned = (char*)d->host_scalars + HOST_HANDSHAKE;
 			const ncclDataType_t type = d->desc.precision == 8 ? ncclDouble : ncclFloat;
 			if (d->desc.precision == 8) std::memcpy(pinned, verdict, 16);
 			else { const float v[2] = {(float)verdict[0], (float)verdict[1]}; std::memcpy(pinned, v, 8); }

@@ -1,0 +1,514 @@
+// hp_observers.hpp -- the three observers of a domain, host side: the output stage (hp_output.hpp), the peak tracker
+// (hp_peaks.hpp) and the probe recorder (hp_probes.hpp).  They read the state the solver leaves behind and never change it.  Here:
+// their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
+// (*_save, *_restore, *_destroy).  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, ProbeRecorder).  Included
+// once by hp_engine.hip, after hp_domain.hpp: the library stays one translation unit.
+#pragma once
+#include "hp_domain.hpp"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+static_assert(OUT_VALUES == HP_OUT_COUNT && OUT_FROUDE == HP_OUT_FROUDE && OUT_DEPTH == HP_OUT_DEPTH, "hp_output.hpp and hipims_mi.h disagree");
+static_assert(sizeof(hp_domain_stats_t) == 64, "hp_domain_stats_t layout");
+static_assert(PEAK_VALUES == HP_PEAK_COUNT && PEAK_SPEED == HP_PEAK_SPEED && PEAK_UNIT_DISCHARGE == HP_PEAK_UNIT_DISCHARGE &&
+              PEAK_HAZARD == HP_PEAK_HAZARD && PEAK_ARRIVAL_TIME == HP_PEAK_ARRIVAL_TIME && PEAK_WET_DURATION == HP_PEAK_WET_DURATION,
+              "hp_peaks.hpp and hipims_mi.h disagree");
+static_assert(sizeof(hp_peaks_desc_t) == 16, "hp_peaks_desc_t layout");
+static_assert(sizeof(hp_probes_desc_t) == 64, "hp_probes_desc_t layout");
+
+// f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
+template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }
+
+// Device (or pinned host) memory, or the call fails with `what` + the runtime's reason.  The sticky last error is cleared: the
+// launches of later steps ask for it, and this one is dealt with here.
+int alloc_or_fail(void** p, const size_t bytes, const std::string& what, const bool pinned = false)
+{
+	const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+	if (e == hipSuccess) return HP_OK;
+	*p = nullptr;
+	(void)hipGetLastError();
+	return fail(HP_ERR_HIP, what + hipGetErrorString(e));
+}
+
+// The value list of hp_domain_derive / hp_peaks_read (`limit` values exist, spelt `limit_name`): none of these checks touches the
+// device or needs the domain.  `seen`: the mask of the values listed.
+int check_value_list(const std::string& who, const int* values, int count, int limit, const char* limit_name, int element_bytes, void* const* rasters, unsigned& seen)
+{
+	if (count < 1 || count > limit) return fail(HP_ERR_INVALID, who + ": count outside 1.." + limit_name);
+	if (!values || !rasters) return fail(HP_ERR_INVALID, who + ": values / rasters == NULL");
+	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, who + ": element_bytes must be 4 or 8");
+	seen = 0;
+	for (int k = 0; k < count; ++k) {
+		if (values[k] < 0 || values[k] >= limit) return fail(HP_ERR_INVALID, who + ": unknown value " + std::to_string(values[k]));
+		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, who + ": value " + std::to_string(values[k]) + " listed twice");
+		seen |= 1u << values[k];
+		if (!rasters[k]) return fail(HP_ERR_INVALID, who + ": rasters[" + std::to_string(k) + "] == NULL");
+	}
+	return HP_OK;
+}
+
+// a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
+inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
+
+// Cap of the raster scratch.  A request that needs more is worked through in blocks of rows; the kernel of a block runs in
+// well under a hundredth of the time its rasters take to cross the host link, so blocks are queued one after the other on the
+// domain's stream and nothing would be won by overlapping them.
+constexpr size_t OUT_SCRATCH_CAP = (size_t)256 << 20;
+
+// The raster scratch of the output stage, at least `need` bytes.  The new block first: if it cannot be had, the smaller one
+// that served so far stays.
+int out_scratch_reserve(hp_domain* d, const size_t need, const std::string& who)
+{
+	if (need <= d->out.scratch_bytes) return HP_OK;
+	void* grown = nullptr;
+	int rc = alloc_or_fail(&grown, need, who + ": cannot allocate " + std::to_string(need) + " bytes of raster scratch: ");
+	if (rc != HP_OK) return rc;
+	if (d->out.scratch) {
+		hipError_t e2 = hipStreamSynchronize(d->stream);              // (an earlier call's copies may still be reading the old block)
+		if (e2 == hipSuccess) e2 = hipFree(d->out.scratch);
+		if (e2 != hipSuccess) { hipFree(grown); return fail(HP_ERR_HIP, who + ": releasing the raster scratch: " + hipGetErrorString(e2)); }
+	}
+	d->out.scratch = grown;
+	d->out.scratch_bytes = need;
+	return HP_OK;
+}
+
+// Rows [row0, row0 + nrows) of `count` rasters of `esize`-byte elements, through the raster scratch to the host: in blocks of
+// rows of at most OUT_SCRATCH_CAP bytes.  queue(first, n) queues what fills the scratch for the n cells from cell `first` on,
+// value after value (value k at byte k * n * esize); one copy per value follows it.
+template <typename Q>
+int read_back_blocked(hp_domain* d, const char* who, int count, size_t esize, void* const* rasters, int64_t row0, int64_t nrows, Q&& queue)
+{
+	const size_t cols = (size_t)d->desc.cols, row_bytes = cols * (size_t)count * esize;      // of all requested rasters together
+	const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)(OUT_SCRATCH_CAP / row_bytes)));
+	int rc = out_scratch_reserve(d, (size_t)block_rows * row_bytes, who);
+	if (rc != HP_OK) return rc;
+	for (int64_t r = 0; r < nrows; r += block_rows) {
+		const size_t n = (size_t)std::min<int64_t>(block_rows, nrows - r) * cols;
+		if ((rc = queue((size_t)(row0 + r) * cols, n)) != HP_OK) return rc;
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)r * cols * esize, (char*)d->out.scratch + (size_t)k * n * esize, n * esize,
+			                       hipMemcpyDeviceToHost, d->stream));
+	}
+	return HP_OK;
+}
+
+// ---- the output stage ----
+void out_destroy(hp_domain* d) { hipFree(d->out.scratch); hipFree(d->out.stats); if (d->out.stats_host) hipHostFree(d->out.stats_host); }
+
+// ---- the peak tracker ----
+inline size_t peaks_bytes(const hp_domain* d) { return (size_t)d->peaks.count * d->cells * sizeof(double) + sizeof(PeakBlock); }
+inline PeakBlock* peaks_block(const hp_domain* d) { return (PeakBlock*)(d->peaks.acc + (size_t)d->peaks.count * d->cells); }
+// accumulator raster of an enabled value: they lie in code order
+inline double* peaks_raster(const hp_domain* d, const int value) { return d->peaks.acc + (size_t)__builtin_popcount(d->peaks.mask & ((1u << value) - 1u)) * d->cells; }
+
+int peaks_reset_queue(hp_domain* d)
+{
+	const size_t n = (size_t)d->peaks.count * d->cells;
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((peaks_reset<T>), dim3(stream_blocks(n)), dim3(256), 0, d->stream, d->peaks.acc, n, (const Scalars<T>*)d->scalars, peaks_block(d));
+	});
+	HIP_TRY(hipGetLastError());
+	d->peaks.samples = 0;
+	return HP_OK;
+}
+
+void peaks_destroy(hp_domain* d) { hipFree(d->peaks.acc); hipFree(d->peaks.saved); }
+
+// frees the tracker (the stream is drained first: queued samples and reads still use the accumulators)
+int peaks_release(hp_domain* d)
+{
+	if (!d->peaks.on && !d->peaks.saved) return HP_OK;
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	peaks_destroy(d);
+	const uint64_t epoch = d->peaks.epoch + (d->peaks.on ? 1 : 0);
+	d->peaks = PeakTracker{};
+	d->peaks.epoch = epoch;
+	return HP_OK;
+}
+
+// hp_state_save, before it touches anything: the copy of the accumulators has to be there -- if it cannot be had the call fails
+// with the checkpoint before it, state and peaks, untouched
+int peaks_save_reserve(hp_domain* d)
+{
+	if (!d->peaks.on || d->peaks.saved) return HP_OK;
+	return alloc_or_fail(&d->peaks.saved, peaks_bytes(d), "hp_state_save: cannot allocate the copy of the peak accumulators: ");
+}
+// ... and behind the state's copies, while the tracker is on: accumulators and block in one copy
+int peaks_save(hp_domain* d)
+{
+	d->peaks.saved_valid = false;
+	if (!d->peaks.on) return HP_OK;
+	HIP_TRY(hipMemcpyAsync(d->peaks.saved, d->peaks.acc, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
+	d->peaks.saved_epoch = d->peaks.epoch;
+	d->peaks.saved_samples = d->peaks.samples;
+	d->peaks.saved_valid = true;
+	return HP_OK;
+}
+// hp_state_restore, behind the state's copies
+int peaks_restore(hp_domain* d)
+{
+	if (!d->peaks.on) return HP_OK;
+	if (d->peaks.saved_valid && d->peaks.saved_epoch == d->peaks.epoch) {
+		HIP_TRY(hipMemcpyAsync(d->peaks.acc, d->peaks.saved, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
+		d->peaks.samples = d->peaks.saved_samples;
+		return HP_OK;
+	}
+	const int rc = peaks_reset_queue(d);                                 // (the time block has come back with the state: t_previous is the restored time)
+	if (rc != HP_OK) return rc;
+	log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no peaks (the tracker was enabled after it was taken): the peaks are reset");
+	return HP_OK;
+}
+
+// ---- the probe recorder ----
+constexpr uint64_t PROBES_MAX_GAUGES = 65536, PROBES_MAX_SECTIONS = 1024;
+constexpr uint64_t PROBES_MAX_BYTES = 256ull << 20;                        // of the record buffer
+
+void probes_destroy(hp_domain* d) { hipFree(d->probes.mem); hipFree(d->probes.records); }
+
+// frees the recorder (the stream is drained first: queued samples and reads still use the lists and the records)
+int probes_release(hp_domain* d)
+{
+	if (!d->probes.on) return HP_OK;
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	probes_destroy(d);
+	const uint64_t epoch = d->probes.epoch + 1;
+	d->probes = ProbeRecorder{};
+	d->probes.epoch = epoch;
+	return HP_OK;
+}
+
+// hp_state_save: the sample count only (the records taken after it are re-recorded by the samples a restore repeats)
+void probes_save(hp_domain* d)
+{
+	d->probes.saved_valid = d->probes.on;
+	d->probes.saved_epoch = d->probes.epoch;
+	d->probes.saved_samples = d->probes.samples;
+}
+void probes_restore(hp_domain* d)
+{
+	if (!d->probes.on) return;
+	const bool mine = d->probes.saved_valid && d->probes.saved_epoch == d->probes.epoch;
+	d->probes.samples = mine ? d->probes.saved_samples : 0;
+	if (!mine) log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no probe sample count (the recorder was enabled or reset after it was taken): the count is 0");
+}
+
+} // namespace
+
+// =================================================================================================
+extern "C" {
+
+// ---- the output stage on the device (hp_output.hpp) ----
+int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
+{
+	// argument checks first: none of them touches the device, and those that do not need the domain come before it
+	unsigned seen;
+	int rc = check_value_list("hp_domain_derive", values, count, HP_OUT_COUNT, "HP_OUT_COUNT", element_bytes, rasters, seen);
+	if (rc != HP_OK) return rc;
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if ((rc = check_rows(d, row0, nrows)) != HP_OK) return rc;
+	if (nrows == 0) return HP_OK;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	return read_back_blocked(d, "hp_domain_derive", count, (size_t)element_bytes, rasters, row0, nrows, [&](const size_t first, const size_t n) -> int {
+		DeriveTargets t = {};
+		for (int k = 0; k < count; ++k) {
+			t.raster[values[k]] = (char*)d->out.scratch + (size_t)k * n * (size_t)element_bytes;
+			t.mask |= 1u << values[k];
+		}
+		const dim3 blocks((unsigned)std::min<size_t>((n + 255) / 256, 8192));
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			const State4<T>* state = (const State4<T>*)d->state[d->use_alt];      // what hp_domain_download(HP_ARRAY_STATE) reads
+			if (element_bytes == 8) hipLaunchKernelGGL((derive_rasters<T, double>), blocks, dim3(256), 0, d->stream, state, (const T*)d->bed, first, n, d->desc.dx, t);
+			else hipLaunchKernelGGL((derive_rasters<T, float>), blocks, dim3(256), 0, d->stream, state, (const T*)d->bed, first, n, d->desc.dx, t);
+		});
+		HIP_TRY(hipGetLastError());
+		return HP_OK;
+	});
+}
+
+int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats_t* out)
+{
+	if (!out) return fail(HP_ERR_INVALID, "hp_domain_stats: out == NULL");
+	if (out->struct_size != sizeof(hp_domain_stats_t)) return fail(HP_ERR_INVALID, "hp_domain_stats_t size mismatch (ABI)");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	out->reserved = 0;
+	out->cells = out->cells_wet = 0;
+	out->volume = out->max_depth = out->max_speed = 0.0;
+	out->max_depth_cell = out->max_speed_cell = UINT64_MAX;
+	if (nrows == 0) return HP_OK;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	if (!d->out.stats && (rc = alloc_or_fail(&d->out.stats, (STATS_MAX_BLOCKS + 1) * sizeof(StatsPart), "hp_domain_stats: cannot allocate the block partials: ")) != HP_OK) return rc;
+	if (!d->out.stats_host && (rc = alloc_or_fail(&d->out.stats_host, sizeof(StatsPart), "hp_domain_stats: cannot allocate pinned memory: ", true)) != HP_OK) return rc;
+	const size_t cols = (size_t)d->desc.cols, n = (size_t)nrows * cols, first = (size_t)row0 * cols;
+	// the launch shape is a function of the range alone: the same range is always summed in the same order
+	const int blocks = (int)std::min<size_t>((n + 255) / 256, STATS_MAX_BLOCKS);
+	StatsPart* partial = (StatsPart*)d->out.stats;
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((domain_stats<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed, first, n, partial);
+	});
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(domain_stats_fold, dim3(1), dim3(256), 0, d->stream, partial, blocks, partial + STATS_MAX_BLOCKS);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(d->out.stats_host, partial + STATS_MAX_BLOCKS, sizeof(StatsPart), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	const StatsPart& s = *(const StatsPart*)d->out.stats_host;
+	out->cells = s.cells; out->cells_wet = s.wet;
+	out->volume = d->desc.dx * d->desc.dx * s.sum;
+	if (s.depth_cell != ~0ull) { out->max_depth = s.max_depth; out->max_depth_cell = s.depth_cell; }
+	if (s.speed_cell != ~0ull) { out->max_speed = s.max_speed; out->max_speed_cell = s.speed_cell; }
+	return HP_OK;
+}
+
+// ---- the peak tracker (hp_peaks.hpp) ----
+int hp_peaks_enable(hp_domain_t* d, const hp_peaks_desc_t* desc)
+{
+	if (!desc) return fail(HP_ERR_INVALID, "hp_peaks_enable: desc == NULL");
+	if (desc->struct_size != sizeof(hp_peaks_desc_t)) return fail(HP_ERR_INVALID, "hp_peaks_desc_t size mismatch (ABI)");
+	if (desc->values_mask == 0) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask is empty");
+	if (desc->values_mask >> HP_PEAK_COUNT) return fail(HP_ERR_INVALID, "hp_peaks_enable: values_mask names an unknown value");
+	if (!(desc->arrival_depth >= OUT_WET)) return fail(HP_ERR_INVALID, "hp_peaks_enable: arrival_depth must be at least 1e-8");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_enable between hp_step_begin and hp_step_end");
+	if ((rc = peaks_release(d)) != HP_OK) return rc;
+	d->peaks.count = __builtin_popcount(desc->values_mask);
+	if ((rc = alloc_or_fail((void**)&d->peaks.acc, peaks_bytes(d), "hp_peaks_enable: cannot allocate the accumulators: ")) != HP_OK) { d->peaks.count = 0; return rc; }
+	d->peaks.mask = desc->values_mask;
+	d->peaks.arrival = desc->arrival_depth;
+	d->peaks.on = true;
+	++d->peaks.epoch;
+	if ((rc = peaks_reset_queue(d)) != HP_OK) { peaks_release(d); return rc; }
+	return HP_OK;
+}
+
+int hp_peaks_disable(hp_domain_t* d)
+{
+	const int rc = check_domain(d);
+	return rc != HP_OK ? rc : peaks_release(d);
+}
+
+int hp_peaks_reset(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->peaks.on) return fail(HP_ERR_STATE, "hp_peaks_reset before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_reset between hp_step_begin and hp_step_end");
+	return peaks_reset_queue(d);
+}
+
+int hp_peaks_sample(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK) return rc;
+	if (!d->peaks.on) return fail(HP_ERR_STATE, "hp_peaks_sample before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_sample between hp_step_begin and hp_step_end");
+	PeakTargets t = {};
+	for (int v = 0; v < HP_PEAK_COUNT; ++v)
+		if (d->peaks.mask & (1u << v)) t.acc[v] = peaks_raster(d, v);
+	t.mask = d->peaks.mask;
+	t.arrival_depth = d->peaks.arrival;
+	const unsigned sample = (unsigned)(d->peaks.samples & 1u);          // picks the time slot; `first`: the first sample since enable / reset
+	const int first = d->peaks.samples == 0;
+	with_real(d, [&](auto zero) { using T = decltype(zero);              // (the buffer hp_domain_download(HP_ARRAY_STATE) reads)
+		hipLaunchKernelGGL((track_peaks<T>), dim3(stream_blocks(d->cells)), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		                   (const Scalars<T>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
+	});
+	HIP_TRY(hipGetLastError());
+	++d->peaks.samples;
+	return HP_OK;
+}
+
+int hp_peaks_read(hp_domain_t* d, const int* values, int count, int element_bytes, void* const* rasters, int64_t row0, int64_t nrows)
+{
+	// argument checks first, as in hp_domain_derive: none of them touches the device
+	unsigned seen;
+	int rc = check_value_list("hp_peaks_read", values, count, HP_PEAK_COUNT, "HP_PEAK_COUNT", element_bytes, rasters, seen);
+	if (rc != HP_OK) return rc;
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->peaks.on) return fail(HP_ERR_STATE, "hp_peaks_read before hp_peaks_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_peaks_read between hp_step_begin and hp_step_end");
+	if (seen & ~d->peaks.mask) return fail(HP_ERR_INVALID, "hp_peaks_read: a value that hp_peaks_enable's values_mask does not track");
+	if ((rc = check_rows(d, row0, nrows)) != HP_OK) return rc;
+	if (nrows == 0) return HP_OK;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	if (element_bytes == 8) {                                             // whole rows are contiguous: the accumulators themselves
+		const size_t cols = (size_t)d->desc.cols;
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync(rasters[k], peaks_raster(d, values[k]) + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double),
+			                       hipMemcpyDeviceToHost, d->stream));
+		return HP_OK;
+	}
+	return read_back_blocked(d, "hp_peaks_read", count, sizeof(float), rasters, row0, nrows, [&](const size_t first, const size_t n) -> int {
+		for (int k = 0; k < count; ++k) {
+			hipLaunchKernelGGL(peaks_round, dim3(stream_blocks(n)), dim3(256), 0, d->stream, (const double*)(peaks_raster(d, values[k]) + first),
+			                   (float*)d->out.scratch + (size_t)k * n, n);
+			HIP_TRY(hipGetLastError());
+		}
+		return HP_OK;
+	});
+}
+
+int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_last)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->peaks.on) return fail(HP_ERR_STATE, "hp_peaks_info before hp_peaks_enable");
+	PeakBlock* host = (PeakBlock*)((char*)d->host_scalars + HOST_PEAKS);
+	HIP_TRY(hipMemcpyAsync(host, peaks_block(d), sizeof(PeakBlock), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	if (samples) *samples = d->peaks.samples;
+	if (t_first) *t_first = host->t_first;
+	if (t_last) *t_last = host->slot[d->peaks.samples & 1u];                 // (sample n - 1 stored its time into slot n & 1)
+	return HP_OK;
+}
+
+// ---- the probe recorder (hp_probes.hpp) ----
+int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
+{
+	// argument checks first: none of them touches the device
+	if (!desc) return fail(HP_ERR_INVALID, "hp_probes_enable: desc == NULL");
+	if (desc->struct_size != sizeof(hp_probes_desc_t)) return fail(HP_ERR_INVALID, "hp_probes_desc_t size mismatch (ABI)");
+	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: capacity must be at least 1");
+	const uint64_t G = desc->gauge_count, S = desc->section_count;
+	if (G > PROBES_MAX_GAUGES) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 65536 gauges");
+	if (S > PROBES_MAX_SECTIONS) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 1024 sections");
+	if (G + S < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: neither a gauge nor a section");
+	if (G && !desc->gauge_cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge_cells == NULL");
+	if (S && (!desc->section_offsets || !desc->section_cells || !desc->section_wx || !desc->section_wy))
+		return fail(HP_ERR_INVALID, "hp_probes_enable: a section array == NULL");
+	const uint64_t stride = 1 + PROBE_GAUGE_WORDS * G + S;
+	if ((uint64_t)desc->capacity * stride * sizeof(double) > PROBES_MAX_BYTES)
+		return fail(HP_ERR_INVALID, "hp_probes_enable: capacity x stride x 8 exceeds 256 MiB");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const uint64_t cells = d->cells;
+	for (uint64_t g = 0; g < G; ++g)
+		if (desc->gauge_cells[g] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: gauge " + std::to_string(g) + ": cell id outside the local array");
+	uint64_t M = 0;
+	if (S) {
+		if (desc->section_offsets[0] != 0) return fail(HP_ERR_INVALID, "hp_probes_enable: section_offsets[0] must be 0");
+		for (uint64_t s = 0; s < S; ++s) {
+			const uint64_t lo = desc->section_offsets[s], hi = desc->section_offsets[s + 1];
+			if (hi < lo || hi - lo < 2) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + " is shorter than 2 entries");
+			if (hi > (1ull << 32)) return fail(HP_ERR_INVALID, "hp_probes_enable: section " + std::to_string(s) + ": offsets out of range");
+		}
+		M = desc->section_offsets[S];
+		for (uint64_t e = 0; e < M; ++e) {
+			if (desc->section_cells[e] >= cells) return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": cell id outside the local array");
+			if (desc->section_wx[e] < -1 || desc->section_wx[e] > 1 || desc->section_wy[e] < -1 || desc->section_wy[e] > 1)
+				return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": weight outside {-1, 0, 1}");
+		}
+	}
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_enable between hp_step_begin and hp_step_end");
+	if ((rc = probes_release(d)) != HP_OK) return rc;
+	// one block for the lists: [gauge cells | section offsets | section cells | wx | wy], the 8-byte arrays first
+	const size_t words = (size_t)(G + (S ? S + 1 : 0) + M);
+	const size_t list_bytes = words * 8 + 2 * (size_t)M;
+	std::vector<unsigned char> host(list_bytes);
+	uint64_t* w = (uint64_t*)host.data();
+	if (G) std::memcpy(w, desc->gauge_cells, G * 8);
+	if (S) {
+		std::memcpy(w + G, desc->section_offsets, (S + 1) * 8);
+		std::memcpy(w + G + S + 1, desc->section_cells, M * 8);
+		std::memcpy(host.data() + words * 8, desc->section_wx, M);
+		std::memcpy(host.data() + words * 8 + M, desc->section_wy, M);
+	}
+	hipError_t e = hipMalloc(&d->probes.mem, list_bytes);
+	if (e == hipSuccess) e = hipMalloc((void**)&d->probes.records, (size_t)desc->capacity * stride * sizeof(double));
+	if (e == hipSuccess) e = hipMemcpyAsync(d->probes.mem, host.data(), list_bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (`host` goes away with this call)
+	if (e != hipSuccess) {
+		hipFree(d->probes.mem); hipFree(d->probes.records);
+		d->probes.mem = nullptr; d->probes.records = nullptr;
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, std::string("hp_probes_enable: cannot allocate the lists and the record buffer: ") + hipGetErrorString(e));
+	}
+	const unsigned long long* dw = (const unsigned long long*)d->probes.mem;
+	ProbeLists& p = d->probes.lists;
+	p.gauge_cells = dw;
+	p.section_offsets = dw + G;
+	p.section_cells = dw + G + (S ? S + 1 : 0);
+	p.section_wx = (const signed char*)d->probes.mem + words * 8;
+	p.section_wy = p.section_wx + M;
+	p.gauges = G;
+	p.gauge_blocks = (unsigned)((G + 255) / 256);
+	p.sections = (unsigned)S;
+	d->probes.capacity = desc->capacity;
+	d->probes.stride = stride;
+	d->probes.samples = 0;
+	d->probes.on = true;
+	++d->probes.epoch;
+	return HP_OK;
+}
+
+int hp_probes_disable(hp_domain_t* d)
+{
+	const int rc = check_domain(d);
+	return rc != HP_OK ? rc : probes_release(d);
+}
+
+int hp_probes_reset(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_reset before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_reset between hp_step_begin and hp_step_end");
+	d->probes.samples = 0;                   // (stream order: a read queued before this call has its records before a later sample overwrites them)
+	++d->probes.epoch;
+	return HP_OK;
+}
+
+int hp_probes_sample(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK) return rc;
+	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_sample before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_sample between hp_step_begin and hp_step_end");
+	if (d->probes.samples >= d->probes.capacity)
+		return fail(HP_ERR_STATE, "hp_probes_sample: the record buffer is full (read the records, then hp_probes_reset)");
+	const ProbeLists& p = d->probes.lists;
+	const unsigned blocks = p.gauge_blocks + p.sections;
+	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
+	with_real(d, [&](auto zero) {
+		using T = decltype(zero);
+		hipLaunchKernelGGL((record_probes<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		                   (const Scalars<T>*)d->scalars, p, d->probes.records, (unsigned long long)d->probes.samples,
+		                   (unsigned long long)d->probes.stride, d->desc.dx);
+	});
+	HIP_TRY(hipGetLastError());
+	++d->probes.samples;
+	return HP_OK;
+}
+
+int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_read before hp_probes_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_read between hp_step_begin and hp_step_end");
+	if (first > d->probes.samples || count > d->probes.samples - first)
+		return fail(HP_ERR_INVALID, "hp_probes_read: first + count beyond the samples taken");
+	if (count == 0) return HP_OK;
+	if (!records) return fail(HP_ERR_INVALID, "hp_probes_read: records == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(records, d->probes.records + first * d->probes.stride, (size_t)(count * d->probes.stride) * sizeof(double),
+	                       hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_info before hp_probes_enable");
+	if (samples) *samples = d->probes.samples;
+	if (capacity) *capacity = d->probes.capacity;
+	if (stride) *stride = d->probes.stride;
+	return HP_OK;
+}
+} // extern "C"

@@ -1,6 +1,6 @@
 // hp_output.hpp -- the output stage on the device: the rasters CDomainCartesian::writeOutputs derives on the host
 // (Datasets/CRasterDataset.cpp:185-267) and the domain statistics of the progress log (CDomainCartesian::getVolume,
-// CDomainCartesian.cpp:743-760), computed where the state lives.  Included by hp_engine.hip, which is built with
+// CDomainCartesian.cpp:743-760), computed where the state lives.  Part of hp_engine.hip's translation unit, which is built with
 // -ffp-contract=off -fno-fast-math: every operation below is a correctly rounded IEEE one (add, multiply, divide, square
 // root, compare), so the rasters equal the host derivation (frontend.derive_output) bit for bit.
 #pragma once
@@ -8,7 +8,7 @@
 
 namespace hp {
 
-constexpr int    OUT_VALUES = 9;                  // HP_OUT_COUNT (include/hipims_mi.h; hp_engine.hip asserts the two agree)
+constexpr int    OUT_VALUES = 9;                  // HP_OUT_COUNT (include/hipims_mi.h; hp_observers.hpp asserts the two agree)
 constexpr double OUT_NODATA = -9999.0;
 constexpr double OUT_WET    = 1e-8;               // CRasterDataset.cpp's threshold: not the scheme's dryThreshold
 

@@ -1,7 +1,7 @@
 // hp_peaks.hpp -- the peak tracker: run-long maxima (speed, unit discharge, hazard rating), time of first inundation and
 // duration of inundation, kept as fp64 accumulator rasters in device memory and folded from the current state each time the
 // host asks for a sample (hp_peaks_sample).  No reference counterpart; closest: the Zmax field the flux kernels carry,
-// CLSchemeGodunov.clc.  Included by hp_engine.hip, which is built with -ffp-contract=off -fno-fast-math: every operation
+// CLSchemeGodunov.clc.  Part of hp_engine.hip's translation unit, which is built with -ffp-contract=off -fno-fast-math: every operation
 // below is a correctly rounded IEEE one (add, multiply, divide, square root, compare), so the accumulators equal the host
 // restatement (frontend.PeakTracker) bit for bit.  The conventions are the output stage's (hp_output.hpp): NODATA, the 1e-8
 // wet test, the counted-cell rule of domain_stats.
@@ -10,7 +10,7 @@
 
 namespace hp {
 
-constexpr int PEAK_VALUES = 5;                    // HP_PEAK_COUNT (include/hipims_mi.h; hp_engine.hip asserts the two agree)
+constexpr int PEAK_VALUES = 5;                    // HP_PEAK_COUNT (include/hipims_mi.h; hp_observers.hpp asserts the two agree)
 
 enum { PEAK_SPEED, PEAK_UNIT_DISCHARGE, PEAK_HAZARD, PEAK_ARRIVAL_TIME, PEAK_WET_DURATION };
 

@@ -1,7 +1,7 @@
 // hp_probes.hpp -- the probe recorder: time series at gauge cells (stage, depth, unit discharge) and the discharge through
 // cross-sections (lists of cells with a signed weight pair each), one record of fp64 words per sample, written where the state
 // lives each time the host asks for a sample (hp_probes_sample).  No reference counterpart: HiPIMS-OCL writes rasters only.
-// Included by hp_engine.hip, which is built with -ffp-contract=off -fno-fast-math: every operation below is a correctly rounded
+// Part of hp_engine.hip's translation unit, which is built with -ffp-contract=off -fno-fast-math: every operation below is a correctly rounded
 // IEEE add, multiply or compare in fp64 and the order of every sum is fixed, so the records equal the host restatement
 // (frontend.ProbeRecorder) bit for bit.  The conventions are the output stage's (hp_output.hpp): NODATA, the 1e-8 wet test,
 // the counted-cell rule of domain_stats.
