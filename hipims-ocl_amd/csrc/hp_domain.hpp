@@ -1,11 +1,12 @@
 // hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain
 // and the map of its pinned host block.  Internal to the library's one translation unit: hp_engine.hip includes it, then
-// hp_observers.hpp (the code of the three observers whose state is declared here).
+// hp_observers.hpp (the code of the four observers whose state is declared here).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_kernels.hpp"
 #include "hp_peaks.hpp"
 #include "hp_probes.hpp"
+#include "hp_zones.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <atomic>
@@ -80,6 +81,18 @@ struct ProbeRecorder {
 	void*            mem = nullptr;                   // the lists (`lists` points into it)
 	double*          records = nullptr;               // capacity records of stride fp64 words
 	ProbeLists       lists = {};
+	uint64_t         capacity = 0, stride = 0;
+	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
+	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
+	bool             saved_valid = false;
+	uint64_t         saved_epoch = 0, saved_samples = 0;
+};
+// the zone recorder (hp_zones.hpp; hp_zones_*): nothing of it exists while recording is off
+struct ZoneRecorder {
+	bool             on = false;
+	unsigned short*  ids = nullptr;                   // the id raster of the local array, 2 bytes per cell
+	unsigned long long* records = nullptr;            // capacity records of stride 64-bit words
+	double           flood_depth = 0.0;
 	uint64_t         capacity = 0, stride = 0;
 	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
 	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
@@ -212,6 +225,7 @@ struct hp_domain {
 	OutputStage      out;
 	PeakTracker      peaks;
 	ProbeRecorder    probes;
+	ZoneRecorder     zones;
 };
 
 namespace {

@@ -1182,7 +1182,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	out_destroy(d); peaks_destroy(d); probes_destroy(d);
+	out_destroy(d); peaks_destroy(d); probes_destroy(d); zones_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1278,6 +1278,7 @@ int hp_state_save(hp_domain_t* d)
 	d->saved_valid = true;
 	if ((rc = peaks_save(d)) != HP_OK) return rc;
 	probes_save(d);
+	zones_save(d);
 	return HP_OK;
 }
 
@@ -1321,6 +1322,7 @@ int hp_state_restore(hp_domain_t* d)
 	d->fork_is_advance = false;
 	if ((rc = peaks_restore(d)) != HP_OK) return rc;
 	probes_restore(d);
+	zones_restore(d);
 	return HP_OK;
 }
 

@@ -1,7 +1,7 @@
-// hp_observers.hpp -- the three observers of a domain, host side: the output stage (hp_output.hpp), the peak tracker
-// (hp_peaks.hpp) and the probe recorder (hp_probes.hpp).  They read the state the solver leaves behind and never change it.  Here:
+// hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp), the peak tracker
+// (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
-// (*_save, *_restore, *_destroy).  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, ProbeRecorder).  Included
+// (*_save, *_restore, *_destroy).  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, ProbeRecorder, ZoneRecorder).  Included
 // once by hp_engine.hip, after hp_domain.hpp: the library stays one translation unit.
 #pragma once
 #include "hp_domain.hpp"
@@ -17,6 +17,8 @@ static_assert(PEAK_VALUES == HP_PEAK_COUNT && PEAK_SPEED == HP_PEAK_SPEED && PEA
               "hp_peaks.hpp and hipims_mi.h disagree");
 static_assert(sizeof(hp_peaks_desc_t) == 16, "hp_peaks_desc_t layout");
 static_assert(sizeof(hp_probes_desc_t) == 64, "hp_probes_desc_t layout");
+static_assert(sizeof(hp_zones_desc_t) == 32, "hp_zones_desc_t layout");
+static_assert(ZONE_WORDS == HP_ZONE_WORDS, "hp_zones.hpp and hipims_mi.h disagree");
 
 // f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
 template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }
@@ -193,6 +195,39 @@ void probes_restore(hp_domain* d)
 	const bool mine = d->probes.saved_valid && d->probes.saved_epoch == d->probes.epoch;
 	d->probes.samples = mine ? d->probes.saved_samples : 0;
 	if (!mine) log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no probe sample count (the recorder was enabled or reset after it was taken): the count is 0");
+}
+
+// ---- the zone recorder ----
+constexpr uint32_t ZONES_MAX = 4096;
+constexpr uint64_t ZONES_MAX_BYTES = 256ull << 20;                         // of the record buffer
+
+void zones_destroy(hp_domain* d) { hipFree(d->zones.ids); hipFree(d->zones.records); }
+
+// frees the recorder (the stream is drained first: queued samples and reads still use the ids and the records)
+int zones_release(hp_domain* d)
+{
+	if (!d->zones.on) return HP_OK;
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	zones_destroy(d);
+	const uint64_t epoch = d->zones.epoch + 1;
+	d->zones = ZoneRecorder{};
+	d->zones.epoch = epoch;
+	return HP_OK;
+}
+
+// hp_state_save: the sample count only, as for the probes
+void zones_save(hp_domain* d)
+{
+	d->zones.saved_valid = d->zones.on;
+	d->zones.saved_epoch = d->zones.epoch;
+	d->zones.saved_samples = d->zones.samples;
+}
+void zones_restore(hp_domain* d)
+{
+	if (!d->zones.on) return;
+	const bool mine = d->zones.saved_valid && d->zones.saved_epoch == d->zones.epoch;
+	d->zones.samples = mine ? d->zones.saved_samples : 0;
+	if (!mine) log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no zone sample count (the recorder was enabled or reset after it was taken): the count is 0");
 }
 
 } // namespace
@@ -509,6 +544,115 @@ int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64
 	if (samples) *samples = d->probes.samples;
 	if (capacity) *capacity = d->probes.capacity;
 	if (stride) *stride = d->probes.stride;
+	return HP_OK;
+}
+
+// ---- the zone recorder (hp_zones.hpp) ----
+int hp_zones_enable(hp_domain_t* d, const hp_zones_desc_t* desc)
+{
+	// argument checks first: none of them touches the device
+	if (!desc) return fail(HP_ERR_INVALID, "hp_zones_enable: desc == NULL");
+	if (desc->struct_size != sizeof(hp_zones_desc_t)) return fail(HP_ERR_INVALID, "hp_zones_desc_t size mismatch (ABI)");
+	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_zones_enable: capacity must be at least 1");
+	if (desc->zone_count < 1 || desc->zone_count > ZONES_MAX) return fail(HP_ERR_INVALID, "hp_zones_enable: zone_count outside 1..4096");
+	if (!desc->zone_of_cell) return fail(HP_ERR_INVALID, "hp_zones_enable: zone_of_cell == NULL");
+	if (!(desc->flood_depth >= OUT_WET)) return fail(HP_ERR_INVALID, "hp_zones_enable: flood_depth must be at least 1e-8");
+	const uint64_t stride = 1 + (uint64_t)ZONE_WORDS * desc->zone_count;
+	if ((uint64_t)desc->capacity * stride * sizeof(uint64_t) > ZONES_MAX_BYTES)
+		return fail(HP_ERR_INVALID, "hp_zones_enable: capacity x stride x 8 exceeds 256 MiB");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const uint64_t cells = d->cells;
+	for (uint64_t k = 0; k < cells; ++k)
+		if (desc->zone_of_cell[k] > desc->zone_count)
+			return fail(HP_ERR_INVALID, "hp_zones_enable: cell " + std::to_string(k) + ": zone id " + std::to_string(desc->zone_of_cell[k]) + " above zone_count");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_enable between hp_step_begin and hp_step_end");
+	if ((rc = zones_release(d)) != HP_OK) return rc;
+	hipError_t e = hipMalloc((void**)&d->zones.ids, (size_t)cells * sizeof(uint16_t));
+	if (e == hipSuccess) e = hipMalloc((void**)&d->zones.records, (size_t)desc->capacity * stride * sizeof(uint64_t));
+	if (e == hipSuccess) e = hipMemcpyAsync(d->zones.ids, desc->zone_of_cell, (size_t)cells * sizeof(uint16_t), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (the caller's array is free again on return)
+	if (e != hipSuccess) {
+		hipFree(d->zones.ids); hipFree(d->zones.records);
+		d->zones.ids = nullptr; d->zones.records = nullptr;
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, std::string("hp_zones_enable: cannot allocate the id raster and the record buffer: ") + hipGetErrorString(e));
+	}
+	d->zones.flood_depth = desc->flood_depth;
+	d->zones.capacity = desc->capacity;
+	d->zones.stride = stride;
+	d->zones.samples = 0;
+	d->zones.on = true;
+	++d->zones.epoch;
+	return HP_OK;
+}
+
+int hp_zones_disable(hp_domain_t* d)
+{
+	const int rc = check_domain(d);
+	return rc != HP_OK ? rc : zones_release(d);
+}
+
+int hp_zones_reset(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_reset before hp_zones_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_reset between hp_step_begin and hp_step_end");
+	d->zones.samples = 0;                    // (stream order: a read queued before this call has its records before a later sample overwrites them)
+	++d->zones.epoch;
+	return HP_OK;
+}
+
+int hp_zones_sample(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK) return rc;
+	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_sample before hp_zones_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_sample between hp_step_begin and hp_step_end");
+	if (d->zones.samples >= d->zones.capacity)
+		return fail(HP_ERR_STATE, "hp_zones_sample: the record buffer is full (read the records, then hp_zones_reset)");
+	unsigned long long* rec = d->zones.records + d->zones.samples * d->zones.stride;
+	// one fill (the sums start from 0, the maxima from the bit pattern of +0.0), one launch.  The waves split the cells into
+	// contiguous runs of a multiple of 64; the record does not depend on the shape.
+	HIP_TRY(hipMemsetAsync(rec, 0, (size_t)d->zones.stride * sizeof(uint64_t), d->stream));
+	const size_t n = d->cells;
+	const unsigned blocks = stream_blocks(n);
+	const size_t waves = (size_t)blocks * (256 / 64);
+	const size_t per_wave = ((n + waves - 1) / waves + 63) / 64 * 64;
+	with_real(d, [&](auto zero) { using T = decltype(zero);              // (the buffer hp_domain_download(HP_ARRAY_STATE) reads)
+		hipLaunchKernelGGL((record_zones<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		                   (const unsigned short*)d->zones.ids, (const Scalars<T>*)d->scalars, rec, n, per_wave, d->zones.flood_depth);
+	});
+	HIP_TRY(hipGetLastError());
+	++d->zones.samples;
+	return HP_OK;
+}
+
+int hp_zones_read(hp_domain_t* d, uint64_t first, uint64_t count, uint64_t* records)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_read before hp_zones_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_read between hp_step_begin and hp_step_end");
+	if (first > d->zones.samples || count > d->zones.samples - first)
+		return fail(HP_ERR_INVALID, "hp_zones_read: first + count beyond the samples taken");
+	if (count == 0) return HP_OK;
+	if (!records) return fail(HP_ERR_INVALID, "hp_zones_read: records == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(records, d->zones.records + first * d->zones.stride, (size_t)(count * d->zones.stride) * sizeof(uint64_t),
+	                       hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_info before hp_zones_enable");
+	if (samples) *samples = d->zones.samples;
+	if (capacity) *capacity = d->zones.capacity;
+	if (stride) *stride = d->zones.stride;
 	return HP_OK;
 }
 } // extern "C"

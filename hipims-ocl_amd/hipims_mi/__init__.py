@@ -43,6 +43,7 @@ EXPORTS = [
     "hp_domain_derive", "hp_domain_stats",
     "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
+    "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -118,6 +119,11 @@ class ProbesDesc(C.Structure):
                 ("section_wx", C.POINTER(C.c_int8)), ("section_wy", C.POINTER(C.c_int8))]
 
 
+class ZonesDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_uint32), ("zone_count", C.c_uint32), ("reserved", C.c_uint32),
+                ("zone_of_cell", C.POINTER(C.c_uint16)), ("flood_depth", C.c_double)]
+
+
 _lib = None
 
 
@@ -167,6 +173,13 @@ def load_library(path: str | None = None):
         lib.hp_probes_sample.argtypes = [C.c_void_p]
         lib.hp_probes_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
         lib.hp_probes_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_zones_enable"):                 # (absent from older builds, as above)
+        lib.hp_zones_enable.argtypes = [C.c_void_p, C.POINTER(ZonesDesc)]
+        lib.hp_zones_disable.argtypes = [C.c_void_p]
+        lib.hp_zones_reset.argtypes = [C.c_void_p]
+        lib.hp_zones_sample.argtypes = [C.c_void_p]
+        lib.hp_zones_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.hp_zones_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -226,6 +239,35 @@ def split_probe_records(records, gauges, sections):
     """[n, 1 + 4 G + S] probe records (hp_probes_read's layout) as {"t": [n], "gauges": [n, G, 4], "sections": [n, S]}."""
     rec = np.asarray(records, dtype=np.float64).reshape(-1, 1 + 4 * gauges + sections)
     return dict(t=rec[:, 0].copy(), gauges=rec[:, 1:1 + 4 * gauges].reshape(-1, gauges, 4).copy(), sections=rec[:, 1 + 4 * gauges:].copy())
+
+
+ZONE_WORDS = 7                 # HP_ZONE_WORDS: cells, wet, flooded, depth_hi, depth_lo, max_depth, max_speed
+ZONES_MAX = 4096
+
+
+def split_zone_records(records, zone_count, dx):
+    """[n, 1 + 7 Z] zone records of uint64 words (hp_zones_read's layout) as {"t": [n], "cells" | "wet" | "flooded" | "depth_hi" |
+    "depth_lo": uint64 [n, Z], "volume" | "max_depth" | "max_speed": float64 [n, Z]}.  The volume comes from the exact integer
+    S = depth_hi * 2^32 + depth_lo with one rounding (what Python's int / int gives), times dx * dx."""
+    rec = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 1 + ZONE_WORDS * zone_count)
+    z = rec[:, 1:].reshape(-1, zone_count, ZONE_WORDS)
+    out = dict(t=rec[:, 0].copy().view(np.float64))
+    for k, name in enumerate(("cells", "wet", "flooded", "depth_hi", "depth_lo")):
+        out[name] = z[:, :, k].copy()
+    # S with its limbs normalised: lo < 2^32 and hi < 2^53 are both exact in fp64, and so is hi * 2^32, which leaves the one
+    # addition as the only rounding (the correctly rounded S); dividing by 2^32 is exact.  Whole arrays at a time: a full buffer
+    # of 4096 zones is some millions of entries.
+    hi = out["depth_hi"] + (out["depth_lo"] >> np.uint64(32))
+    lo = out["depth_lo"] & np.uint64(0xffffffff)
+    if hi.size and int(hi.max()) >> 53:                 # (2^21 cells at the depth cap each, and more: Python's integers)
+        depth_sum = ((hi.astype(object) << 32) + lo.astype(object)) / 4294967296
+        depth_sum = depth_sum.astype(np.float64)
+    else:
+        depth_sum = (hi.astype(np.float64) * 4294967296.0 + lo.astype(np.float64)) / 4294967296.0
+    out["volume"] = depth_sum * (float(dx) * float(dx))
+    out["max_depth"] = z[:, :, 5].copy().view(np.float64)
+    out["max_speed"] = z[:, :, 6].copy().view(np.float64)
+    return out
 
 
 COMM_ID_BYTES = 128
@@ -316,6 +358,10 @@ class Domain:
         self._probes_drained = []                       # records read back when the device buffer was full: [k, stride] arrays
         self._probes_saved = None                       # state_save's (recorder generation, samples so far)
         self._probes_generation = 0
+        self._zones = None                              # zone_count the library records (zones_enable's)
+        self._zones_drained = []                        # as for the probes
+        self._zones_saved = None
+        self._zones_generation = 0
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -532,6 +578,82 @@ class Domain:
         rec = np.concatenate(self._probes_drained + [pending], axis=0)
         return split_probe_records(rec, *self._probes)
 
+    # ---- the zone recorder (hp_zones_*): per-zone counts, volume, largest depth and speed, one record per SAMPLE the host takes ----
+    def zones_enable(self, ids, zone_count=None, flood_depth=0.1, capacity=4096):
+        """Start recording: `ids` is the [rows, cols] raster of zone ids of the local array (row 0 = south; 0 = in no zone),
+        `zone_count` the number of zones (default: the largest id), `flood_depth` the "flooded" threshold in metres.  `capacity`
+        is the number of samples the device buffer holds; zones_sample() drains a full buffer by itself."""
+        a = np.asarray(ids)
+        if a.shape != (self.rows, self.cols):
+            raise ValueError(f"the zone raster must be [{self.rows}, {self.cols}]")
+        if a.dtype.kind not in "iu":
+            if not np.array_equal(a, np.round(a)):
+                raise ValueError("zone ids must be integers")
+        if a.size and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("zone ids must lie in 0..65535")
+        ids16 = np.ascontiguousarray(a, dtype=np.uint16)
+        count = int(zone_count) if zone_count is not None else max(1, int(ids16.max()) if ids16.size else 1)
+        if not 0 <= count < 2 ** 32:
+            raise ValueError("zone_count out of range")
+        self.zones_enable_raw(ids16, count, flood_depth, capacity)
+
+    def zones_enable_raw(self, ids16, zone_count, flood_depth=0.1, capacity=4096):
+        """zones_enable with what hp_zones_desc_t takes (a contiguous uint16 array of cols * rows ids; not checked here: the
+        library does that)."""
+        ids16 = np.ascontiguousarray(ids16, dtype=np.uint16)
+        desc = ZonesDesc(C.sizeof(ZonesDesc), int(capacity), int(zone_count), 0, ids16.ctypes.data_as(C.POINTER(C.c_uint16)), float(flood_depth))
+        rc = self.lib.hp_zones_enable(self.h, C.byref(desc))
+        if rc == -3:                                    # HP_ERR_HIP: the allocation failed and the library has switched recording off
+            self._zones, self._zones_drained = None, []
+        _check(self.lib, rc, "hp_zones_enable")
+        self._zones, self._zones_drained = int(zone_count), []
+        self._zones_generation += 1
+
+    def zones_disable(self):
+        _check(self.lib, self.lib.hp_zones_disable(self.h), "hp_zones_disable")
+        self._zones, self._zones_drained = None, []
+        self._zones_generation += 1
+
+    def zones_reset(self):
+        """Forget every sample taken so far (those read back already too)."""
+        _check(self.lib, self.lib.hp_zones_reset(self.h), "hp_zones_reset")
+        self._zones_drained = []
+        self._zones_generation += 1
+
+    def zones_info(self):
+        """dict(samples, pending, capacity, stride): samples taken since zones_enable / zones_reset, how many of them are still in
+        the device buffer, that buffer's capacity and the record length in 64-bit words; host-side counters, does not block."""
+        n, cap, stride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_zones_info(self.h, C.byref(n), C.byref(cap), C.byref(stride)), "hp_zones_info")
+        return dict(samples=sum(len(a) for a in self._zones_drained) + n.value, pending=n.value, capacity=cap.value, stride=stride.value)
+
+    def _zones_pending(self):
+        info = self.zones_info()
+        out = np.empty((info["pending"], info["stride"]), np.uint64)
+        if info["pending"]:
+            _check(self.lib, self.lib.hp_zones_read(self.h, 0, info["pending"], out.ctypes.data_as(C.POINTER(C.c_uint64))), "hp_zones_read")
+            self.sync()
+        return out, info
+
+    def zones_sample(self):
+        """One record of the current state: one fill and one launch on the domain's stream.  Does not block -- except when the
+        device buffer is full: then its records are read back first (one copy, one sync per `capacity` samples)."""
+        info = self.zones_info() if self._zones else None          # (not recording: the library's own answer below)
+        if info and info["pending"] == info["capacity"]:
+            self._zones_drained.append(self._zones_pending()[0])
+            _check(self.lib, self.lib.hp_zones_reset(self.h), "hp_zones_reset")
+        _check(self.lib, self.lib.hp_zones_sample(self.h), "hp_zones_sample")
+
+    def zone_records(self):
+        """Every record since zones_enable, in order: uint64 [n, 1 + 7 Z] (hp_zones_read's layout); blocks."""
+        pending, _ = self._zones_pending()
+        return np.concatenate(self._zones_drained + [pending], axis=0)
+
+    def zones(self):
+        """Every sample since zones_enable, in order (split_zone_records' dictionary), equal in every word to frontend.ZoneRecorder
+        fed the same samples; blocks."""
+        return split_zone_records(self.zone_records(), self._zones, self.desc.dx)
+
     def upload_rows(self, rows_state, row0):
         a = np.ascontiguousarray(rows_state, dtype=self.real)
         _check(self.lib, self.lib.hp_domain_upload_rows(self.h, a.ctypes.data_as(C.c_void_p), row0, a.shape[0]),
@@ -542,6 +664,7 @@ class Domain:
         """Device-side checkpoint of cell states + time-control block (saveCurrentState without the PCIe trip)."""
         _check(self.lib, self.lib.hp_state_save(self.h), "hp_state_save")
         self._probes_saved = (self._probes_generation, self.probes_info()["samples"]) if self._probes else None
+        self._zones_saved = (self._zones_generation, self.zones_info()["samples"]) if self._zones else None
 
     def state_restore(self):
         _check(self.lib, self.lib.hp_state_restore(self.h), "hp_state_restore")
@@ -551,6 +674,12 @@ class Domain:
             drained = np.concatenate(self._probes_drained, axis=0) if self._probes_drained else None
             keep = max(0, total - self.probes_info()["pending"])
             self._probes_drained = [drained[:keep]] if drained is not None and keep else []
+        if self._zones:
+            saved = self._zones_saved
+            total = saved[1] if saved and saved[0] == self._zones_generation else 0
+            drained = np.concatenate(self._zones_drained, axis=0) if self._zones_drained else None
+            keep = max(0, total - self.zones_info()["pending"])
+            self._zones_drained = [drained[:keep]] if drained is not None and keep else []
 
     # ---- boundaries ----
     def add_uniform(self, definition, series, interval, length):

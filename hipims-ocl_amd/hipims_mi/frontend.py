@@ -31,7 +31,7 @@ import numpy as np
 from . import (DEPTH_IGNORE, DEPTH_IS_DEPTH, DEPTH_IS_FSL, DISCHARGE_IGNORE, DISCHARGE_IS_DISCHARGE,
                DISCHARGE_IS_VELOCITY, DISCHARGE_IS_VOLUME, SCHEME_GODUNOV, SCHEME_INERTIAL, SCHEME_MUSCL_HANCOCK,
                UNIFORM_LOSS_RATE,
-               UNIFORM_RAIN_INTENSITY, hfa)
+               UNIFORM_RAIN_INTENSITY, ZONE_WORDS, ZONES_MAX, hfa, split_zone_records)
 
 NODATA = -9999.0
 
@@ -480,6 +480,121 @@ def write_probe_files(target_dir, series, gauge_names, section_names):
             for t, rec in zip(series["t"], series["sections"]):
                 for name, v in zip(section_names, rec):
                     f.write(f"{float(t)!r},{name},{float(v)!r}\n")
+
+
+# ------------------------------------------------------------------------------------------------ zones (areas)
+ZONE_DEPTH_CAP = 1048576.0                      # csrc/hp_zones.hpp: 2^20 m, so that the scaled depth is an exact integer <= 2^52
+ZONE_SCALE = 4294967296.0                       # 2^32: a depth is summed in units of 2^-32 m
+
+
+def zone_ids(values, what="the zone raster"):
+    """A raster of zone ids as uint16: every value an integer in 0..4096 (0 = in no zone), else ValueError."""
+    a = np.asarray(values)
+    if a.dtype.kind not in "iu":
+        a = a.astype(np.float64)
+        if not np.isfinite(a).all() or not np.array_equal(a, np.round(a)):
+            raise ValueError(f"{what}: zone ids must be integers")
+    if a.size and (a.min() < 0 or a.max() > ZONES_MAX):
+        raise ValueError(f"{what}: zone ids must lie in 0..{ZONES_MAX}")
+    return np.ascontiguousarray(a, dtype=np.uint16)
+
+
+class ZoneRecorder:
+    """The zone recorder in NumPy (csrc/hp_zones.hpp: record_zones): the reference the GPU tests compare against word for word, and
+    the recorder of engines without the device path.  Floating-point operations in fp64, correctly rounded ones only; what is
+    accumulated is unsigned 64-bit integers (np.add.at / np.maximum.at on uint64, never a float bincount), so the record does not
+    depend on the order of the cells.
+
+        ZoneRecorder(ids, zone_count, flood_depth, dx)   ids[rows, cols]: 0 = in no zone, 1..zone_count
+        record(state, bed, t)                            one sample: state[rows, cols, 4] = {Z, Zmax, Qx, Qy}, bed[rows, cols]
+        words()                                          uint64 [n, 1 + 7 zone_count]: hp_zones_read's layout
+        series()                                         split_zone_records' dictionary
+    """
+
+    def __init__(self, ids, zone_count=None, flood_depth=0.1, dx=1.0):
+        self.ids = zone_ids(ids)
+        self.zone_count = int(zone_count) if zone_count is not None else max(1, int(self.ids.max()) if self.ids.size else 1)
+        if not 1 <= self.zone_count <= ZONES_MAX:
+            raise ValueError(f"zone_count outside 1..{ZONES_MAX}")
+        if self.ids.size and int(self.ids.max()) > self.zone_count:
+            raise ValueError("a zone id above zone_count")
+        if not flood_depth >= 1e-8:
+            raise ValueError("flood_depth must be at least 1e-8")
+        self.flood_depth, self.dx = float(flood_depth), float(dx)
+        self.records = []
+
+    def record(self, state, bed, t):
+        z, zmax, qx, qy = (np.asarray(state)[..., k].astype(np.float64) for k in range(4))
+        zb = np.asarray(bed).astype(np.float64)
+        if z.shape != self.ids.shape:
+            raise ValueError("the state and the zone raster differ in shape")
+        with np.errstate(all="ignore"):                                       # (cells that are not counted may hold anything)
+            depth = z - zb
+            counted = (zmax > -9999.0) & (zb <= 9999.0) & (self.ids != 0)     # domain_stats' rule, inside a zone
+            d = np.where(depth > 0.0, depth, 0.0)
+            d = np.where(d > ZONE_DEPTH_CAP, ZONE_DEPTH_CAP, d)
+            q = np.rint(d * ZONE_SCALE).astype(np.uint64)                     # exact scaling, half to even
+            wet = counted & (depth > 1e-8)
+            flooded = counted & (depth > self.flood_depth)
+            div = np.where(wet, depth, 1.0)                                   # (a dry cell's quotient is never formed)
+            vx, vy = qx / div, qy / div
+            sp = np.sqrt(vx * vx + vy * vy)
+            fast = wet & (sp > 0.0)                                           # (a NaN or a zero contributes nothing)
+        words = np.zeros((self.zone_count + 1, ZONE_WORDS), np.uint64)        # row 0: scratch, dropped below
+        one = np.uint64(1)
+        np.add.at(words[:, 0], self.ids[counted], one)
+        np.add.at(words[:, 1], self.ids[wet], one)
+        np.add.at(words[:, 2], self.ids[flooded], one)
+        np.add.at(words[:, 3], self.ids[counted], q[counted] >> np.uint64(32))
+        np.add.at(words[:, 4], self.ids[counted], q[counted] & np.uint64(0xffffffff))
+        np.maximum.at(words[:, 5], self.ids[counted], np.ascontiguousarray(d[counted]).view(np.uint64))
+        np.maximum.at(words[:, 6], self.ids[fast], np.ascontiguousarray(sp[fast]).view(np.uint64))
+        rec = np.empty(1 + ZONE_WORDS * self.zone_count, np.uint64)
+        rec[0] = np.array([float(t)], np.float64).view(np.uint64)[0]
+        rec[1:] = words[1:].reshape(-1)
+        self.records.append(rec)
+
+    def words(self):
+        return np.array(self.records, np.uint64).reshape(len(self.records), 1 + ZONE_WORDS * self.zone_count)
+
+    def series(self):
+        return split_zone_records(self.words(), self.zone_count, self.dx)
+
+
+def combine_zones(parts):
+    """The zone records of the whole grid from those of its parts (uint64 [n, 1 + 7 Z] each, hp_zones_read's layout; None entries
+    are skipped), every cell counted in exactly one part: counts and depth limbs added, the two maxima taken.  Integer sums and
+    maxima: equal to the single domain's record in every word, whatever the cut."""
+    parts = [np.asarray(p, dtype=np.uint64) for p in parts if p is not None]
+    if not parts:
+        raise ValueError("no part")
+    out = parts[0].copy()
+    z = out[:, 1:].reshape(len(out), -1, ZONE_WORDS)
+    for p in parts[1:]:
+        if p.shape != out.shape:
+            raise ValueError("the parts' zone records differ in shape")
+        if not np.array_equal(p[:, 0], out[:, 0]):
+            raise RuntimeError("the parts' zone samples were taken at different model times")
+        pz = p[:, 1:].reshape(len(p), -1, ZONE_WORDS)
+        z[:, :, :5] += pz[:, :, :5]
+        z[:, :, 5:] = np.maximum(z[:, :, 5:], pz[:, :, 5:])
+    return out
+
+
+def write_zone_file(target_dir, series, dx, zone_names=None):
+    """zones.csv (time,zone,cells,wet_area,flooded_area,volume,max_depth,max_speed): one line per sample and zone, areas = counts
+    x dx^2, every number in its shortest exact decimal form (repr), so equal words give equal bytes."""
+    os.makedirs(target_dir, exist_ok=True)
+    area = float(dx) * float(dx)
+    zones = series["cells"].shape[1]
+    names = list(zone_names) if zone_names else [str(k + 1) for k in range(zones)]
+    with open(os.path.join(target_dir, "zones.csv"), "w") as f:
+        f.write("time,zone,cells,wet_area,flooded_area,volume,max_depth,max_speed\n")
+        for n, t in enumerate(series["t"]):
+            for k, name in enumerate(names):
+                f.write(",".join([repr(float(t)), name, str(int(series["cells"][n, k])), repr(float(int(series["wet"][n, k]) * area)),
+                                  repr(float(int(series["flooded"][n, k]) * area)), repr(float(series["volume"][n, k])),
+                                  repr(float(series["max_depth"][n, k])), repr(float(series["max_speed"][n, k]))]) + "\n")
 
 
 def derive_output(what, state, bed, resolution=1.0):

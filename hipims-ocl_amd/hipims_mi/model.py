@@ -22,6 +22,8 @@ import math
 import os
 import time
 
+import numpy as np
+
 from . import frontend
 
 
@@ -162,11 +164,16 @@ class SchemeDriver:
 
 
 class Model:
-    """CModel for one domain: `run()` is runModelMain."""
+    """CModel for one domain: `run()` is runModelMain.
+
+    The zone recorder's arguments: `zones` is the raster of zone ids ([rows, cols] array, row 0 = south, or a raster file;
+    default: the model file's "zones" data source), `zone_flood_depth` the "flooded" threshold in metres, `zone_capacity` the
+    number of samples the device buffer holds before it is drained to the host (as `probe_capacity` for the probes; clamped to
+    what fits the recorder's 256 MiB limit; it changes when the buffer is drained, never what is recorded)."""
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
-                 probe_capacity=4096):
+                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -245,6 +252,31 @@ class Model:
             else:
                 self.host_probes = frontend.ProbeRecorder(xy, secs, self.res)
                 self.scheme.samplers.append(self.sample_probes_on_host)
+        # The zone recorder (no reference counterpart): the raster of a <dataSource type="raster" value="zones" source="..."/> of
+        # the model file, or `zones` (an array [rows, cols], row 0 = south, or a raster file); integers 0..4096, 0 = in no zone.  One
+        # sample after every batch, zones.csv rewritten at every output time and at the end.  On the device (Domain.zones_*) wherever
+        # the output rasters are derived there -- fp32 model files included when device_outputs is forced: the recorder widens the
+        # values itself --; otherwise frontend.ZoneRecorder on the downloaded state with the front end's bed.
+        source = next((src for src in cfg.sources if "zones" in src[1]), None)
+        if zones is None and source is not None:
+            if source[0] != "raster":
+                raise ValueError("the zones data source must be a raster")
+            zones = os.path.join(cfg.source_dir, source[2])
+        self.zone_ids, self.host_zones, self.device_zones = None, None, False
+        if zones is not None:
+            values = frontend.read_raster(zones)[0] if isinstance(zones, (str, os.PathLike)) else np.asarray(zones)
+            if values.shape != (self.rows, self.cols):
+                raise ValueError(f"the zone raster is {values.shape[1]} x {values.shape[0]} cells, the domain {self.cols} x {self.rows}")
+            self.zone_ids = frontend.zone_ids(values)
+            self.zone_count = max(1, int(self.zone_ids.max()))
+            self.device_zones = self.device_outputs and hasattr(sim, "zones_enable")
+            if self.device_zones:                                  # (a record buffer of at most 256 MiB: it is drained when full)
+                fits = (256 << 20) // (8 * (1 + 7 * self.zone_count))
+                sim.zones_enable(self.zone_ids, self.zone_count, flood_depth=zone_flood_depth, capacity=max(1, min(int(zone_capacity), fits)))
+                self.scheme.samplers.append(sim.zones_sample)
+            else:
+                self.host_zones = frontend.ZoneRecorder(self.zone_ids, self.zone_count, zone_flood_depth, self.res)
+                self.scheme.samplers.append(self.sample_zones_on_host)
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
 
@@ -266,6 +298,20 @@ class Model:
         if (self.host_probes is not None or self.device_probes) and self.cfg.target_dir and self.output_format:
             frontend.write_probe_files(self.cfg.target_dir, self.probes(), [n for n, _, _ in self.gauge_list],
                                        [n for n, _ in self.section_list])
+
+    def sample_zones_on_host(self):
+        s = self.scheme._call("read_scalars", "scalars")()
+        self.host_zones.record(self.sim.download(), self.bed, s["time"] if "time" in s else s["t"])
+
+    def zones(self):
+        """The zone series so far (split_zone_records' dictionary): one entry per batch (None without a zone raster)."""
+        if self.host_zones is not None:
+            return self.host_zones.series()
+        return self.sim.zones() if self.device_zones else None
+
+    def write_zones(self):
+        if (self.host_zones is not None or self.device_zones) and self.cfg.target_dir and self.output_format:
+            frontend.write_zone_file(self.cfg.target_dir, self.zones(), self.res)
 
     def peaks(self):
         """{name: array} of the tracked peak values so far."""
@@ -313,6 +359,7 @@ class Model:
         for name, arr in peaks.items():                            # (asked for through Model(peaks=...) only: no file)
             out.setdefault(name, arr)
         self.write_probes()
+        self.write_zones()
         self.outputs.append((self.current_time, out))
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()
@@ -388,6 +435,7 @@ class Model:
         if self.scheme.is_sync_ready(self.target_time):
             self.write_outputs()
         self.write_probes()
+        self.write_zones()
         self.seconds = self.clock() - t0
         self.log_progress(self.seconds)
         return self.outputs

@@ -209,6 +209,28 @@ class HipEngine:
     def probes_info(self):
         return self.domain.probes_info()
 
+    # the zone recorder (Domain.zones_*)
+    def zones_enable(self, ids, zone_count=None, flood_depth=0.1, capacity=4096):
+        self.domain.zones_enable(ids, zone_count, flood_depth=flood_depth, capacity=capacity)
+
+    def zones_disable(self):
+        self.domain.zones_disable()
+
+    def zones_reset(self):
+        self.domain.zones_reset()
+
+    def zones_sample(self):
+        self.domain.zones_sample()
+
+    def zone_records(self):
+        return self.domain.zone_records()
+
+    def zones(self):
+        return self.domain.zones()
+
+    def zones_info(self):
+        return self.domain.zones_info()
+
     def set_target_time(self, t):
         self.domain.set_target_time(t)
 
@@ -572,6 +594,49 @@ class StripRunner:
             parts = [None] * self.world if self.rank == 0 else None
             self.dist.gather_object(mine, parts, dst=0)
         return assemble_probes(parts, self._probe_gauges, self._probe_sections, self._probe_dx) if self.rank == 0 else None
+
+    # ---- the zone recorder: every rank records its local rows with the ghost rows' ids set to 0, so that every cell is counted on
+    #      exactly one rank; the records are integers, so rank 0's sums and maxima (frontend.combine_zones) are the single domain's ----
+    def zones_enable(self, ids_global, zone_count=None, flood_depth=0.1, capacity=4096, dx=None):
+        """`ids_global`: the [rows, cols] raster of zone ids of the WHOLE grid (row 0 = south; 0 = in no zone).  `dx`: the cell size
+        of the volumes (default: the HIP domain's; 1 with another engine)."""
+        from . import frontend
+        ids = frontend.zone_ids(ids_global)
+        if ids.shape != (self.rows, self.cols):
+            raise ValueError(f"the zone raster must be [{self.rows}, {self.cols}]")
+        self._zone_count = int(zone_count) if zone_count is not None else max(1, int(ids.max()))
+        self._zone_dx = float(dx if dx is not None else (self.domain.desc.dx if self.domain is not None else 1.0))
+        local = ids[self.local_slice()].copy()
+        local[:self.own_lo - self.local_lo] = 0         # the ghost rows belong to the neighbours
+        local[self.own_hi - self.local_lo:] = 0
+        self._zone_host, self._zones_on = None, True
+        if hasattr(self.engine, "zones_enable"):
+            self.engine.zones_enable(local, self._zone_count, flood_depth=flood_depth, capacity=capacity)
+        else:                                           # an engine without the device path: the host recorder on the downloaded strip
+            self._zone_host = frontend.ZoneRecorder(local, self._zone_count, flood_depth, self._zone_dx)
+
+    def _zones_required(self, what):
+        if not getattr(self, "_zones_on", False):
+            raise RuntimeError(f"{what}: the zone recorder is not enabled (StripRunner.zones_enable comes first)")
+
+    def zones_sample(self):
+        self._zones_required("zones_sample")
+        if self._zone_host is None:
+            self.engine.zones_sample()
+        else:
+            self._zone_host.record(self.engine.download(), self._bed_local, self.engine.scalars()["t"])
+
+    def gather_zones(self):
+        """The series of the whole grid: rank 0 gets Domain.zones()' dictionary, equal to the single domain's in every word; the
+        other ranks None.  Pickled objects over the process group; collective."""
+        from . import frontend, split_zone_records
+        self._zones_required("gather_zones")
+        mine = self.engine.zone_records() if self._zone_host is None else self._zone_host.words()
+        parts = [mine]
+        if self.world > 1:
+            parts = [None] * self.world if self.rank == 0 else None
+            self.dist.gather_object(mine, parts, dst=0)
+        return split_zone_records(frontend.combine_zones(parts), self._zone_count, self._zone_dx) if self.rank == 0 else None
 
     def gather_stats(self):
         """Domain.stats over the whole grid, on every rank (combine_stats); cell ids are global.  Collective."""

@@ -303,6 +303,66 @@ int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* recor
  * of the three pointers may be NULL.  HP_ERR_STATE before hp_probes_enable. */
 int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride);
 
+/* ---- the zone recorder: per-zone cell counts, volume of water, largest depth and speed as a time series (a zone = the cells that
+ *      carry one id in a 2-byte raster: a sub-catchment, a ward, a reservoir; no reference counterpart: HiPIMS-OCL writes rasters
+ *      only).  Rasters, peaks, points and lines have their observers above; this one answers for AREAS, and with one zone over the
+ *      whole grid it is a mass-balance series that does not block, which hp_domain_stats cannot give.
+ *      Opt-in.  One fill and one kernel launch per sample (csrc/hp_zones.hpp: record_zones) write one RECORD of
+ *      stride = 1 + 7 * zone_count 64-bit words into a buffer of `capacity` records in device memory:
+ *          [t | zone 1: cells, cells_wet, cells_flooded, depth_hi, depth_lo, max_depth, max_speed | zone 2: ... ]
+ *      Word 0 is the bit pattern of the device's own "Time" scalar as fp64.  A sample reads the buffer
+ *      hp_domain_download(HP_ARRAY_STATE) reads, the bed and that scalar, in stream order behind whatever is queued, without any
+ *      host synchronisation, and changes nothing the steps depend on: a recorded run's state, scalars, launch counts and pair
+ *      statistics are the unrecorded run's, bit for bit.  With the recorder off nothing is allocated or launched.  A sample can
+ *      only be taken between batches (the peak tracker's rule).
+ *      Conventions of the output stage: values widened to fp64 first whatever the domain's precision, correctly rounded
+ *      operations only (add, multiply, divide, square root, round to integer, compare).  A cell is counted exactly as in
+ *      hp_domain_stats (Zmax > -9999 and bed <= 9999).  depth = Z - bed; d = depth > 0 ? depth : 0, then at most 1048576.0.
+ *      Per zone, over the counted cells that carry its id:
+ *        0 cells          counted cells
+ *        1 cells_wet      depth > 1e-8
+ *        2 cells_flooded  depth > flood_depth
+ *        3 depth_hi       sum of (q >> 32), q = (uint64) rint(d * 4294967296.0): round half to even; the scaling is exact, q <= 2^52
+ *        4 depth_lo       sum of (q & 0xffffffff).  The exact sum is S = depth_hi * 2^32 + depth_lo; the zone's volume is
+ *                         dx^2 * S / 2^32: the quantum is 2^-32 m and the error at most 2^-33 m per cell
+ *        5 max_depth      bit pattern of the largest d (non-negative doubles order like their bit patterns); 0 without a counted cell
+ *        6 max_speed      bit pattern of the largest sp = sqrt((Qx / depth)^2 + (Qy / depth)^2) over the wet cells with sp > 0 (a NaN
+ *                         or a zero speed contributes nothing); 0 if no cell qualifies
+ *      ALL SEVEN ARE SUMS OR MAXIMA OF INTEGERS: the record is a pure function of the state and the id raster -- independent of
+ *      the launch shape, of the order in which the atomics arrive and of how the grid is cut into strips.  The records of an
+ *      N-strip run (ghost rows carrying id 0), words added and maxima taken, are the single domain's in every bit;
+ *      frontend.ZoneRecorder restates the record in NumPy and frontend.combine_zones the combination.  Cells with id 0 contribute
+ *      nothing; a zone that no cell carries stays all-zero. ---- */
+enum { HP_ZONE_WORDS = 7 };
+typedef struct {
+	uint32_t struct_size;              /* = sizeof(hp_zones_desc_t) */
+	uint32_t capacity;                 /* records the device buffer holds; >= 1; capacity * stride * 8 <= 256 MiB */
+	uint32_t zone_count;               /* 1 .. 4096 */
+	uint32_t reserved;
+	const uint16_t* zone_of_cell;      /* cols * rows ids of the LOCAL array, row 0 = south; 0 = in no zone, 1..zone_count */
+	double   flood_depth;              /* metres, >= 1e-8: the "flooded" threshold.  Typical: 0.1 */
+} hp_zones_desc_t;
+/* Copies the id raster to the device (2 bytes per cell there too; the caller's array is free again on return) and allocates the
+ * record buffer; sample count 0.  On a domain that is already recording, the old recorder is freed first.  Argument errors -- a
+ * bad struct_size, a NULL pointer, zone_count outside 1..4096, flood_depth below 1e-8, a record buffer over 256 MiB, an id above
+ * zone_count (the message names the first such cell) -- are HP_ERR_INVALID before any device call.  If an allocation fails the
+ * call returns HP_ERR_HIP and the domain stays usable with the recorder off. */
+int hp_zones_enable(hp_domain_t* d, const hp_zones_desc_t* desc);
+int hp_zones_disable(hp_domain_t* d);                  /* frees; idempotent (also done by hp_domain_destroy) */
+/* Sample count 0; the buffer is not cleared.  Reads queued before the call still deliver the old records (stream order). */
+int hp_zones_reset(hp_domain_t* d);
+/* One sample: enqueued on the domain's stream, never blocks.  HP_ERR_STATE before hp_zones_enable, between hp_step_begin and
+ * hp_step_end, and when samples == capacity: nothing is enqueued then and the count is unchanged -- the host reads the records
+ * and calls hp_zones_reset. */
+int hp_zones_sample(hp_domain_t* d);
+/* Records [first, first + count) into records[count * stride]: a device-to-host copy enqueued behind the queued samples; the host
+ * memory must stay alive until hp_sync().  first + count beyond the samples taken is HP_ERR_INVALID; a read before
+ * hp_zones_enable or inside a split step is HP_ERR_STATE; count == 0 is HP_OK. */
+int hp_zones_read(hp_domain_t* d, uint64_t first, uint64_t count, uint64_t* records);
+/* Samples taken since enable / reset, the capacity and the record stride in 64-bit words.  Host-side counters: does not block.
+ * Any of the three pointers may be NULL.  HP_ERR_STATE before hp_zones_enable. */
+int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride);
+
 /* Device-side checkpoint: what saveCurrentState + rollbackSimulation do through host memory (CSchemeGodunov.cpp:1720-1736,
  * :1474-1518), kept in HBM instead (two more copies of a 4096^2 fp64 state are 1 GB of 288).  hp_state_save copies BOTH
  * ping-pong buffers and the time-control block; hp_state_restore puts each buffer, the time-control block, the ping-pong phase
@@ -316,7 +376,8 @@ int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64
  * disabled or re-enabled holds no peaks: hp_state_restore then resets them and sends one HP_LOG_WARNING to the log sink.
  * While the probe recorder is on, hp_state_save remembers its sample count and hp_state_restore puts it back: the records taken
  * since then are re-recorded by the samples that are repeated.  If the recorder was enabled, disabled, re-enabled or reset since
- * the snapshot, hp_state_restore sets the count to 0 and sends one HP_LOG_WARNING to the log sink. */
+ * the snapshot, hp_state_restore sets the count to 0 and sends one HP_LOG_WARNING to the log sink.  The zone recorder's sample
+ * count follows the same rule, with a warning of its own. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
