@@ -1,6 +1,6 @@
 // hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain
 // and the map of its pinned host block.  Internal to the library's one translation unit: hp_engine.hip includes it, then
-// hp_observers.hpp (the code of the four observers whose state is declared here).
+// hp_observers.hpp (the code of the four observers whose state is declared here, and of the RecordLog two of them share).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_kernels.hpp"
@@ -75,29 +75,27 @@ struct PeakTracker {
 	bool             saved_valid = false;
 	uint64_t         saved_epoch = 0, saved_samples = 0;
 };
-// the probe recorder (hp_probes.hpp; hp_probes_*): nothing of it exists while recording is off
-struct ProbeRecorder {
+// What the probe and the zone recorder share: a log of `capacity` records of `stride` 8-byte words each in device memory, one
+// record per sample, and its lifecycle (hp_observers.hpp: log_*).  Nothing of it exists while recording is off.
+struct RecordLog {
 	bool             on = false;
-	void*            mem = nullptr;                   // the lists (`lists` points into it)
-	double*          records = nullptr;               // capacity records of stride fp64 words
-	ProbeLists       lists = {};
+	void*            input = nullptr;                 // what the recorder's kernel reads besides the state: allocated and freed with the records
+	unsigned long long* records = nullptr;            // capacity records of stride 64-bit words (the probes': fp64)
 	uint64_t         capacity = 0, stride = 0;
 	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
 	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
 	bool             saved_valid = false;
 	uint64_t         saved_epoch = 0, saved_samples = 0;
 };
-// the zone recorder (hp_zones.hpp; hp_zones_*): nothing of it exists while recording is off
+// the probe recorder (hp_probes.hpp; hp_probes_*): log.input holds the lists (`lists` points into it)
+struct ProbeRecorder {
+	RecordLog        log;
+	ProbeLists       lists = {};
+};
+// the zone recorder (hp_zones.hpp; hp_zones_*): log.input is the id raster of the local array, 2 bytes per cell
 struct ZoneRecorder {
-	bool             on = false;
-	unsigned short*  ids = nullptr;                   // the id raster of the local array, 2 bytes per cell
-	unsigned long long* records = nullptr;            // capacity records of stride 64-bit words
+	RecordLog        log;
 	double           flood_depth = 0.0;
-	uint64_t         capacity = 0, stride = 0;
-	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
-	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
-	bool             saved_valid = false;
-	uint64_t         saved_epoch = 0, saved_samples = 0;
 };
 
 } // namespace

@@ -1182,7 +1182,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	out_destroy(d); peaks_destroy(d); probes_destroy(d); zones_destroy(d);
+	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1277,8 +1277,8 @@ int hp_state_save(hp_domain_t* d)
 	d->saved_ghost_valid = d->ghost_valid;
 	d->saved_valid = true;
 	if ((rc = peaks_save(d)) != HP_OK) return rc;
-	probes_save(d);
-	zones_save(d);
+	log_save(d, PROBES);
+	log_save(d, ZONES);
 	return HP_OK;
 }
 
@@ -1321,8 +1321,8 @@ int hp_state_restore(hp_domain_t* d)
 	d->edge_dirty = d->edge_dirty || d->saved_edge_dirty;
 	d->fork_is_advance = false;
 	if ((rc = peaks_restore(d)) != HP_OK) return rc;
-	probes_restore(d);
-	zones_restore(d);
+	log_restore(d, PROBES);
+	log_restore(d, ZONES);
 	return HP_OK;
 }
 

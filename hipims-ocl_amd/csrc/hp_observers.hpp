@@ -1,7 +1,8 @@
 // hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp), the peak tracker
 // (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
-// (*_save, *_restore, *_destroy).  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, ProbeRecorder, ZoneRecorder).  Included
+// (*_save, *_restore, *_destroy).  The two recorders share one record log (log_*): their own entry points keep the argument
+// checks, what they upload and the launch.  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, RecordLog, ProbeRecorder, ZoneRecorder).  Included
 // once by hp_engine.hip, after hp_domain.hpp: the library stays one translation unit.
 #pragma once
 #include "hp_domain.hpp"
@@ -164,70 +165,148 @@ int peaks_restore(hp_domain* d)
 	return HP_OK;
 }
 
-// ---- the probe recorder ----
+// ---- the record log (RecordLog, hp_domain.hpp): everything the probe and the zone recorder do alike.  The calls name the
+//      recorder (not its log: their first check may be the null domain) by its public prefix, from which the messages are built
+//      when a call fails, and the noun of hp_state_restore's warning ----
+struct Recorder { const char* prefix; const char* noun; RecordLog& (*log)(hp_domain*); };
+const Recorder PROBES = {"hp_probes", "probe", [](hp_domain* d) -> RecordLog& { return d->probes.log; }};
+const Recorder ZONES = {"hp_zones", "zone", [](hp_domain* d) -> RecordLog& { return d->zones.log; }};
 constexpr uint64_t PROBES_MAX_GAUGES = 65536, PROBES_MAX_SECTIONS = 1024;
-constexpr uint64_t PROBES_MAX_BYTES = 256ull << 20;                        // of the record buffer
+constexpr uint32_t ZONES_MAX = 4096;
+constexpr uint64_t LOG_MAX_BYTES = 256ull << 20;                           // of a record buffer
 
-void probes_destroy(hp_domain* d) { hipFree(d->probes.mem); hipFree(d->probes.records); }
+void log_destroy(hp_domain* d, const Recorder& r) { hipFree(r.log(d).input); hipFree(r.log(d).records); }
 
-// frees the recorder (the stream is drained first: queued samples and reads still use the lists and the records)
-int probes_release(hp_domain* d)
+// frees the recorder (the stream is drained first: queued samples and reads still use its input block and the records).  What
+// the recorder keeps next to the log is only read while the log is on.
+int log_release(hp_domain* d, const Recorder& r)
 {
-	if (!d->probes.on) return HP_OK;
+	RecordLog& g = r.log(d);
+	if (!g.on) return HP_OK;
 	HIP_TRY(hipStreamSynchronize(d->stream));
-	probes_destroy(d);
-	const uint64_t epoch = d->probes.epoch + 1;
-	d->probes = ProbeRecorder{};
-	d->probes.epoch = epoch;
+	log_destroy(d, r);
+	const uint64_t epoch = g.epoch + 1;
+	g = RecordLog{};
+	g.epoch = epoch;
 	return HP_OK;
 }
 
 // hp_state_save: the sample count only (the records taken after it are re-recorded by the samples a restore repeats)
-void probes_save(hp_domain* d)
+void log_save(hp_domain* d, const Recorder& r)
 {
-	d->probes.saved_valid = d->probes.on;
-	d->probes.saved_epoch = d->probes.epoch;
-	d->probes.saved_samples = d->probes.samples;
+	RecordLog& g = r.log(d);
+	g.saved_valid = g.on;
+	g.saved_epoch = g.epoch;
+	g.saved_samples = g.samples;
 }
-void probes_restore(hp_domain* d)
+void log_restore(hp_domain* d, const Recorder& r)
 {
-	if (!d->probes.on) return;
-	const bool mine = d->probes.saved_valid && d->probes.saved_epoch == d->probes.epoch;
-	d->probes.samples = mine ? d->probes.saved_samples : 0;
-	if (!mine) log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no probe sample count (the recorder was enabled or reset after it was taken): the count is 0");
+	RecordLog& g = r.log(d);
+	if (!g.on) return;
+	const bool mine = g.saved_valid && g.saved_epoch == g.epoch;
+	g.samples = mine ? g.saved_samples : 0;
+	if (!mine) log_line(HP_LOG_WARNING, std::string("hp_state_restore: the saved state holds no ") + r.noun + " sample count (the recorder was enabled or reset after it was taken): the count is 0");
 }
 
-// ---- the zone recorder ----
-constexpr uint32_t ZONES_MAX = 4096;
-constexpr uint64_t ZONES_MAX_BYTES = 256ull << 20;                         // of the record buffer
-
-void zones_destroy(hp_domain* d) { hipFree(d->zones.ids); hipFree(d->zones.records); }
-
-// frees the recorder (the stream is drained first: queued samples and reads still use the ids and the records)
-int zones_release(hp_domain* d)
+// <prefix><call> on a recorder that is off, or inside a split step
+int log_check_state(hp_domain* d, const Recorder& r, const char* call)
 {
-	if (!d->zones.on) return HP_OK;
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	zones_destroy(d);
-	const uint64_t epoch = d->zones.epoch + 1;
-	d->zones = ZoneRecorder{};
-	d->zones.epoch = epoch;
+	if (!r.log(d).on) return fail(HP_ERR_STATE, std::string(r.prefix) + call + " before " + r.prefix + "_enable");
+	if (d->in_step) return fail(HP_ERR_STATE, std::string(r.prefix) + call + " between hp_step_begin and hp_step_end");
 	return HP_OK;
 }
 
-// hp_state_save: the sample count only, as for the probes
-void zones_save(hp_domain* d)
+// <prefix>_enable, first: the descriptor checks every recorder starts with ...
+template <typename D> int log_check_desc(const Recorder& r, const D* desc)
 {
-	d->zones.saved_valid = d->zones.on;
-	d->zones.saved_epoch = d->zones.epoch;
-	d->zones.saved_samples = d->zones.samples;
+	if (!desc) return fail(HP_ERR_INVALID, std::string(r.prefix) + "_enable: desc == NULL");
+	if (desc->struct_size != sizeof(D)) return fail(HP_ERR_INVALID, std::string(r.prefix) + "_desc_t size mismatch (ABI)");
+	if (desc->capacity < 1) return fail(HP_ERR_INVALID, std::string(r.prefix) + "_enable: capacity must be at least 1");
+	return HP_OK;
 }
-void zones_restore(hp_domain* d)
+// ... behind the recorder's own argument checks, and in front of those that need the domain: the size of the record buffer ...
+int log_check_bytes(const Recorder& r, const uint64_t capacity, const uint64_t stride)
 {
-	if (!d->zones.on) return;
-	const bool mine = d->zones.saved_valid && d->zones.saved_epoch == d->zones.epoch;
-	d->zones.samples = mine ? d->zones.saved_samples : 0;
-	if (!mine) log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no zone sample count (the recorder was enabled or reset after it was taken): the count is 0");
+	if (capacity * stride * 8 > LOG_MAX_BYTES) return fail(HP_ERR_INVALID, std::string(r.prefix) + "_enable: capacity x stride x 8 exceeds 256 MiB");
+	return HP_OK;
+}
+// ... and last: the old recorder goes, the input block (`input_bytes` from `host`; `what` names it) and the record buffer come.
+// Returns when the upload has landed: `host` is free again.
+int log_open(hp_domain* d, const Recorder& r, const char* what, const void* host, const size_t input_bytes, const uint64_t capacity, const uint64_t stride)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, std::string(r.prefix) + "_enable between hp_step_begin and hp_step_end");
+	if ((rc = log_release(d, r)) != HP_OK) return rc;
+	RecordLog& g = r.log(d);
+	hipError_t e = hipMalloc(&g.input, input_bytes);
+	if (e == hipSuccess) e = hipMalloc((void**)&g.records, (size_t)(capacity * stride * 8));
+	if (e == hipSuccess) e = hipMemcpyAsync(g.input, host, input_bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+	if (e != hipSuccess) {
+		log_destroy(d, r);
+		g.input = nullptr; g.records = nullptr;
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, std::string(r.prefix) + "_enable: cannot allocate " + what + " and the record buffer: " + hipGetErrorString(e));
+	}
+	g.capacity = capacity;
+	g.stride = stride;
+	g.samples = 0;
+	g.on = true;
+	++g.epoch;
+	return HP_OK;
+}
+
+int log_disable(hp_domain* d, const Recorder& r)
+{
+	const int rc = check_domain(d);
+	return rc != HP_OK ? rc : log_release(d, r);
+}
+
+int log_reset(hp_domain* d, const Recorder& r)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK || (rc = log_check_state(d, r, "_reset")) != HP_OK) return rc;
+	r.log(d).samples = 0;                    // (stream order: a read queued before this call has its records before a later sample overwrites them)
+	++r.log(d).epoch;
+	return HP_OK;
+}
+
+// <prefix>_sample, in front of the launch; ++samples follows it
+int log_sample_check(hp_domain* d, const Recorder& r)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	if (rc != HP_OK || (rc = log_check_state(d, r, "_sample")) != HP_OK) return rc;
+	if (r.log(d).samples >= r.log(d).capacity)
+		return fail(HP_ERR_STATE, std::string(r.prefix) + "_sample: the record buffer is full (read the records, then " + r.prefix + "_reset)");
+	return HP_OK;
+}
+
+// queues the copy of records [first, first + count)
+int log_read(hp_domain* d, const Recorder& r, const uint64_t first, const uint64_t count, void* records)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	int rc = log_check_state(d, r, "_read");
+	if (rc != HP_OK) return rc;
+	const RecordLog& g = r.log(d);
+	if (first > g.samples || count > g.samples - first)
+		return fail(HP_ERR_INVALID, std::string(r.prefix) + "_read: first + count beyond the samples taken");
+	if (count == 0) return HP_OK;
+	if (!records) return fail(HP_ERR_INVALID, std::string(r.prefix) + "_read: records == NULL");
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	HIP_TRY(hipMemcpyAsync(records, g.records + first * g.stride, (size_t)(count * g.stride) * 8, hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+// host-side counters only
+int log_info(hp_domain* d, const Recorder& r, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!r.log(d).on) return fail(HP_ERR_STATE, std::string(r.prefix) + "_info before " + r.prefix + "_enable");
+	if (samples) *samples = r.log(d).samples;
+	if (capacity) *capacity = r.log(d).capacity;
+	if (stride) *stride = r.log(d).stride;
+	return HP_OK;
 }
 
 } // namespace
@@ -406,9 +485,8 @@ int hp_peaks_info(hp_domain_t* d, uint64_t* samples, double* t_first, double* t_
 int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
 {
 	// argument checks first: none of them touches the device
-	if (!desc) return fail(HP_ERR_INVALID, "hp_probes_enable: desc == NULL");
-	if (desc->struct_size != sizeof(hp_probes_desc_t)) return fail(HP_ERR_INVALID, "hp_probes_desc_t size mismatch (ABI)");
-	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_probes_enable: capacity must be at least 1");
+	int rc = log_check_desc(PROBES, desc);
+	if (rc != HP_OK) return rc;
 	const uint64_t G = desc->gauge_count, S = desc->section_count;
 	if (G > PROBES_MAX_GAUGES) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 65536 gauges");
 	if (S > PROBES_MAX_SECTIONS) return fail(HP_ERR_INVALID, "hp_probes_enable: more than 1024 sections");
@@ -417,8 +495,7 @@ int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
 	if (S && (!desc->section_offsets || !desc->section_cells || !desc->section_wx || !desc->section_wy))
 		return fail(HP_ERR_INVALID, "hp_probes_enable: a section array == NULL");
 	const uint64_t stride = 1 + PROBE_GAUGE_WORDS * G + S;
-	if ((uint64_t)desc->capacity * stride * sizeof(double) > PROBES_MAX_BYTES)
-		return fail(HP_ERR_INVALID, "hp_probes_enable: capacity x stride x 8 exceeds 256 MiB");
+	if ((rc = log_check_bytes(PROBES, desc->capacity, stride)) != HP_OK) return rc;
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	const uint64_t cells = d->cells;
 	for (uint64_t g = 0; g < G; ++g)
@@ -438,10 +515,6 @@ int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
 				return fail(HP_ERR_INVALID, "hp_probes_enable: section entry " + std::to_string(e) + ": weight outside {-1, 0, 1}");
 		}
 	}
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_enable between hp_step_begin and hp_step_end");
-	if ((rc = probes_release(d)) != HP_OK) return rc;
 	// one block for the lists: [gauge cells | section offsets | section cells | wx | wy], the 8-byte arrays first
 	const size_t words = (size_t)(G + (S ? S + 1 : 0) + M);
 	const size_t list_bytes = words * 8 + 2 * (size_t)M;
@@ -454,205 +527,90 @@ int hp_probes_enable(hp_domain_t* d, const hp_probes_desc_t* desc)
 		std::memcpy(host.data() + words * 8, desc->section_wx, M);
 		std::memcpy(host.data() + words * 8 + M, desc->section_wy, M);
 	}
-	hipError_t e = hipMalloc(&d->probes.mem, list_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&d->probes.records, (size_t)desc->capacity * stride * sizeof(double));
-	if (e == hipSuccess) e = hipMemcpyAsync(d->probes.mem, host.data(), list_bytes, hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (`host` goes away with this call)
-	if (e != hipSuccess) {
-		hipFree(d->probes.mem); hipFree(d->probes.records);
-		d->probes.mem = nullptr; d->probes.records = nullptr;
-		(void)hipGetLastError();
-		return fail(HP_ERR_HIP, std::string("hp_probes_enable: cannot allocate the lists and the record buffer: ") + hipGetErrorString(e));
-	}
-	const unsigned long long* dw = (const unsigned long long*)d->probes.mem;
+	if ((rc = log_open(d, PROBES, "the lists", host.data(), list_bytes, desc->capacity, stride)) != HP_OK) return rc;
+	const unsigned long long* dw = (const unsigned long long*)d->probes.log.input;
 	ProbeLists& p = d->probes.lists;
 	p.gauge_cells = dw;
 	p.section_offsets = dw + G;
 	p.section_cells = dw + G + (S ? S + 1 : 0);
-	p.section_wx = (const signed char*)d->probes.mem + words * 8;
+	p.section_wx = (const signed char*)d->probes.log.input + words * 8;
 	p.section_wy = p.section_wx + M;
 	p.gauges = G;
 	p.gauge_blocks = (unsigned)((G + 255) / 256);
 	p.sections = (unsigned)S;
-	d->probes.capacity = desc->capacity;
-	d->probes.stride = stride;
-	d->probes.samples = 0;
-	d->probes.on = true;
-	++d->probes.epoch;
 	return HP_OK;
 }
 
-int hp_probes_disable(hp_domain_t* d)
-{
-	const int rc = check_domain(d);
-	return rc != HP_OK ? rc : probes_release(d);
-}
-
-int hp_probes_reset(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_reset before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_reset between hp_step_begin and hp_step_end");
-	d->probes.samples = 0;                   // (stream order: a read queued before this call has its records before a later sample overwrites them)
-	++d->probes.epoch;
-	return HP_OK;
-}
+int hp_probes_disable(hp_domain_t* d) { return log_disable(d, PROBES); }
+int hp_probes_reset(hp_domain_t* d) { return log_reset(d, PROBES); }
 
 int hp_probes_sample(hp_domain_t* d)
 {
-	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	const int rc = log_sample_check(d, PROBES);
 	if (rc != HP_OK) return rc;
-	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_sample before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_sample between hp_step_begin and hp_step_end");
-	if (d->probes.samples >= d->probes.capacity)
-		return fail(HP_ERR_STATE, "hp_probes_sample: the record buffer is full (read the records, then hp_probes_reset)");
+	RecordLog& g = d->probes.log;
 	const ProbeLists& p = d->probes.lists;
 	const unsigned blocks = p.gauge_blocks + p.sections;
 	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
 	with_real(d, [&](auto zero) {
 		using T = decltype(zero);
 		hipLaunchKernelGGL((record_probes<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
-		                   (const Scalars<T>*)d->scalars, p, d->probes.records, (unsigned long long)d->probes.samples,
-		                   (unsigned long long)d->probes.stride, d->desc.dx);
+		                   (const Scalars<T>*)d->scalars, p, (double*)g.records, (unsigned long long)g.samples, (unsigned long long)g.stride, d->desc.dx);
 	});
 	HIP_TRY(hipGetLastError());
-	++d->probes.samples;
+	++g.samples;
 	return HP_OK;
 }
 
-int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_read before hp_probes_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_probes_read between hp_step_begin and hp_step_end");
-	if (first > d->probes.samples || count > d->probes.samples - first)
-		return fail(HP_ERR_INVALID, "hp_probes_read: first + count beyond the samples taken");
-	if (count == 0) return HP_OK;
-	if (!records) return fail(HP_ERR_INVALID, "hp_probes_read: records == NULL");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	HIP_TRY(hipMemcpyAsync(records, d->probes.records + first * d->probes.stride, (size_t)(count * d->probes.stride) * sizeof(double),
-	                       hipMemcpyDeviceToHost, d->stream));
-	return HP_OK;
-}
-
-int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->probes.on) return fail(HP_ERR_STATE, "hp_probes_info before hp_probes_enable");
-	if (samples) *samples = d->probes.samples;
-	if (capacity) *capacity = d->probes.capacity;
-	if (stride) *stride = d->probes.stride;
-	return HP_OK;
-}
+int hp_probes_read(hp_domain_t* d, uint64_t first, uint64_t count, double* records) { return log_read(d, PROBES, first, count, records); }
+int hp_probes_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride) { return log_info(d, PROBES, samples, capacity, stride); }
 
 // ---- the zone recorder (hp_zones.hpp) ----
 int hp_zones_enable(hp_domain_t* d, const hp_zones_desc_t* desc)
 {
 	// argument checks first: none of them touches the device
-	if (!desc) return fail(HP_ERR_INVALID, "hp_zones_enable: desc == NULL");
-	if (desc->struct_size != sizeof(hp_zones_desc_t)) return fail(HP_ERR_INVALID, "hp_zones_desc_t size mismatch (ABI)");
-	if (desc->capacity < 1) return fail(HP_ERR_INVALID, "hp_zones_enable: capacity must be at least 1");
+	int rc = log_check_desc(ZONES, desc);
+	if (rc != HP_OK) return rc;
 	if (desc->zone_count < 1 || desc->zone_count > ZONES_MAX) return fail(HP_ERR_INVALID, "hp_zones_enable: zone_count outside 1..4096");
 	if (!desc->zone_of_cell) return fail(HP_ERR_INVALID, "hp_zones_enable: zone_of_cell == NULL");
 	if (!(desc->flood_depth >= OUT_WET)) return fail(HP_ERR_INVALID, "hp_zones_enable: flood_depth must be at least 1e-8");
 	const uint64_t stride = 1 + (uint64_t)ZONE_WORDS * desc->zone_count;
-	if ((uint64_t)desc->capacity * stride * sizeof(uint64_t) > ZONES_MAX_BYTES)
-		return fail(HP_ERR_INVALID, "hp_zones_enable: capacity x stride x 8 exceeds 256 MiB");
+	if ((rc = log_check_bytes(ZONES, desc->capacity, stride)) != HP_OK) return rc;
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	const uint64_t cells = d->cells;
 	for (uint64_t k = 0; k < cells; ++k)
 		if (desc->zone_of_cell[k] > desc->zone_count)
 			return fail(HP_ERR_INVALID, "hp_zones_enable: cell " + std::to_string(k) + ": zone id " + std::to_string(desc->zone_of_cell[k]) + " above zone_count");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_enable between hp_step_begin and hp_step_end");
-	if ((rc = zones_release(d)) != HP_OK) return rc;
-	hipError_t e = hipMalloc((void**)&d->zones.ids, (size_t)cells * sizeof(uint16_t));
-	if (e == hipSuccess) e = hipMalloc((void**)&d->zones.records, (size_t)desc->capacity * stride * sizeof(uint64_t));
-	if (e == hipSuccess) e = hipMemcpyAsync(d->zones.ids, desc->zone_of_cell, (size_t)cells * sizeof(uint16_t), hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);           // (the caller's array is free again on return)
-	if (e != hipSuccess) {
-		hipFree(d->zones.ids); hipFree(d->zones.records);
-		d->zones.ids = nullptr; d->zones.records = nullptr;
-		(void)hipGetLastError();
-		return fail(HP_ERR_HIP, std::string("hp_zones_enable: cannot allocate the id raster and the record buffer: ") + hipGetErrorString(e));
-	}
+	if ((rc = log_open(d, ZONES, "the id raster", desc->zone_of_cell, (size_t)cells * sizeof(uint16_t), desc->capacity, stride)) != HP_OK) return rc;
 	d->zones.flood_depth = desc->flood_depth;
-	d->zones.capacity = desc->capacity;
-	d->zones.stride = stride;
-	d->zones.samples = 0;
-	d->zones.on = true;
-	++d->zones.epoch;
 	return HP_OK;
 }
 
-int hp_zones_disable(hp_domain_t* d)
-{
-	const int rc = check_domain(d);
-	return rc != HP_OK ? rc : zones_release(d);
-}
-
-int hp_zones_reset(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_reset before hp_zones_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_reset between hp_step_begin and hp_step_end");
-	d->zones.samples = 0;                    // (stream order: a read queued before this call has its records before a later sample overwrites them)
-	++d->zones.epoch;
-	return HP_OK;
-}
+int hp_zones_disable(hp_domain_t* d) { return log_disable(d, ZONES); }
+int hp_zones_reset(hp_domain_t* d) { return log_reset(d, ZONES); }
 
 int hp_zones_sample(hp_domain_t* d)
 {
-	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: a sample never sees a state that is re-run)
+	const int rc = log_sample_check(d, ZONES);
 	if (rc != HP_OK) return rc;
-	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_sample before hp_zones_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_sample between hp_step_begin and hp_step_end");
-	if (d->zones.samples >= d->zones.capacity)
-		return fail(HP_ERR_STATE, "hp_zones_sample: the record buffer is full (read the records, then hp_zones_reset)");
-	unsigned long long* rec = d->zones.records + d->zones.samples * d->zones.stride;
+	RecordLog& g = d->zones.log;
+	unsigned long long* rec = g.records + g.samples * g.stride;
 	// one fill (the sums start from 0, the maxima from the bit pattern of +0.0), one launch.  The waves split the cells into
 	// contiguous runs of a multiple of 64; the record does not depend on the shape.
-	HIP_TRY(hipMemsetAsync(rec, 0, (size_t)d->zones.stride * sizeof(uint64_t), d->stream));
+	HIP_TRY(hipMemsetAsync(rec, 0, (size_t)g.stride * sizeof(uint64_t), d->stream));
 	const size_t n = d->cells;
 	const unsigned blocks = stream_blocks(n);
 	const size_t waves = (size_t)blocks * (256 / 64);
 	const size_t per_wave = ((n + waves - 1) / waves + 63) / 64 * 64;
 	with_real(d, [&](auto zero) { using T = decltype(zero);              // (the buffer hp_domain_download(HP_ARRAY_STATE) reads)
 		hipLaunchKernelGGL((record_zones<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
-		                   (const unsigned short*)d->zones.ids, (const Scalars<T>*)d->scalars, rec, n, per_wave, d->zones.flood_depth);
+		                   (const unsigned short*)g.input, (const Scalars<T>*)d->scalars, rec, n, per_wave, d->zones.flood_depth);
 	});
 	HIP_TRY(hipGetLastError());
-	++d->zones.samples;
+	++g.samples;
 	return HP_OK;
 }
 
-int hp_zones_read(hp_domain_t* d, uint64_t first, uint64_t count, uint64_t* records)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_read before hp_zones_enable");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_zones_read between hp_step_begin and hp_step_end");
-	if (first > d->zones.samples || count > d->zones.samples - first)
-		return fail(HP_ERR_INVALID, "hp_zones_read: first + count beyond the samples taken");
-	if (count == 0) return HP_OK;
-	if (!records) return fail(HP_ERR_INVALID, "hp_zones_read: records == NULL");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	HIP_TRY(hipMemcpyAsync(records, d->zones.records + first * d->zones.stride, (size_t)(count * d->zones.stride) * sizeof(uint64_t),
-	                       hipMemcpyDeviceToHost, d->stream));
-	return HP_OK;
-}
-
-int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!d->zones.on) return fail(HP_ERR_STATE, "hp_zones_info before hp_zones_enable");
-	if (samples) *samples = d->zones.samples;
-	if (capacity) *capacity = d->zones.capacity;
-	if (stride) *stride = d->zones.stride;
-	return HP_OK;
-}
+int hp_zones_read(hp_domain_t* d, uint64_t first, uint64_t count, uint64_t* records) { return log_read(d, ZONES, first, count, records); }
+int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride) { return log_info(d, ZONES, samples, capacity, stride); }
 } // extern "C"

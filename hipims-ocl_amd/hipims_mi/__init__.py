@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -311,6 +312,67 @@ def device_info(device: int = 0) -> dict:
                 lds_bytes_per_cu=info.lds_bytes_per_cu, wavefront=info.wavefront, fp64=bool(info.fp64))
 
 
+class _RecordLog:
+    """The host side of a recorder's record log (hp_probes_* / hp_zones_*): the records read back whenever the device buffer was
+    full, and which of them a state_restore keeps.  The three callables are the library's: info() -> (samples in the device
+    buffer, its capacity, words per record), read(out) fills out[pending, stride] and returns once it has landed, reset() empties
+    the device buffer."""
+
+    def __init__(self, dtype, info, read, reset):
+        self.dtype, self._info, self._read, self._reset = dtype, info, read, reset
+        self.on = False
+        self.drained = []                               # records read back when the device buffer was full: [k, stride] arrays
+        self.generation = 0                             # counts opened / closed / reset: a checkpoint's count belongs to one
+        self.saved_at = None                            # saved()'s (generation, samples so far)
+
+    def opened(self):
+        self.on, self.drained = True, []
+        self.generation += 1
+
+    def closed(self):
+        self.on, self.drained = False, []
+        self.generation += 1
+
+    def info(self):
+        n, capacity, stride = self._info()
+        return dict(samples=sum(len(a) for a in self.drained) + n, pending=n, capacity=capacity, stride=stride)
+
+    def pending(self):
+        info = self.info()
+        out = np.empty((info["pending"], info["stride"]), self.dtype)
+        if info["pending"]:
+            self._read(out)
+        return out
+
+    def before_sample(self):
+        """A full device buffer is read back and emptied (one copy, one sync per `capacity` samples)."""
+        info = self.info() if self.on else None         # (not recording: the library's own answer to the sample)
+        if info and info["pending"] == info["capacity"]:
+            self.drained.append(self.pending())
+            self._reset()
+
+    def records(self):
+        return np.concatenate(self.drained + [self.pending()], axis=0)
+
+    def reset(self):
+        self._reset()
+        self.drained = []
+        self.generation += 1
+
+    def saved(self):
+        self.saved_at = (self.generation, self.info()["samples"]) if self.on else None
+
+    def restored(self):
+        """The library's count is the saved one again (0 if the checkpoint is not this generation's): the records read back
+        already follow it."""
+        if not self.on:
+            return
+        total = self.saved_at[1] if self.saved_at and self.saved_at[0] == self.generation else 0
+        drained = np.concatenate(self.drained, axis=0) if self.drained else None
+        keep = max(0, total - self.info()["pending"])
+        self.drained = [drained[:keep]] if drained is not None and keep else []
+
+
 class _DevicePointer:
     """Raw device allocation exposed through __cuda_array_interface__ so torch can wrap it without a copy."""
 
@@ -355,13 +417,24 @@ class Domain:
         self._bed_host = None
         self._peak_values = []                          # HP_PEAK_* codes the library tracks (peaks_enable's mask)
         self._probes = None                             # (gauges, sections) the library records (probes_enable's lists)
-        self._probes_drained = []                       # records read back when the device buffer was full: [k, stride] arrays
-        self._probes_saved = None                       # state_save's (recorder generation, samples so far)
-        self._probes_generation = 0
+        self._probe_log = self._record_log("hp_probes", np.float64, C.c_double)
         self._zones = None                              # zone_count the library records (zones_enable's)
-        self._zones_drained = []                        # as for the probes
-        self._zones_saved = None
-        self._zones_generation = 0
+        self._zone_log = self._record_log("hp_zones", np.uint64, C.c_uint64)
+
+    def _record_log(self, prefix, dtype, ctype):
+        """The host side of the recorder `prefix`, on this domain's hp_*_info, hp_*_read + sync and hp_*_reset."""
+        dom = weakref.proxy(self)                       # (no cycle: the domain still goes, and frees the device, with its last reference)
+        call = lambda name, *args: _check(dom.lib, getattr(dom.lib, prefix + name)(dom.h, *args), prefix + name)
+
+        def info():
+            n, cap, stride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+            call("_info", C.byref(n), C.byref(cap), C.byref(stride))
+            return n.value, cap.value, stride.value
+
+        def read(out):
+            call("_read", 0, len(out), out.ctypes.data_as(C.POINTER(ctype)))
+            dom.sync()
+        return _RecordLog(dtype, info, read, lambda: call("_reset"))
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -537,46 +610,32 @@ class Domain:
                           wx.ctypes.data_as(C.POINTER(C.c_int8)), wy.ctypes.data_as(C.POINTER(C.c_int8)))
         rc = self.lib.hp_probes_enable(self.h, C.byref(desc))
         if rc == -3:                                    # HP_ERR_HIP: the allocation failed and the library has switched recording off
-            self._probes, self._probes_drained = None, []   # (an argument or state error leaves the recorder as it was)
+            self._probes = None                         # (an argument or state error leaves the recorder as it was)
+            self._probe_log.closed()
         _check(self.lib, rc, "hp_probes_enable")
-        self._probes, self._probes_drained = (int(g.size), len(sections)), []
-        self._probes_generation += 1
+        self._probes = (int(g.size), len(sections))
+        self._probe_log.opened()
 
     def probes_disable(self):
         _check(self.lib, self.lib.hp_probes_disable(self.h), "hp_probes_disable")
-        self._probes, self._probes_drained = None, []
-        self._probes_generation += 1
+        self._probes = None
+        self._probe_log.closed()
 
     def probes_info(self):
         """dict(samples, pending, capacity, stride): samples taken since probes_enable, how many of them are still in the device
         buffer, that buffer's capacity and the record length in fp64 words; host-side counters, does not block."""
-        n, cap, stride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(self.lib, self.lib.hp_probes_info(self.h, C.byref(n), C.byref(cap), C.byref(stride)), "hp_probes_info")
-        return dict(samples=sum(len(a) for a in self._probes_drained) + n.value, pending=n.value, capacity=cap.value, stride=stride.value)
-
-    def _probes_pending(self):
-        info = self.probes_info()
-        out = np.empty((info["pending"], info["stride"]), np.float64)
-        if info["pending"]:
-            _check(self.lib, self.lib.hp_probes_read(self.h, 0, info["pending"], out.ctypes.data_as(C.POINTER(C.c_double))), "hp_probes_read")
-            self.sync()
-        return out, info
+        return self._probe_log.info()
 
     def probes_sample(self):
         """One record of the current state: one launch on the domain's stream.  Does not block -- except when the device buffer
         is full: then its records are read back first (one copy, one sync per `capacity` samples)."""
-        info = self.probes_info() if self._probes else None        # (not recording: the library's own answer below)
-        if info and info["pending"] == info["capacity"]:
-            self._probes_drained.append(self._probes_pending()[0])
-            _check(self.lib, self.lib.hp_probes_reset(self.h), "hp_probes_reset")
+        self._probe_log.before_sample()
         _check(self.lib, self.lib.hp_probes_sample(self.h), "hp_probes_sample")
 
     def probes(self):
         """Every sample since probes_enable, in order: {"t": [n], "gauges": [n, G, 4] (z, depth, qx, qy), "sections": [n, S]
         (discharge, m3/s)}, bit-identical to frontend.ProbeRecorder fed the same samples; blocks."""
-        pending, _ = self._probes_pending()
-        rec = np.concatenate(self._probes_drained + [pending], axis=0)
-        return split_probe_records(rec, *self._probes)
+        return split_probe_records(self._probe_log.records(), *self._probes)
 
     # ---- the zone recorder (hp_zones_*): per-zone counts, volume, largest depth and speed, one record per SAMPLE the host takes ----
     def zones_enable(self, ids, zone_count=None, flood_depth=0.1, capacity=4096):
@@ -604,50 +663,35 @@ class Domain:
         desc = ZonesDesc(C.sizeof(ZonesDesc), int(capacity), int(zone_count), 0, ids16.ctypes.data_as(C.POINTER(C.c_uint16)), float(flood_depth))
         rc = self.lib.hp_zones_enable(self.h, C.byref(desc))
         if rc == -3:                                    # HP_ERR_HIP: the allocation failed and the library has switched recording off
-            self._zones, self._zones_drained = None, []
+            self._zones = None
+            self._zone_log.closed()
         _check(self.lib, rc, "hp_zones_enable")
-        self._zones, self._zones_drained = int(zone_count), []
-        self._zones_generation += 1
+        self._zones = int(zone_count)
+        self._zone_log.opened()
 
     def zones_disable(self):
         _check(self.lib, self.lib.hp_zones_disable(self.h), "hp_zones_disable")
-        self._zones, self._zones_drained = None, []
-        self._zones_generation += 1
+        self._zones = None
+        self._zone_log.closed()
 
     def zones_reset(self):
         """Forget every sample taken so far (those read back already too)."""
-        _check(self.lib, self.lib.hp_zones_reset(self.h), "hp_zones_reset")
-        self._zones_drained = []
-        self._zones_generation += 1
+        self._zone_log.reset()
 
     def zones_info(self):
         """dict(samples, pending, capacity, stride): samples taken since zones_enable / zones_reset, how many of them are still in
         the device buffer, that buffer's capacity and the record length in 64-bit words; host-side counters, does not block."""
-        n, cap, stride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(self.lib, self.lib.hp_zones_info(self.h, C.byref(n), C.byref(cap), C.byref(stride)), "hp_zones_info")
-        return dict(samples=sum(len(a) for a in self._zones_drained) + n.value, pending=n.value, capacity=cap.value, stride=stride.value)
-
-    def _zones_pending(self):
-        info = self.zones_info()
-        out = np.empty((info["pending"], info["stride"]), np.uint64)
-        if info["pending"]:
-            _check(self.lib, self.lib.hp_zones_read(self.h, 0, info["pending"], out.ctypes.data_as(C.POINTER(C.c_uint64))), "hp_zones_read")
-            self.sync()
-        return out, info
+        return self._zone_log.info()
 
     def zones_sample(self):
         """One record of the current state: one fill and one launch on the domain's stream.  Does not block -- except when the
         device buffer is full: then its records are read back first (one copy, one sync per `capacity` samples)."""
-        info = self.zones_info() if self._zones else None          # (not recording: the library's own answer below)
-        if info and info["pending"] == info["capacity"]:
-            self._zones_drained.append(self._zones_pending()[0])
-            _check(self.lib, self.lib.hp_zones_reset(self.h), "hp_zones_reset")
+        self._zone_log.before_sample()
         _check(self.lib, self.lib.hp_zones_sample(self.h), "hp_zones_sample")
 
     def zone_records(self):
         """Every record since zones_enable, in order: uint64 [n, 1 + 7 Z] (hp_zones_read's layout); blocks."""
-        pending, _ = self._zones_pending()
-        return np.concatenate(self._zones_drained + [pending], axis=0)
+        return self._zone_log.records()
 
     def zones(self):
         """Every sample since zones_enable, in order (split_zone_records' dictionary), equal in every word to frontend.ZoneRecorder
@@ -663,23 +707,13 @@ class Domain:
     def state_save(self):
         """Device-side checkpoint of cell states + time-control block (saveCurrentState without the PCIe trip)."""
         _check(self.lib, self.lib.hp_state_save(self.h), "hp_state_save")
-        self._probes_saved = (self._probes_generation, self.probes_info()["samples"]) if self._probes else None
-        self._zones_saved = (self._zones_generation, self.zones_info()["samples"]) if self._zones else None
+        self._probe_log.saved()
+        self._zone_log.saved()
 
     def state_restore(self):
         _check(self.lib, self.lib.hp_state_restore(self.h), "hp_state_restore")
-        if self._probes:                                # the records read back already follow the library's count
-            saved = self._probes_saved
-            total = saved[1] if saved and saved[0] == self._probes_generation else 0
-            drained = np.concatenate(self._probes_drained, axis=0) if self._probes_drained else None
-            keep = max(0, total - self.probes_info()["pending"])
-            self._probes_drained = [drained[:keep]] if drained is not None and keep else []
-        if self._zones:
-            saved = self._zones_saved
-            total = saved[1] if saved and saved[0] == self._zones_generation else 0
-            drained = np.concatenate(self._zones_drained, axis=0) if self._zones_drained else None
-            keep = max(0, total - self.zones_info()["pending"])
-            self._zones_drained = [drained[:keep]] if drained is not None and keep else []
+        self._probe_log.restored()
+        self._zone_log.restored()
 
     # ---- boundaries ----
     def add_uniform(self, definition, series, interval, length):

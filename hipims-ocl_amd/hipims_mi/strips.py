@@ -538,6 +538,15 @@ class StripRunner:
         self.dist.gather_object(mine, parts, dst=0)                 # rasters travel to rank 0 only
         return assemble_outputs(parts) if self.rank == 0 else None
 
+    def _gather_parts(self, mine):
+        """Every rank's `mine` in rank order on rank 0, None on the other ranks: pickled over the process group, which a single
+        rank does not need."""
+        if self.world == 1:
+            return [mine]
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        return parts
+
     # ---- the peak tracker: every rank tracks its own strip (ghost rows included: they hold their owners' values between
     #      batches), nothing is exchanged; only owned rows are ever gathered ----
     def peaks_enable(self, values, arrival_depth=0.01):
@@ -589,10 +598,7 @@ class StripRunner:
         if len(self._probe_mine):
             series = self.engine.probes() if self._probe_host is None else self._probe_host.series()
             mine = (self._probe_mine, series["t"], series["gauges"])
-        parts = [mine]
-        if self.world > 1:
-            parts = [None] * self.world if self.rank == 0 else None
-            self.dist.gather_object(mine, parts, dst=0)
+        parts = self._gather_parts(mine)
         return assemble_probes(parts, self._probe_gauges, self._probe_sections, self._probe_dx) if self.rank == 0 else None
 
     # ---- the zone recorder: every rank records its local rows with the ghost rows' ids set to 0, so that every cell is counted on
@@ -632,10 +638,7 @@ class StripRunner:
         from . import frontend, split_zone_records
         self._zones_required("gather_zones")
         mine = self.engine.zone_records() if self._zone_host is None else self._zone_host.words()
-        parts = [mine]
-        if self.world > 1:
-            parts = [None] * self.world if self.rank == 0 else None
-            self.dist.gather_object(mine, parts, dst=0)
+        parts = self._gather_parts(mine)
         return split_zone_records(frontend.combine_zones(parts), self._zone_count, self._zone_dx) if self.rank == 0 else None
 
     def gather_stats(self):
