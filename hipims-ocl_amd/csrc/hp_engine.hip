@@ -735,6 +735,10 @@ static bool pair_skip_enabled()
 	return v;
 }
 static void still_rec_forget(hp_domain* d) { d->still_rec_valid = false; }
+// slot[SLOT_M1] prices the primary buffer under the boundary set and the bed of its time: a change of either voids the figure a checkpoint
+// holds as well -- hp_state_restore brings the slot block back, but neither the boundary list nor the bed (as need_full_reduce, a mark
+// left since the save stays)
+static void m1_forget(hp_domain* d) { d->m1_valid = false; d->saved_m1_valid = false; }
 static int still_rec_alloc(hp_domain* d, const int windows)
 {
 	const size_t slots = (size_t)windows * (size_t)d->desc.rows;
@@ -1200,7 +1204,7 @@ int hp_domain_upload(hp_domain_t* d, int which, const void* host, size_t bytes)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
 	still_rec_forget(d);                                                  // (state, bed or Manning: the records describe the old ones)
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
 	if (d->in_step) return fail(HP_ERR_STATE, "upload between hp_step_begin and hp_step_end");
@@ -1309,7 +1313,8 @@ int hp_state_restore(hp_domain_t* d)
 	d->other_stale = false;                                               // (a checkpoint is taken with both buffers brought up to date)
 	d->rings_differ = d->saved_rings_differ;
 	d->rings_checked = false;
-	d->m1_valid = d->saved_m1_valid;                                      // (slot[SLOT_M1] has come back with the slot block)
+	d->m1_valid = d->saved_m1_valid;                                      // (slot[SLOT_M1] has come back with the slot block -- unless a boundary or the
+	                                                                      // bed changed since the save: m1_forget)
 	d->tune_phase = 0;                                                    // (another state: the exact mode's pairs-or-singles choice is measured anew -- a sample
 	                                                                      // still in flight measured the state that is being replaced: with samples every 128
 	                                                                      // iterations bench.py's restore found one in flight nearly every time and the timed
@@ -1371,7 +1376,7 @@ int hp_boundary_add_uniform(hp_domain_t* d, int definition, const void* series, 
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
 	if (!series || entries == 0 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad uniform boundary");
 	if (definition != HP_UNIFORM_RAIN_INTENSITY && definition != HP_UNIFORM_LOSS_RATE)
 		return fail(HP_ERR_INVALID, "unknown uniform boundary definition");
@@ -1390,7 +1395,7 @@ int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, u
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
 	if (!grids || entries == 0 || grid_rows == 0 || grid_cols == 0 || !(resolution > 0) || !(interval > 0))
 		return fail(HP_ERR_INVALID, "bad gridded boundary");
 	{
@@ -1418,7 +1423,7 @@ int hp_boundary_add_cell(hp_domain_t* d, int depth_definition, int discharge_def
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
 	if (!cells || count == 0 || !series || entries < 2 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad cell boundary");
 	if (depth_definition < 0 || depth_definition > 3 || discharge_definition < 0 || discharge_definition > 3)
 		return fail(HP_ERR_INVALID, "unknown cell boundary definition");
@@ -1452,7 +1457,7 @@ int hp_boundary_clear(hp_domain_t* d)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
 	HIP_TRY(hipStreamSynchronize(d->stream));
 	for (auto& b : d->bdy) { hipFree(b.data); hipFree(b.cells); }
 	d->bdy.clear();
@@ -1541,6 +1546,7 @@ int hp_step_begin(hp_domain_t* d)
 		                                "(two reaches of ghost rows are hp_strip_step_batch's)");
 	d->split_now = true;
 	d->fork_is_advance = fork_ready;
+	d->m1_valid = false;                           // (a single iteration prices one maximum, as in run_single: the next pair starts cold)
 	if ((rc = dispatch_begin(d)) != HP_OK) return rc;
 	d->in_step = true;
 	return HP_OK;
@@ -1600,6 +1606,9 @@ bool spec_wanted(const hp_domain* d, uint32_t n)
 int spec_begin(hp_domain* d)
 {
 	const size_t bytes = d->cells * 4 * d->esize, sc_bytes = sizeof(Scalars<double>);
+	// (after iteration pairs, as hp_state_save: the batch's first single iteration would repair the other buffer and clear other_stale, and
+	// a replay would put the stale copy back with the flag down)
+	{ const int rc = repair_other_buffer(d); if (rc != HP_OK) return rc; }
 	if (!d->spec_state) HIP_TRY(hipMalloc(&d->spec_state, 2 * bytes));
 	if (!d->spec_scalars) HIP_TRY(hipMalloc(&d->spec_scalars, sc_bytes + CFL_SLOT_BYTES));
 	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_SPEC * d->esize, 0, d->esize, d->stream));
@@ -1665,6 +1674,8 @@ int run_iterations(hp_domain* d, uint32_t n_iterations)
 	int rc;
 	const bool tune = tuner_on(d);
 	if (tune && (rc = tuner_poll(d)) != HP_OK) return rc;
+	// (partial uploads since the last look: the rings are compared once, before the first pair_eligible -- blocks)
+	if (d->rings_differ && !d->rings_checked && n_iterations >= 2 && pairs_possible(d) && (rc = rings_really_differ(d)) != HP_OK) return rc;
 	for (uint32_t i = 0; i < n_iterations; ++i) {
 		if (tune && d->tune_phase != 0 && (i & 15u) == 15u && (rc = tuner_poll(d)) != HP_OK) return rc;   // (two event queries: host time, behind the queue)
 		// (STRICT) a sample: three pairs, then six single iterations -- the first pair and the first two single iterations warm the
