@@ -3,6 +3,7 @@
 // hp_observers.hpp (the code of the four observers whose state is declared here, and of the RecordLog two of them share).
 #pragma once
 #include "../../include/hipims_mi.h"
+#include "hp_facts.hpp"
 #include "hp_kernels.hpp"
 #include "hp_peaks.hpp"
 #include "hp_probes.hpp"
@@ -111,15 +112,14 @@ struct hp_domain {
 	void*            cfl_slot = nullptr;              // CFL_SLOT_BYTES: running max | SLOT_SAVED last used max | SLOT_EDGE ring maxima of [0], [1]
 	bool             manning_uniform = false;         // found at upload: one value everywhere -> kernels skip the array
 	double           manning_value = 0.0;
-	bool             need_full_reduce = true;         // the remembered maximum is stale (upload / link import)
-	bool             edge_dirty = true;               // edge-ring maxima must be re-priced
+	BufferFacts      facts;                           // what the host knows about the state buffers and the slot block between launches, and the
+	                                                  // checkpoint's and the speculative batch's copies of it: changed through its events only
 	bool             bdy_on_ring = false;             // a cell boundary imposes values on never-written ring cells: re-price every iteration
 	int              adv_fresh = 1;                   // does hp_step_end's advance kernel read a new maximum?
 	Tiling           tiling;                          // tile heights and row bands of its launches (hp_tiling.hpp: choose_tiling)
 	int              sweep_flip = 0;                  // parity of the whole-domain flux launches: every other one visits each band's tiles from
 	                                                  // the top down, so that it starts on the rows its predecessor wrote last (sweep_alternates)
 	void*            host_scalars = nullptr;          // pinned mirror
-	int              use_alt = 0;                     // bUseAlternateKernel
 	bool             in_step = false;
 	std::vector<Boundary> bdy;
 	// area boundaries carried by the flux kernel's fused epilogue (K1, FUSED): device copy of their descriptors
@@ -136,8 +136,8 @@ struct hp_domain {
 	double           timing_overhead_ms = 0.0;        // an empty event pair's own time (taken off every sample)
 	long             own_lo = 0, own_hi = 0;          // rows this rank owns (CFL reduction range)
 	// ghost rows of a strip: `ghost_rows` stored per interior side (g or 2g, g = the scheme's stencil reach), of which
-	// `ghost_valid` currently hold their owners' values; an iteration consumes g of them, the exchange refills them all
-	long             ghost_rows = 0, ghost_valid = 0, saved_ghost_valid = 0;
+	// facts->ghost_valid currently hold their owners' values; an iteration consumes g of them, the exchange refills them all
+	long             ghost_rows = 0;
 	bool             split_now = false;               // this iteration is followed by an exchange: halo part on its own stream
 	// what the ranks told each other at the start of the batch (hp_strip_step_batch): which of them price a new maximum on
 	// the iterations that the ping-pong phase alone would not make them price
@@ -155,8 +155,6 @@ struct hp_domain {
 	void*            saved_state = nullptr;
 	void*            saved_scalars = nullptr;         // Scalars<T> + the four CFL slots
 	bool             saved_valid = false;
-	bool             saved_full_reduce = true, saved_edge_dirty = true;
-	int              saved_use_alt = 0;
 	ncclComm_t       comm = nullptr;
 	int              comm_rank = 0, comm_world = 1;
 	hipEvent_t       ev_xchg = nullptr;               // ghost rows of the iteration in flight have arrived
@@ -175,26 +173,18 @@ struct hp_domain {
 	bool             push_now = false;                // this iteration's advance kernel carries the ghost rows
 	// the flux launch's own tail block instead of a separate advance launch (LaunchTail, hp_kernels.hpp): small launches only
 	unsigned long long* tail_words = nullptr;         // one word per flux block (EMPTY between launches)
-	bool             rings_differ = false;            // a partial state upload went into ONE buffer: the edge rings of the two may differ -- no iteration pairs until the next full upload (pair_eligible)
-	bool             saved_rings_differ = false;
-	bool             rings_checked = false;           // ... and have been compared since (rings_really_differ): the flag is a fact, not a maybe
 	bool             fill_now = false;                // this iteration's K1 launch stores the cells the reference leaves untouched as well (dispatch_begin)
-	bool             other_stale = false;             // pairs (godunov_march2) ran since the non-current state buffer last held a state the single-iteration kernels can build on
 	// quirk Q3 across pair launches, exactly (hp_kernels.hpp: PairAux): stamps of the cells whose first-step stale value the next launch needs
 	void*            z_state = nullptr;               // stamp records, one per cell: State4<T> + the number of the pair launch that wrote it (allocated with the first pair)
 	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
-	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while other_stale holds
+	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while facts->other_stale holds
 	// still records of the FAST fp64 pair kernel (hp_kernels.hpp: StillRec; round 8): two halves of windows x rows records, the last launch's
-	// in half still_rec_half, then two counters (hp_pair_stats).  Valid while no writer of either state buffer has run since that launch
-	// other than such launches themselves (still_rec_forget)
+	// in half still_rec_half, then two counters (hp_pair_stats).  Valid (facts->still_rec_valid) while no writer of either state buffer has run
+	// since that launch other than such launches themselves
 	void*            still_rec = nullptr;
 	size_t           still_rec_slots = 0;             // records per half
 	int              still_rec_half = 0;
-	bool             still_rec_valid = false;
 	bool             still_rec_last = false;          // the last pair launch wrote records (hp_pair_stats)
-	bool             saved_m1_valid = false;
-	bool             pair_fused_next = false;         // the last pair stored its state with the next iteration's boundaries applied (SLOT_BDY = 1)
-	bool             m1_valid = false;                // area boundaries: cfl_slot[SLOT_M1] prices the primary buffer with the next iteration's boundaries (left by the last pair)
 	uint64_t         pair_cold_starts = 0;
 	// STRICT: pairs or single iterations, by measurement (pair_tuner: the two are the same bits; which is faster depends on how much of
 	// the water stands still)
@@ -218,7 +208,7 @@ struct hp_domain {
 	uint32_t         spec_pending = 0;                // iterations of a speculative batch whose flag word has not been looked at yet
 	void*            spec_state = nullptr;            // snapshot in front of the batch: both state buffers ...
 	void*            spec_scalars = nullptr;          // ... Scalars<T> + the slot block
-	struct { int use_alt, adv_fresh; bool need_full_reduce, edge_dirty; long ghost_valid; uint64_t cells_calculated, iterations; } spec_host;
+	struct { int adv_fresh; uint64_t cells_calculated, iterations; } spec_host;   // ... and what the host counts besides the facts
 	uint64_t         spec_batches = 0, spec_replays = 0;
 	OutputStage      out;
 	PeakTracker      peaks;

@@ -164,7 +164,7 @@ template <typename T> int price_edge_ring(hp_domain* d)
 			                   (const T*)d->bed, lo, hi, south, north, w, (T*)d->cfl_slot + SLOT_EDGE + b);
 	}
 	HIP_TRY(hipGetLastError());
-	d->edge_dirty = false;
+	d->facts.edge_ring_priced();
 	return HP_OK;
 }
 
@@ -206,7 +206,7 @@ bool march2_rseg_forced()               // (run_pair_t: no STRICT 12-row cap the
 inline void launch_rows(const hp_domain* d, long g, long& lo, long& hi)
 {
 	const bool south = d->desc.row_offset > 0, north = d->desc.row_offset + d->desc.rows < d->desc.global_rows;
-	const long keep = d->ghost_rows - (d->ghost_valid - g);             // ghost rows at each interior side NOT updated now
+	const long keep = d->ghost_rows - (d->facts->ghost_valid - g);      // ghost rows at each interior side NOT updated now
 	lo = south ? keep : g;
 	hi = d->desc.rows - (north ? keep : g);
 }
@@ -248,7 +248,7 @@ template <typename T> int make_tail(hp_domain* d, unsigned& blocks, int part, hi
 	int kind = 1;
 	if (d->push_now) {
 		const long G = d->ghost_rows, rows = d->desc.rows, cols = d->desc.cols;
-		const int b = d->use_alt ^ 1;
+		const int b = d->facts->use_alt ^ 1;
 		if (d->peer_state[0][b]) {
 			tail.peer_rows[0] = (State4<T>*)d->peer_state[0][b] + (d->peer_rows[0] - 2 * G) * cols;     // my row G -> its row rows_s - G
 			tail.edge_rows[0] = (int)G; tail.edge_rows[1] = (int)(2 * G);
@@ -412,14 +412,14 @@ int launch_flux(hp_domain* d, const void* src, void* dst, int cfl_mode, int part
 	const Params<T> p = make_params<T>(d);
 	if (d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK) {
 		if (p.cols < 5 || p.rows < 5) return fail(HP_ERR_INVALID, "MUSCL-Hancock needs at least a 5x5 grid");
-		return cfl_mode ? launch_muscl<T, STRICT, 1>(d, src, dst, d->use_alt ^ 1, part, stream)
+		return cfl_mode ? launch_muscl<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream)
 		                : launch_muscl<T, STRICT, 0>(d, src, dst, 0, part, stream);
 	}
 	if (d->desc.scheme == HP_SCHEME_INERTIAL) {
 		if (p.cols < 3 || p.rows < 3) return fail(HP_ERR_INVALID, "the inertial scheme needs at least a 3x3 grid");
 		switch (cfl_mode) {
-		case 1:  return launch_inertial<T, STRICT, 1>(d, src, dst, d->use_alt ^ 1, part, stream);
-		case 2:  return launch_inertial<T, STRICT, 2>(d, src, dst, d->use_alt, part, stream);
+		case 1:  return launch_inertial<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream);
+		case 2:  return launch_inertial<T, STRICT, 2>(d, src, dst, d->facts->use_alt, part, stream);
 		default: return launch_inertial<T, STRICT, 0>(d, src, dst, 0, part, stream);
 		}
 	}
@@ -435,8 +435,8 @@ int launch_flux(hp_domain* d, const void* src, void* dst, int cfl_mode, int part
 	}
 	// ring of the buffer that is priced: mode 1 -> dst, mode 2 -> src (= primary)
 	switch (cfl_mode) {
-	case 1:  return launch_march<T, STRICT, 1>(d, src, dst, d->use_alt ^ 1, part, stream);
-	case 2:  return launch_march<T, STRICT, 2>(d, src, dst, d->use_alt, part, stream);
+	case 1:  return launch_march<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream);
+	case 2:  return launch_march<T, STRICT, 2>(d, src, dst, d->facts->use_alt, part, stream);
 	default: return launch_march<T, STRICT, 0>(d, src, dst, 0, part, stream);
 	}
 }
@@ -445,8 +445,8 @@ static bool pairs_possible(const hp_domain* d);
 // boundaries -> flux -> local CFL maximum   (CSchemeGodunov.cpp:1637-1657)
 template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 {
-	void* src = d->state[d->use_alt];
-	void* dst = d->state[d->use_alt ^ 1];
+	void* src = d->state[d->facts->use_alt];
+	void* dst = d->state[d->facts->use_alt ^ 1];
 	int rc;
 	const bool has_bdy = !d->bdy.empty() && d->desc.scheme != HP_SCHEME_MUSCL_HANCOCK;   // MUSCL never applies them (Q8)
 	if (has_bdy) {
@@ -459,7 +459,7 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 	const bool q1 = (d->desc.quirks & HP_QUIRK_CFL_READS_PRIMARY) != 0;
 	const bool muscl = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK;
 	const bool basic = d->desc.kernel == HP_KERNEL_BASIC && d->desc.scheme == HP_SCHEME_GODUNOV;
-	const bool dst_is_primary = d->use_alt == 1;
+	const bool dst_is_primary = d->facts->use_alt == 1;
 	int cfl_mode = 0;                                    // fused epilogue of the tuned kernel
 	if (d->desc.dynamic_dt && !basic) {
 		// MUSCL-Hancock has ONE state buffer in the reference (updated in place), so its reduction always sees
@@ -469,7 +469,7 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 		else                       cfl_mode = 0;         // primary untouched: last maximum still holds
 		// the ring maxima are cached from the last upload -- unless a cell boundary rewrites ring cells in place
 		// (bdy_cell accepts any cell; tst_Reduce re-reads every cell each iteration, CLDynamicTimestep.clc:166-249)
-		if (cfl_mode != 0 && (d->edge_dirty || (has_bdy && d->bdy_on_ring)))
+		if (cfl_mode != 0 && (d->facts->edge_dirty || (has_bdy && d->bdy_on_ring)))
 			{ d->fork_is_advance = false; if ((rc = price_edge_ring<T>(d)) != HP_OK) return rc; }
 	}
 
@@ -495,7 +495,7 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 	{
 		static const bool enabled = !(std::getenv("HP_LAUNCH_TAIL") && std::atoi(std::getenv("HP_LAUNCH_TAIL")) == 0);
 		static const bool lonely_too = std::getenv("HP_STRIP_REDUCE_ALWAYS") && std::atoi(std::getenv("HP_STRIP_REDUCE_ALWAYS")) != 0;
-		const bool reduce_after = d->desc.dynamic_dt && cfl_mode == 0 && (basic || d->need_full_reduce);
+		const bool reduce_after = d->desc.dynamic_dt && cfl_mode == 0 && (basic || d->facts->need_full_reduce);
 		const int priced = (d->desc.dynamic_dt && cfl_mode != 0) ? 1 : 0;
 		// strips: the ranks reduce on the iterations strip_allreduce_max says (`everyone`); the tail block serves the two plain
 		// shapes -- this rank priced and everyone reduces, or nobody does -- and leaves the rest (a rank that passes its
@@ -537,12 +537,12 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 	if (d->desc.dynamic_dt) {
 		if (cfl_mode != 0) {
 			d->adv_fresh = 1;
-			d->need_full_reduce = false;
-		} else if (basic || d->need_full_reduce) {
+			d->facts.maximum_priced();
+		} else if (basic || d->facts->need_full_reduce) {
 			const void* reduce_buf = q1 ? d->state[0] : dst;
 			if ((rc = launch_reduce<T>(d, reduce_buf, d->own_lo, d->own_hi)) != HP_OK) return rc;
 			d->adv_fresh = 1;
-			d->need_full_reduce = false;
+			d->facts.maximum_priced();
 		}
 	}
 	return HP_OK;
@@ -554,7 +554,7 @@ PeerPush make_push(const hp_domain* d)
 {
 	const long G = d->ghost_rows, rows = d->desc.rows;
 	const size_t row_bytes = (size_t)d->desc.cols * 4 * d->esize;
-	const int b = d->use_alt ^ 1;
+	const int b = d->facts->use_alt ^ 1;
 	const char* mine = (const char*)d->state[b];
 	PeerPush push{};
 	push.count = (unsigned)((size_t)G * row_bytes / 16);
@@ -614,7 +614,7 @@ template <typename T> int step_end_impl(hp_domain* d)
 		                   (T*)d->cfl_slot, d->adv_fresh, box, PeerPush{});
 	}
 	HIP_TRY(hipGetLastError());
-	d->use_alt ^= 1;                                                      // Threaded_runBatch :1300
+	d->facts.single_ended();
 	d->cells_calculated += (uint64_t)d->desc.cols * (uint64_t)d->desc.rows;   // :1299
 	d->iterations += 1;
 	return HP_OK;
@@ -669,7 +669,7 @@ static bool pairs_possible(const hp_domain* d)          // a single domain
 // them equal to the zero-filled other buffer's wherever the ring is the usual closed wall (state 0), and such domains pair.  Blocks.
 static int rings_really_differ(hp_domain* d)
 {
-	if (!d->rings_differ || d->rings_checked) return HP_OK;
+	if (!d->facts->rings_differ || d->facts->rings_checked) return HP_OK;
 	unsigned long long* word = (unsigned long long*)((char*)d->scalars + 192);     // (device scratch behind the Scalars block)
 	HIP_TRY(hipMemsetAsync(word, 0, 8, d->stream));
 	if (d->desc.precision == 8)
@@ -683,23 +683,19 @@ static int rings_really_differ(hp_domain* d)
 	*host = 1;
 	HIP_TRY(hipMemcpyAsync((void*)host, word, 8, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(hipStreamSynchronize(d->stream));
-	d->rings_checked = true;
-	if (*host == 0) d->rings_differ = false;
+	d->facts.rings_compared(*host == 0);
 	return HP_OK;
 }
-// (not after a PARTIAL upload -- rings_differ, until the next full one: queueWritePartial goes to the current buffer only, so the two
-// buffers' edge rings may differ, and single iterations read the OTHER buffer's ring on every second iteration while a pair carries the
-// primary buffer's through both steps: next to ring cells that matter hydraulically -- an edge without walls -- the two part.  ADVICE r05)
 static bool pair_eligible(const hp_domain* d)
 {
-	return pairs_possible(d) && d->use_alt == 0 && !d->rings_differ && (!d->desc.dynamic_dt || (!d->need_full_reduce && !d->edge_dirty));
+	return pairs_possible(d) && d->facts.pair_ready(d->desc.dynamic_dt != 0);
 }
 // A ROW STRIP runs pairs where it stores two reaches of ghost rows (one exchange per two iterations anyway) and the strips write
 // their rows into each other themselves (transport level 2: the pair's tail block holds the one mailbox round, which is the
 // hand-over).  What THIS rank can do goes into the batch's handshake (strip_handshake); the ranks pair up only if all of them can.
 static bool strip_pairs_possible_here(const hp_domain* d)
 {
-	return pairs_possible_common(d) && d->comm && d->comm_world > 1 && d->peer_direct && d->ghost_rows == 2 && !d->rings_differ;
+	return pairs_possible_common(d) && d->comm && d->comm_world > 1 && d->peer_direct && d->ghost_rows == 2 && !d->facts->rings_differ;
 }
 // The stamps' buffers (PairAux), allocated with a domain's first exact pair.
 // Which pairs keep quirk Q3 exact (godunov_march2's HZ instantiation: 4-9 % slower): HP_PAIR_EXACT=1 all of them, =0 none; default: the
@@ -726,26 +722,20 @@ static int pair_stamps_alloc(hp_domain* d)
 }
 // Still records (hp_kernels.hpp: StillRec): a tile of a FAST fp64 pair launch whose stencil the launch before recorded as one still state,
 // found as it was left, is skipped.  That holds only while nothing else writes either state buffer (or the bed) between the two launches:
-// every such writer calls still_rec_forget -- single iterations and their FILL, the boundary passes (dispatch_begin; pair_cold_start),
-// repair_other_buffer, uploads of any array, hp_state_restore, a speculative batch's replay, a device pointer handed out (hp_device_ptr),
-// and every pair launch that does not write records itself (run_pair_t).  HP_PAIR_SKIP=0: no records, nothing skipped (A/B runs).
+// every such writer says so (hp_facts.hpp: buffers_written_outside), and so does every pair launch that does not write records itself
+// (pair_launched).  HP_PAIR_SKIP=0: no records, nothing skipped (A/B runs).
 static bool pair_skip_enabled()
 {
 	static const bool v = !(std::getenv("HP_PAIR_SKIP") && std::atoi(std::getenv("HP_PAIR_SKIP")) == 0);
 	return v;
 }
-static void still_rec_forget(hp_domain* d) { d->still_rec_valid = false; }
-// slot[SLOT_M1] prices the primary buffer under the boundary set and the bed of its time: a change of either voids the figure a checkpoint
-// holds as well -- hp_state_restore brings the slot block back, but neither the boundary list nor the bed (as need_full_reduce, a mark
-// left since the save stays)
-static void m1_forget(hp_domain* d) { d->m1_valid = false; d->saved_m1_valid = false; }
 static int still_rec_alloc(hp_domain* d, const int windows)
 {
 	const size_t slots = (size_t)windows * (size_t)d->desc.rows;
 	if (d->still_rec && d->still_rec_slots == slots) return HP_OK;
 	hipFree(d->still_rec);
 	d->still_rec = nullptr;
-	d->still_rec_valid = false;
+	d->facts.buffers_written_outside();
 	const size_t bytes = (2 * slots + 1) * sizeof(StillRec);              // (+1: the counters of hp_pair_stats)
 	HIP_TRY(hipMalloc(&d->still_rec, bytes));
 	HIP_TRY(hipMemsetAsync(d->still_rec, 0xff, bytes, d->stream));       // the sentinel (rows no launch writes: the edge ring's)
@@ -759,12 +749,12 @@ static int still_rec_alloc(hp_domain* d, const int windows)
 template <typename T> int pair_cold_start(hp_domain* d)
 {
 	int rc;
-	still_rec_forget(d);
+	d->facts.buffers_written_outside();
 	if ((rc = apply_boundaries<T>(d, d->state[0])) != HP_OK) return rc;
 	if ((rc = launch_reduce<T>(d, d->state[0], d->own_lo, d->own_hi)) != HP_OK) return rc;
 	hipLaunchKernelGGL((pair_cold_start_words<T>), dim3(1), dim3(1), 0, d->stream, (T*)d->cfl_slot);
 	HIP_TRY(hipGetLastError());
-	d->m1_valid = true;
+	d->facts.cold_started();
 	d->pair_cold_starts++;
 	return HP_OK;
 }
@@ -799,28 +789,28 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	int rc;
 	if ((rc = pair_stamps_alloc(d)) != HP_OK) return rc;
 	bool in_place = false;
-	if (bdy && !d->m1_valid) {                                            // (queued in front of the pair launch: same stream)
+	if (bdy && !d->facts->m1_valid) {                                     // (queued in front of the pair launch: same stream)
 		if ((rc = pair_cold_start<T>(d)) != HP_OK) return rc;
 		in_place = true;
-	} else if (bdy) in_place = d->pair_fused_next;                        // the pair before stored this iteration's boundaries with its state
+	} else if (bdy) in_place = d->facts->pair_fused_next;                 // the pair before stored this iteration's boundaries with its state
 	tail.pair = bdy ? 2 : 1;
 	tail.bdy_flag = bdy && followed ? 1 : 0;
 	PairAux<T> aux{};
 	const bool exact = pair_exact(d) && d->z_state != nullptr;
 	if (exact) aux.stamps = StampBufs<T>{(char*)d->z_state, d->haz_words};
-	aux.prev_gen = d->other_stale ? d->pair_gen : 0u;                     // `src` was written by a pair launch: its stamps apply
+	aux.prev_gen = d->facts->other_stale ? d->pair_gen : 0u;              // `src` was written by a pair launch: its stamps apply
 	aux.gen = ++d->pair_gen;
 	if (aux.gen == 0) aux.gen = ++d->pair_gen;                            // (0 means "no launch")
 	aux.list = (const AreaBdyList<T>*)d->fused_list; aux.fuse_next = bdy && followed ? 1 : 0; aux.in_place = in_place ? 1 : 0;
 	aux.truncated = (d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0 ? 1 : 0;
 	// still records: the instantiations that take still runs on a single domain (FAST fp64, no area boundaries, no stamps) -- this launch
-	// writes the half the launch before did not, and reads that one if nothing has written a state buffer since (still_rec_forget)
+	// writes the half the launch before did not, and reads that one if nothing has written a state buffer since (still_rec_valid)
 	const bool recs = sizeof(T) == 8 && pair_skip_enabled() && !strip && !bdy && !exact && d->desc.math_mode != HP_MATH_STRICT && rseg2 <= 32;
 	if (recs) {
 		if ((rc = still_rec_alloc(d, tm.nstrips)) != HP_OK) return rc;
 		StillRec* const base = (StillRec*)d->still_rec;
 		aux.still_out = base + (size_t)(d->still_rec_half ^ 1) * d->still_rec_slots;
-		aux.still_in = d->still_rec_valid ? base + (size_t)d->still_rec_half * d->still_rec_slots : nullptr;
+		aux.still_in = d->facts->still_rec_valid ? base + (size_t)d->still_rec_half * d->still_rec_slots : nullptr;
 		aux.still_rows = d->desc.rows;
 	}
 	const void* src = d->state[0];
@@ -844,11 +834,10 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	else          { if (d->desc.dynamic_dt) HP_LAUNCH_K1B(1, false, 1); else HP_LAUNCH_K1B(0, false, 1); }
 #undef HP_LAUNCH_K1B
 #undef HP_LAUNCH_K1B2
-	d->pair_fused_next = bdy && followed;
-	d->m1_valid = bdy;
+	d->facts.pair_queued(bdy, followed);
 	HIP_TRY(hipGetLastError());
 	if (recs) d->still_rec_half ^= 1;
-	d->still_rec_valid = recs; d->still_rec_last = recs;
+	d->facts.pair_launched(recs); d->still_rec_last = recs;
 	if (sample) { HIP_TRY(hipEventRecord(d->timing_events[d->timing_used].second, d->stream)); d->timing_used++; }
 	// the pass wrote state k + 2 into the other buffer: that buffer IS the primary one from here on (two single iterations would
 	// have left the newest state in the primary buffer; the two buffers' edge rings are equal -- pair_eligible -- and so are their maxima)
@@ -856,9 +845,8 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	if (strip) {                                                          // every rank swaps: a neighbour's buffer b is the one it calls b now
 		std::swap(d->peer_state[0][0], d->peer_state[0][1]);
 		std::swap(d->peer_state[1][0], d->peer_state[1][1]);
-		d->ghost_valid = d->ghost_rows;                                   // the exchange happened inside the launch
 	}
-	d->other_stale = true;
+	d->facts.pair_ran(strip, d->ghost_rows);                              // (a strip: the exchange happened inside the launch)
 	d->single_streak = 0;
 	d->tail_done = false; d->fork_is_advance = false;
 	d->adv_fresh = d->desc.dynamic_dt ? 1 : 0;
@@ -877,38 +865,52 @@ static int run_pair(hp_domain* d, const bool strip = false, const bool followed 
 // quirk Q3): that buffer holds a state two iterations old after pairs -- bring it up to date with one device copy.
 static int repair_other_buffer(hp_domain* d)
 {
-	if (!d->other_stale) return HP_OK;
-	still_rec_forget(d);
+	if (!d->facts->other_stale) return HP_OK;
+	d->facts.buffers_written_outside();
 	// (the edge rings of the two buffers are equal whenever pairs have run: pair_eligible, hp_domain_upload_rows)
-	HIP_TRY(hipMemcpyAsync(d->state[d->use_alt ^ 1], d->state[d->use_alt], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync(d->state[d->facts->use_alt ^ 1], d->state[d->facts->use_alt], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
 	if (d->z_state) {                                                     // ... except where the last pair launch stamped a different value (PairAux)
 		if (d->desc.precision == 8)
-			hipLaunchKernelGGL((stamps_to_buffer<double>), dim3(1024), dim3(256), 0, d->stream, (State4<double>*)d->state[d->use_alt ^ 1],
+			hipLaunchKernelGGL((stamps_to_buffer<double>), dim3(1024), dim3(256), 0, d->stream, (State4<double>*)d->state[d->facts->use_alt ^ 1],
 			                   StampBufs<double>{(char*)d->z_state, d->haz_words}, d->pair_gen, d->cells);
 		else
-			hipLaunchKernelGGL((stamps_to_buffer<float>), dim3(1024), dim3(256), 0, d->stream, (State4<float>*)d->state[d->use_alt ^ 1],
+			hipLaunchKernelGGL((stamps_to_buffer<float>), dim3(1024), dim3(256), 0, d->stream, (State4<float>*)d->state[d->facts->use_alt ^ 1],
 			                   StampBufs<float>{(char*)d->z_state, d->haz_words}, d->pair_gen, d->cells);
 		HIP_TRY(hipGetLastError());
 	}
-	d->other_stale = false;
+	d->facts.other_made_current();
+	return HP_OK;
+}
+// What a checkpoint (hp_state_save) and the snapshot in front of a speculative batch (spec_begin) copy, queued on the domain's stream: both
+// state buffers, state[first] in front, the scalars, and the WHOLE slot block: running maximum, last maximum used (SLOT_SAVED), ring
+// maxima (SLOT_EDGE) -- round 2 kept the first four elements only, which since the slots moved 256 B apart no longer included the
+// remembered maximum
+static int snapshot_take(hp_domain* d, void* state, void* scalars, const int first)
+{
+	const size_t bytes = d->cells * 4 * d->esize;
+	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
+	HIP_TRY(hipMemcpyAsync(state, d->state[first], bytes, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync((char*)state + bytes, d->state[first ^ 1], bytes, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync(scalars, d->scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync((char*)scalars + sc_bytes, d->cfl_slot, CFL_SLOT_BYTES, hipMemcpyDeviceToDevice, d->stream));
 	return HP_OK;
 }
 
 int dispatch_begin(hp_domain* d)
 {
-	still_rec_forget(d);                                                  // (a single iteration writes the other buffer, its boundaries the current one)
+	d->facts.buffers_written_outside();                                   // (a single iteration writes the other buffer, its boundaries the current one)
 	// after iteration pairs the non-current buffer is out of date; K1 brings it up to date by itself (its FILL flag: every cell of the
 	// launch's rows is stored), any other kernel gets the device copy first
 	static const bool fill_enabled = !(std::getenv("HP_FILL_AFTER_PAIRS") && std::atoi(std::getenv("HP_FILL_AFTER_PAIRS")) == 0);
 	// (exact pairs: the device copy, then the stamps on top -- repair_other_buffer -- so that K1 needs no knowledge of them)
-	const bool fill = fill_enabled && d->other_stale && d->desc.scheme == HP_SCHEME_GODUNOV && d->desc.kernel != HP_KERNEL_BASIC && !(pair_exact(d) && d->z_state);
+	const bool fill = fill_enabled && d->facts->other_stale && d->desc.scheme == HP_SCHEME_GODUNOV && d->desc.kernel != HP_KERNEL_BASIC && !(pair_exact(d) && d->z_state);
 	if (!fill) { const int rc0 = repair_other_buffer(d); if (rc0 != HP_OK) return rc0; }
 	d->fill_now = fill;
 	const bool strict = d->desc.math_mode == HP_MATH_STRICT;
 	const int rc = d->desc.precision == 8 ? (strict ? step_begin_impl<double, true>(d) : step_begin_impl<double, false>(d))
 	                                      : (strict ? step_begin_impl<float, true>(d) : step_begin_impl<float, false>(d));
 	d->fill_now = false;
-	if (fill && rc == HP_OK) d->other_stale = false;
+	if (fill && rc == HP_OK) d->facts.other_made_current();
 	return rc;
 }
 
@@ -1103,7 +1105,7 @@ int hp_domain_create(const hp_domain_desc_t* desc, hp_domain_t** out)
 		delete d;
 		return fail(HP_ERR_INVALID, "ghost_rows must be 0, the scheme's stencil reach or twice that");
 	}
-	d->ghost_valid = d->ghost_rows;
+	d->facts.ghosts_exchanged(d->ghost_rows);
 	d->split_now = true;                                                  // (hp_step_begin: every iteration is followed by an exchange)
 	d->own_lo = (d->desc.row_offset > 0) ? d->ghost_rows : 0;
 	d->own_hi = d->desc.rows - ((d->desc.row_offset + d->desc.rows < d->desc.global_rows) ? d->ghost_rows : 0);
@@ -1204,8 +1206,8 @@ int hp_domain_upload(hp_domain_t* d, int which, const void* host, size_t bytes)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
-	still_rec_forget(d);                                                  // (state, bed or Manning: the records describe the old ones)
+	d->facts.boundaries_or_bed_changed();
+	d->facts.buffers_written_outside();                                   // (state, bed or Manning: the records describe the old ones)
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
 	if (d->in_step) return fail(HP_ERR_STATE, "upload between hp_step_begin and hp_step_end");
 	switch (which) {
@@ -1214,20 +1216,14 @@ int hp_domain_upload(hp_domain_t* d, int which, const void* host, size_t bytes)
 		// both ping-pong buffers get the same host array (CSchemeGodunov.cpp:1064-1065)
 		HIP_TRY(hipMemcpyAsync(d->state[0], host, bytes, hipMemcpyHostToDevice, d->stream));
 		HIP_TRY(hipMemcpyAsync(d->state[1], host, bytes, hipMemcpyHostToDevice, d->stream));
-		d->other_stale = false;
-		d->rings_differ = false;
 		d->tune_phase = 0;                                                // (a sample still in flight measured the state that has just been replaced)
-		d->use_alt = 0;                                                   // :1075
-		d->need_full_reduce = true;
-		d->edge_dirty = true;
-		d->ghost_valid = d->ghost_rows;                                   // the host uploads strips with all their ghost rows
+		d->facts.full_state_uploaded(d->ghost_rows);                      // (use_alt = 0: :1075)
 		HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
 		return HP_OK;
 	case HP_ARRAY_BED:
 		if (bytes != d->cells * d->esize) return fail(HP_ERR_INVALID, "bed size mismatch");
 		HIP_TRY(hipMemcpyAsync(d->bed, host, bytes, hipMemcpyHostToDevice, d->stream));
-		d->need_full_reduce = true;
-		d->edge_dirty = true;
+		d->facts.bed_uploaded();
 		return HP_OK;
 	case HP_ARRAY_MANNING:
 		if (bytes != d->cells * d->esize) return fail(HP_ERR_INVALID, "manning size mismatch");
@@ -1267,18 +1263,8 @@ int hp_state_save(hp_domain_t* d)
 	// configurations found 6 % of them replaying differently when only the next-source buffer was kept, round 3)
 	if (!d->saved_state) HIP_TRY(hipMalloc(&d->saved_state, 2 * bytes));
 	if (!d->saved_scalars) HIP_TRY(hipMalloc(&d->saved_scalars, sc_bytes + CFL_SLOT_BYTES));
-	HIP_TRY(hipMemcpyAsync(d->saved_state, d->state[d->use_alt], bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync((char*)d->saved_state + bytes, d->state[d->use_alt ^ 1], bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync(d->saved_scalars, d->scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
-	// the WHOLE slot block: running maximum, last maximum used (SLOT_SAVED), ring maxima (SLOT_EDGE) -- round 2 kept the first
-	// four elements only, which since the slots moved 256 B apart no longer included the remembered maximum
-	HIP_TRY(hipMemcpyAsync((char*)d->saved_scalars + sc_bytes, d->cfl_slot, CFL_SLOT_BYTES, hipMemcpyDeviceToDevice, d->stream));
-	d->saved_full_reduce = d->need_full_reduce;
-	d->saved_edge_dirty = d->edge_dirty;
-	d->saved_use_alt = d->use_alt;
-	d->saved_rings_differ = d->rings_differ;
-	d->saved_m1_valid = d->m1_valid;
-	d->saved_ghost_valid = d->ghost_valid;
+	if ((rc = snapshot_take(d, d->saved_state, d->saved_scalars, d->facts->use_alt)) != HP_OK) return rc;
+	d->facts.checkpoint_taken();
 	d->saved_valid = true;
 	if ((rc = peaks_save(d)) != HP_OK) return rc;
 	log_save(d, PROBES);
@@ -1292,14 +1278,14 @@ int hp_state_restore(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_restore between hp_step_begin and hp_step_end");
 	if (!d->saved_valid) return fail(HP_ERR_STATE, "hp_state_restore without a saved state");
-	still_rec_forget(d);
+	d->facts.buffers_written_outside();
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// both ping-pong buffers return to what EACH of them held (rollbackSimulation writes the saved next-source state into both,
 	// CSchemeGodunov.cpp:1496-1499, after which its cells with an all-dry neighbourhood no longer continue as the original run
 	// did), and so do the ping-pong phase and the remembered CFL maxima: the steps that follow repeat the original ones bit for bit
-	HIP_TRY(hipMemcpyAsync(d->state[d->saved_use_alt], d->saved_state, bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync(d->state[d->saved_use_alt ^ 1], (char*)d->saved_state + bytes, bytes, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync(d->state[d->facts.saved().use_alt], d->saved_state, bytes, hipMemcpyDeviceToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync(d->state[d->facts.saved().use_alt ^ 1], (char*)d->saved_state + bytes, bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->scalars, d->saved_scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
 	// (the slot block AROUND the sticky "a tail block gave up" word: a word raised since the checkpoint, and not yet seen by the host
 	// through hp_sync / hp_read_scalars, must survive the roll-back -- ADVICE r05)
@@ -1309,21 +1295,11 @@ int hp_state_restore(hp_domain_t* d)
 		HIP_TRY(hipMemcpyAsync(d->cfl_slot, from, lo, hipMemcpyDeviceToDevice, d->stream));
 		HIP_TRY(hipMemcpyAsync((char*)d->cfl_slot + hi, from + hi, CFL_SLOT_BYTES - hi, hipMemcpyDeviceToDevice, d->stream));
 	}
-	d->use_alt = d->saved_use_alt;
-	d->other_stale = false;                                               // (a checkpoint is taken with both buffers brought up to date)
-	d->rings_differ = d->saved_rings_differ;
-	d->rings_checked = false;
-	d->m1_valid = d->saved_m1_valid;                                      // (slot[SLOT_M1] has come back with the slot block -- unless a boundary or the
-	                                                                      // bed changed since the save: m1_forget)
+	d->facts.checkpoint_restored();
 	d->tune_phase = 0;                                                    // (another state: the exact mode's pairs-or-singles choice is measured anew -- a sample
 	                                                                      // still in flight measured the state that is being replaced: with samples every 128
 	                                                                      // iterations bench.py's restore found one in flight nearly every time and the timed
 	                                                                      // region ran on a choice made for the pre-warmed flood)
-	d->pair_fused_next = false;                                           // (a checkpoint is taken between batches: nothing fused is in the buffer)
-	d->ghost_valid = d->saved_ghost_valid;
-	// a bed or state upload between save and restore has left its own marks: they stay
-	d->need_full_reduce = d->need_full_reduce || d->saved_full_reduce;
-	d->edge_dirty = d->edge_dirty || d->saved_edge_dirty;
 	d->fork_is_advance = false;
 	if ((rc = peaks_restore(d)) != HP_OK) return rc;
 	log_restore(d, PROBES);
@@ -1340,7 +1316,7 @@ int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int6
 	const size_t per_row = (size_t)d->desc.cols * d->esize * (which == HP_ARRAY_STATE ? 4 : 1);
 	const void* base;
 	switch (which) {
-	case HP_ARRAY_STATE:   base = d->state[d->use_alt]; break;            // getNextCellSourceBuffer (:1705-1715)
+	case HP_ARRAY_STATE:   base = d->state[d->facts->use_alt]; break;     // getNextCellSourceBuffer (:1705-1715)
 	case HP_ARRAY_BED:     base = d->bed; break;
 	case HP_ARRAY_MANNING: base = d->manning; break;
 	default: return fail(HP_ERR_INVALID, "unknown array id");
@@ -1354,20 +1330,17 @@ int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
-	still_rec_forget(d);
+	d->facts.time_control_changed();                                     // (not boundaries_or_bed_changed: hp_facts.hpp, ODD)
+	d->facts.buffers_written_outside();
 	if (!host) return fail(HP_ERR_INVALID, "host == NULL");
 	if ((rc = check_rows(d, row0, nrows)) != HP_OK) return rc;
 	const size_t per_row = (size_t)d->desc.cols * d->esize * 4;
 	// queueWritePartial goes to the CURRENT buffer only: the other one keeps what it held -- after iteration pairs it has to be
 	// brought up to date first, or the rows written now would reach it with the next single iteration's FILL
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;
-	HIP_TRY(hipMemcpyAsync((char*)d->state[d->use_alt] + (size_t)row0 * per_row, host, (size_t)nrows * per_row,
+	HIP_TRY(hipMemcpyAsync((char*)d->state[d->facts->use_alt] + (size_t)row0 * per_row, host, (size_t)nrows * per_row,
 	                       hipMemcpyHostToDevice, d->stream));
-	d->need_full_reduce = true;
-	d->edge_dirty = true;
-	d->rings_differ = true;
-	d->rings_checked = false;
+	d->facts.rows_uploaded();
 	return HP_OK;
 }
 
@@ -1376,7 +1349,7 @@ int hp_boundary_add_uniform(hp_domain_t* d, int definition, const void* series, 
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
+	d->facts.boundaries_or_bed_changed();
 	if (!series || entries == 0 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad uniform boundary");
 	if (definition != HP_UNIFORM_RAIN_INTENSITY && definition != HP_UNIFORM_LOSS_RATE)
 		return fail(HP_ERR_INVALID, "unknown uniform boundary definition");
@@ -1395,7 +1368,7 @@ int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, u
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
+	d->facts.boundaries_or_bed_changed();
 	if (!grids || entries == 0 || grid_rows == 0 || grid_cols == 0 || !(resolution > 0) || !(interval > 0))
 		return fail(HP_ERR_INVALID, "bad gridded boundary");
 	{
@@ -1423,7 +1396,7 @@ int hp_boundary_add_cell(hp_domain_t* d, int depth_definition, int discharge_def
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
+	d->facts.boundaries_or_bed_changed();
 	if (!cells || count == 0 || !series || entries < 2 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad cell boundary");
 	if (depth_definition < 0 || depth_definition > 3 || discharge_definition < 0 || discharge_definition > 3)
 		return fail(HP_ERR_INVALID, "unknown cell boundary definition");
@@ -1457,7 +1430,7 @@ int hp_boundary_clear(hp_domain_t* d)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	m1_forget(d);                                                        // (pairs with area boundaries start cold: pair_cold_start; a checkpoint's figure goes too)
+	d->facts.boundaries_or_bed_changed();
 	HIP_TRY(hipStreamSynchronize(d->stream));
 	for (auto& b : d->bdy) { hipFree(b.data); hipFree(b.cells); }
 	d->bdy.clear();
@@ -1476,7 +1449,7 @@ int hp_set_target_time(hp_domain_t* d, double t)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	d->facts.time_control_changed();
 	return d->desc.precision == 8 ? set_scalar_field<double>(d, offsetof(Scalars<double>, t_sync), t)
 	                              : set_scalar_field<float>(d, offsetof(Scalars<float>, t_sync), t);
 }
@@ -1485,7 +1458,7 @@ int hp_set_time(hp_domain_t* d, double t)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	d->facts.time_control_changed();
 	return d->desc.precision == 8 ? set_scalar_field<double>(d, offsetof(Scalars<double>, t), t)
 	                              : set_scalar_field<float>(d, offsetof(Scalars<float>, t), t);
 }
@@ -1494,7 +1467,7 @@ int hp_force_timestep(hp_domain_t* d, double dt)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	d->facts.time_control_changed();
 	return d->desc.precision == 8 ? set_scalar_field<double>(d, offsetof(Scalars<double>, dt), dt)
 	                              : set_scalar_field<float>(d, offsetof(Scalars<float>, dt), dt);
 }
@@ -1513,7 +1486,7 @@ int hp_update_timestep(hp_domain_t* d)
 {
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
-	d->m1_valid = false;                                                 // (pairs with area boundaries start cold: pair_cold_start)
+	d->facts.time_control_changed();
 	if (d->in_step) return fail(HP_ERR_STATE, "inside a split step");
 	if (d->desc.dynamic_dt && d->desc.global_rows != d->desc.rows)
 		return fail(HP_ERR_UNSUPPORTED, "hp_update_timestep on a row strip: the maximum must be all-reduced across "
@@ -1521,7 +1494,7 @@ int hp_update_timestep(hp_domain_t* d)
 	// tst_Reduce reads the primary buffer (arg wiring CSchemeGodunov.cpp:922, :927), then tst_UpdateTimestep.  MUSCL-Hancock
 	// has ONE state buffer in the reference, updated in place -- its primary buffer is always the current state, which here
 	// is whichever ping-pong buffer the next iteration reads (found by the fuzz's update-timestep calls between batches)
-	const void* priced = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? d->state[d->use_alt] : d->state[0];
+	const void* priced = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? d->state[d->facts->use_alt] : d->state[0];
 	if (d->desc.precision == 8) {
 		if (d->desc.dynamic_dt && (rc = launch_reduce<double>(d, priced, d->own_lo, d->own_hi)) != HP_OK) return rc;
 		hipLaunchKernelGGL((advance_time<true, double>), dim3(1), dim3(64), 0, d->stream, make_params<double>(d),
@@ -1546,7 +1519,7 @@ int hp_step_begin(hp_domain_t* d)
 		                                "(two reaches of ghost rows are hp_strip_step_batch's)");
 	d->split_now = true;
 	d->fork_is_advance = fork_ready;
-	d->m1_valid = false;                           // (a single iteration prices one maximum, as in run_single: the next pair starts cold)
+	d->facts.single_begins();
 	if ((rc = dispatch_begin(d)) != HP_OK) return rc;
 	d->in_step = true;
 	return HP_OK;
@@ -1612,13 +1585,9 @@ int spec_begin(hp_domain* d)
 	if (!d->spec_state) HIP_TRY(hipMalloc(&d->spec_state, 2 * bytes));
 	if (!d->spec_scalars) HIP_TRY(hipMalloc(&d->spec_scalars, sc_bytes + CFL_SLOT_BYTES));
 	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_SPEC * d->esize, 0, d->esize, d->stream));
-	HIP_TRY(hipMemcpyAsync(d->spec_state, d->state[0], bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync((char*)d->spec_state + bytes, d->state[1], bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync(d->spec_scalars, d->scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
-	HIP_TRY(hipMemcpyAsync((char*)d->spec_scalars + sc_bytes, d->cfl_slot, CFL_SLOT_BYTES, hipMemcpyDeviceToDevice, d->stream));
-	d->spec_host.use_alt = d->use_alt; d->spec_host.adv_fresh = d->adv_fresh;
-	d->spec_host.need_full_reduce = d->need_full_reduce; d->spec_host.edge_dirty = d->edge_dirty;
-	d->spec_host.ghost_valid = d->ghost_valid;
+	{ const int rc = snapshot_take(d, d->spec_state, d->spec_scalars, 0); if (rc != HP_OK) return rc; }
+	d->facts.spec_taken();
+	d->spec_host.adv_fresh = d->adv_fresh;
 	d->spec_host.cells_calculated = d->cells_calculated; d->spec_host.iterations = d->iterations;
 	d->spec_now = true;
 	return HP_OK;
@@ -1662,7 +1631,7 @@ int run_single(hp_domain* d, const bool followed)
 	// (K1 FUSED) every iteration but the last carries its successor's rain / loss: between batches the buffers are
 	// what the reference's are -- a download never sees rain of an iteration that has not begun
 	d->fuse_next = followed;
-	d->m1_valid = false;                           // (a single iteration prices one maximum: the next pair starts cold)
+	d->facts.single_begins();
 	d->tail_allowed = true;                        // nothing is queued between the flux launch and the advance in this loop
 	int rc = dispatch_begin(d);
 	d->tail_allowed = false;
@@ -1675,12 +1644,12 @@ int run_iterations(hp_domain* d, uint32_t n_iterations)
 	const bool tune = tuner_on(d);
 	if (tune && (rc = tuner_poll(d)) != HP_OK) return rc;
 	// (partial uploads since the last look: the rings are compared once, before the first pair_eligible -- blocks)
-	if (d->rings_differ && !d->rings_checked && n_iterations >= 2 && pairs_possible(d) && (rc = rings_really_differ(d)) != HP_OK) return rc;
+	if (d->facts->rings_differ && !d->facts->rings_checked && n_iterations >= 2 && pairs_possible(d) && (rc = rings_really_differ(d)) != HP_OK) return rc;
 	for (uint32_t i = 0; i < n_iterations; ++i) {
 		if (tune && d->tune_phase != 0 && (i & 15u) == 15u && (rc = tuner_poll(d)) != HP_OK) return rc;   // (two event queries: host time, behind the queue)
 		// (STRICT) a sample: three pairs, then six single iterations -- the first pair and the first two single iterations warm the
 		// kernel's code and are not timed, the rest are bracketed by events
-		if (tune && d->tune_phase == 0 && i + 12 <= n_iterations && !d->rings_differ && pair_eligible(d)) {
+		if (tune && d->tune_phase == 0 && i + 12 <= n_iterations && !d->facts->rings_differ && pair_eligible(d)) {
 			for (hipEvent_t& e : d->tune_ev) if (!e) HIP_TRY(hipEventCreate(&e));
 			if ((rc = pair_stamps_alloc(d)) != HP_OK) return rc;           // (the first pair's allocation and its memset are not the pair's price)
 			rc = run_pair(d, false, true);
@@ -1723,14 +1692,13 @@ int spec_resolve(hp_domain* d)
 	d->spec_replays++;
 	log_line(HP_LOG_INFORMATION, "a speculative STRICT batch of " + std::to_string(n) + " iterations is re-run with the plain divisions");
 	const size_t bytes = d->cells * 4 * d->esize, sc_bytes = sizeof(Scalars<double>);
-	still_rec_forget(d);
+	d->facts.buffers_written_outside();
 	HIP_TRY(hipMemcpyAsync(d->state[0], d->spec_state, bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->state[1], (char*)d->spec_state + bytes, bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->scalars, d->spec_scalars, sc_bytes, hipMemcpyDeviceToDevice, d->stream));
 	HIP_TRY(hipMemcpyAsync(d->cfl_slot, (char*)d->spec_scalars + sc_bytes, CFL_SLOT_BYTES, hipMemcpyDeviceToDevice, d->stream));
-	d->use_alt = d->spec_host.use_alt; d->adv_fresh = d->spec_host.adv_fresh;
-	d->need_full_reduce = d->spec_host.need_full_reduce; d->edge_dirty = d->spec_host.edge_dirty;
-	d->ghost_valid = d->spec_host.ghost_valid;
+	d->facts.spec_replayed();
+	d->adv_fresh = d->spec_host.adv_fresh;
 	d->cells_calculated = d->spec_host.cells_calculated; d->iterations = d->spec_host.iterations;
 	d->fork_is_advance = false;
 	return run_iterations(d, n);
@@ -1861,10 +1829,10 @@ int hp_device_ptr(hp_domain_t* d, int which, void** ptr)
 {
 	if (!d || !ptr) return fail(HP_ERR_INVALID, "null argument");
 	d->fork_is_advance = false;          // the caller may queue work on these buffers behind the last advance_time
-	if (which == HP_PTR_STATE_NEXT_SRC || which == HP_PTR_STATE_OTHER || which == HP_PTR_BED) still_rec_forget(d);   // ... or write into them
+	if (which == HP_PTR_STATE_NEXT_SRC || which == HP_PTR_STATE_OTHER || which == HP_PTR_BED) d->facts.buffers_written_outside();  // ... or write into them
 	switch (which) {
-	case HP_PTR_STATE_NEXT_SRC: *ptr = d->state[d->use_alt]; return HP_OK;
-	case HP_PTR_STATE_OTHER:    *ptr = d->state[d->use_alt ^ 1]; return HP_OK;
+	case HP_PTR_STATE_NEXT_SRC: *ptr = d->state[d->facts->use_alt]; return HP_OK;
+	case HP_PTR_STATE_OTHER:    *ptr = d->state[d->facts->use_alt ^ 1]; return HP_OK;
 	case HP_PTR_BED:            *ptr = d->bed; return HP_OK;
 	case HP_PTR_MANNING:        *ptr = d->manning; return HP_OK;
 	case HP_PTR_CFL_MAX:        *ptr = d->cfl_slot; return HP_OK;
@@ -1923,7 +1891,7 @@ int strip_halo_exchange(hp_domain* d)
 	const long G = d->ghost_rows, rows = d->desc.rows;
 	const size_t row_elems = (size_t)d->desc.cols * 4, count = (size_t)G * row_elems;
 	const ncclDataType_t type = d->desc.precision == 8 ? ncclDouble : ncclFloat;
-	char* state = (char*)d->state[d->use_alt ^ 1];                    // the buffer the iteration in flight writes
+	char* state = (char*)d->state[d->facts->use_alt ^ 1];             // the buffer the iteration in flight writes
 	const size_t row_bytes = row_elems * d->esize;
 	const bool south = d->comm_rank > 0, north = d->comm_rank < d->comm_world - 1;
 	// the rows the neighbours need come from the halo part of the step: the transfer is ordered after that stream only
@@ -1966,7 +1934,7 @@ int strip_allreduce_max(hp_domain* d, bool first_of_batch)
 	}
 	const bool q1 = (d->desc.quirks & HP_QUIRK_CFL_READS_PRIMARY) != 0, muscl = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK;
 	const bool basic = d->desc.kernel == HP_KERNEL_BASIC && d->desc.scheme == HP_SCHEME_GODUNOV;
-	const bool dst_is_primary = d->use_alt == 1;
+	const bool dst_is_primary = d->facts->use_alt == 1;
 	const bool everyone = muscl || !q1 || dst_is_primary || basic || d->strip_any_bdy || (first_of_batch && d->strip_any_full);
 	if (!everyone) {
 		if (d->adv_fresh) return fail(HP_ERR_STATE, "a strip priced a new maximum on an iteration the other ranks do not reduce "
@@ -1994,7 +1962,7 @@ int strip_allreduce_max(hp_domain* d, bool first_of_batch)
 int strip_handshake(hp_domain* d)
 {
 	d->strip_any_bdy = !d->bdy.empty() && d->desc.scheme != HP_SCHEME_MUSCL_HANCOCK;
-	d->strip_any_full = d->need_full_reduce;
+	d->strip_any_full = d->facts->need_full_reduce;
 	d->strip_pairs = false;
 	if (d->comm_world <= 1) return HP_OK;
 	// (element 0 also carries the mailboxes' sticky error word of THIS rank as a value above 1: the all-reduce then tells every
@@ -2002,8 +1970,8 @@ int strip_handshake(hp_domain* d)
 	const bool broken = peer_error_check(d) != HP_OK;
 	// (element 0: 3 = this rank's exchange is broken, 1 = it has boundary conditions, 0.5 = it has none but cannot run iteration
 	// pairs, 0 = it can: the maximum over the ranks says what ALL of them may do)
-	const double mine[8] = {broken ? 3.0 : (d->strip_any_bdy ? 1.0 : (strip_pairs_possible_here(d) ? 0.0 : 0.5)), d->strip_any_full ? 1.0 : 0.0, (double)d->use_alt, -(double)d->use_alt,
-	                        (double)d->ghost_valid, -(double)d->ghost_valid, (double)d->ghost_rows, -(double)d->ghost_rows};
+	const double mine[8] = {broken ? 3.0 : (d->strip_any_bdy ? 1.0 : (strip_pairs_possible_here(d) ? 0.0 : 0.5)), d->strip_any_full ? 1.0 : 0.0, (double)d->facts->use_alt, -(double)d->facts->use_alt,
+	                        (double)d->facts->ghost_valid, -(double)d->facts->ghost_valid, (double)d->ghost_rows, -(double)d->ghost_rows};
 	double all[8];
 	char* slot = (char*)d->cfl_slot + (size_t)SLOT_HANDSHAKE * d->esize;
 	const ncclDataType_t type = d->desc.precision == 8 ? ncclDouble : ncclFloat;
@@ -2387,20 +2355,20 @@ int hp_strip_step_batch(hp_domain_t* d, uint32_t n_iterations)
 	// until the first iteration that prices on every rank has run: a decision every rank takes from the same, handshaken facts)
 	bool full_pending = d->strip_any_full;
 	for (uint32_t i = 0; i < n_iterations; ++i) {
-		if (i + 2 <= n_iterations && d->strip_pairs && !full_pending && d->use_alt == 0 && d->ghost_valid == d->ghost_rows) {
+		if (i + 2 <= n_iterations && d->strip_pairs && !full_pending && d->facts.strip_pair_ready(d->ghost_rows)) {
 			rc = run_pair(d, true);
 			if (rc != HP_OK) return rc == HP_ERR_STATE ? fail(HP_ERR_STATE, "a strip could not launch an iteration pair the ranks had agreed on") : rc;
 			++i;
 			d->fork_is_advance = false;
 			continue;
 		}
-		if (d->use_alt == 1) full_pending = false;    // this iteration writes the primary buffer: every rank prices it
+		if (d->facts->use_alt == 1) full_pending = false;  // this iteration writes the primary buffer: every rank prices it
 		d->fuse_next = i + 1 < n_iterations;          // as hp_step_batch: the rows sent to the neighbours carry the rain too
-		if (d->ghost_valid < g) return fail(HP_ERR_STATE, "ghost rows exhausted");
+		if (d->facts->ghost_valid < g) return fail(HP_ERR_STATE, "ghost rows exhausted");
 		// an iteration consumes g layers of ghost rows; when fewer than g are left afterwards, the new state's rows are
 		// exchanged (ghost_rows = g: every iteration; 2g: every second one, and only those iterations are split into a
 		// halo and an interior launch)
-		const bool exchange = d->ghost_valid - g < g;
+		const bool exchange = d->facts->ghost_valid - g < g;
 		d->split_now = exchange && !d->peer_direct;   // (rows that travel inside the advance kernel need no launch of their own)
 		d->push_now = exchange && d->peer_direct;     // ... and leave with the advance kernel, or with the flux launch's tail block
 		d->strip_first = i == 0;
@@ -2410,9 +2378,9 @@ int hp_strip_step_batch(hp_domain_t* d, uint32_t n_iterations)
 		if (rc != HP_OK) return rc;
 		if (exchange) {
 			if (!d->peer_direct && (rc = strip_halo_exchange(d)) != HP_OK) return rc;
-			d->ghost_valid = d->ghost_rows;
+			d->facts.ghosts_exchanged(d->ghost_rows);
 		} else {
-			d->ghost_valid -= g;
+			d->facts.ghosts_consumed(g);
 		}
 		if ((rc = strip_allreduce_max(d, i == 0)) != HP_OK) return rc;
 		if ((rc = dispatch_end(d)) != HP_OK) return rc;
@@ -2439,7 +2407,7 @@ int hp_strip_update_timestep(hp_domain_t* d)
 	// rank's host has arrived here -- the library's all-reduce of the handshake waits without a limit, a strip still busy with
 	// a long upload is no error
 	if (d->peer_agreed && d->comm_world > 1 && (rc = strip_handshake(d)) != HP_OK) return rc;
-	const void* priced = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? d->state[d->use_alt] : d->state[0];     // (as hp_update_timestep)
+	const void* priced = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? d->state[d->facts->use_alt] : d->state[0];  // (as hp_update_timestep)
 	if (d->desc.precision == 8) {
 		if (d->desc.dynamic_dt && (rc = launch_reduce<double>(d, priced, d->own_lo, d->own_hi)) != HP_OK) return rc;
 	} else {

@@ -333,7 +333,7 @@ int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_b
 		}
 		const dim3 blocks((unsigned)std::min<size_t>((n + 255) / 256, 8192));
 		with_real(d, [&](auto zero) { using T = decltype(zero);
-			const State4<T>* state = (const State4<T>*)d->state[d->use_alt];      // what hp_domain_download(HP_ARRAY_STATE) reads
+			const State4<T>* state = (const State4<T>*)d->state[d->facts->use_alt];      // what hp_domain_download(HP_ARRAY_STATE) reads
 			if (element_bytes == 8) hipLaunchKernelGGL((derive_rasters<T, double>), blocks, dim3(256), 0, d->stream, state, (const T*)d->bed, first, n, d->desc.dx, t);
 			else hipLaunchKernelGGL((derive_rasters<T, float>), blocks, dim3(256), 0, d->stream, state, (const T*)d->bed, first, n, d->desc.dx, t);
 		});
@@ -362,7 +362,7 @@ int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats
 	const int blocks = (int)std::min<size_t>((n + 255) / 256, STATS_MAX_BLOCKS);
 	StatsPart* partial = (StatsPart*)d->out.stats;
 	with_real(d, [&](auto zero) { using T = decltype(zero);
-		hipLaunchKernelGGL((domain_stats<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed, first, n, partial);
+		hipLaunchKernelGGL((domain_stats<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed, first, n, partial);
 	});
 	HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(domain_stats_fold, dim3(1), dim3(256), 0, d->stream, partial, blocks, partial + STATS_MAX_BLOCKS);
@@ -429,7 +429,7 @@ int hp_peaks_sample(hp_domain_t* d)
 	const unsigned sample = (unsigned)(d->peaks.samples & 1u);          // picks the time slot; `first`: the first sample since enable / reset
 	const int first = d->peaks.samples == 0;
 	with_real(d, [&](auto zero) { using T = decltype(zero);              // (the buffer hp_domain_download(HP_ARRAY_STATE) reads)
-		hipLaunchKernelGGL((track_peaks<T>), dim3(stream_blocks(d->cells)), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		hipLaunchKernelGGL((track_peaks<T>), dim3(stream_blocks(d->cells)), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed,
 		                   (const Scalars<T>*)d->scalars, peaks_block(d), sample, first, d->cells, t);
 	});
 	HIP_TRY(hipGetLastError());
@@ -554,7 +554,7 @@ int hp_probes_sample(hp_domain_t* d)
 	// the buffer hp_domain_download(HP_ARRAY_STATE) reads
 	with_real(d, [&](auto zero) {
 		using T = decltype(zero);
-		hipLaunchKernelGGL((record_probes<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		hipLaunchKernelGGL((record_probes<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed,
 		                   (const Scalars<T>*)d->scalars, p, (double*)g.records, (unsigned long long)g.samples, (unsigned long long)g.stride, d->desc.dx);
 	});
 	HIP_TRY(hipGetLastError());
@@ -603,7 +603,7 @@ int hp_zones_sample(hp_domain_t* d)
 	const size_t waves = (size_t)blocks * (256 / 64);
 	const size_t per_wave = ((n + waves - 1) / waves + 63) / 64 * 64;
 	with_real(d, [&](auto zero) { using T = decltype(zero);              // (the buffer hp_domain_download(HP_ARRAY_STATE) reads)
-		hipLaunchKernelGGL((record_zones<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->use_alt], (const T*)d->bed,
+		hipLaunchKernelGGL((record_zones<T>), dim3(blocks), dim3(256), 0, d->stream, (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed,
 		                   (const unsigned short*)g.input, (const Scalars<T>*)d->scalars, rec, n, per_wave, d->zones.flood_depth);
 	});
 	HIP_TRY(hipGetLastError());

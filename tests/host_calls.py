@@ -1,7 +1,7 @@
 """Random host-call sequences and their oracle twin (shared by host_calls_worker.py, test_gpu_host_calls.py and test_host_calls_cpu.py).
 
 The engine's correctness between launches rests on host-side flags (m1_valid, other_stale, use_alt, rings_differ, need_full_reduce,
-spec_now ...) that every entry point sets or clears by hand.  `make_sequence(seed, leg)` draws a small configuration and 8-20 host
+spec_now ...) that every entry point changes (most of them through the events of csrc/hp_facts.hpp).  `make_sequence(seed, leg)` draws a small configuration and 8-20 host
 calls in any order -- batches on both sides of SPEC_MIN and of the tuner's 12, split steps, time-control calls, full / partial /
 block-wise state uploads, bed and Manning uploads, boundaries added and cleared mid-run, checkpoints with anything in between,
 observer samples, downloads -- and `execute(seq, sim)` runs them on anything with the small surface of `EngineSim` / `OracleTwin`.

@@ -1,7 +1,8 @@
 """Mixed host-call sequences with iteration pairs forced on (tests/host_calls.py draws them, tests/host_calls_worker.py runs them).
 
-The engine's state between launches is a dozen host-side flags that every entry point sets or clears by hand; every finding of the
-round-6 review was a call sequence that left one of them wrong.  Three fuzz legs of 120 seeds each, in chunks of 30 per
+The engine's state between launches is ten host-side facts that the entry points change by naming what happened to the device
+(csrc/hp_facts.hpp, pinned event by event in test_facts.py); every finding of the round-6 review was a call sequence that
+left one of them wrong, when each entry point still set and cleared them by hand.  Three fuzz legs of 120 seeds each, in chunks of 30 per
 worker process, mix everything the host can call with HP_TWO_STEP=1, and four hand-written regressions name the findings:
 
 * STRICT == the oracle, bit for bit (state at every download, time, timestep, hydrological time, counters), pairs forced on;
