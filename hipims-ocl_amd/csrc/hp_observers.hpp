@@ -1,4 +1,4 @@
-// hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp), the peak tracker
+// hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp, hp_overview.hpp), the peak tracker
 // (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
 // (*_save, *_restore, *_destroy).  The two recorders share one record log (log_*): their own entry points keep the argument
@@ -20,6 +20,7 @@ static_assert(sizeof(hp_peaks_desc_t) == 16, "hp_peaks_desc_t layout");
 static_assert(sizeof(hp_probes_desc_t) == 64, "hp_probes_desc_t layout");
 static_assert(sizeof(hp_zones_desc_t) == 32, "hp_zones_desc_t layout");
 static_assert(ZONE_WORDS == HP_ZONE_WORDS, "hp_zones.hpp and hipims_mi.h disagree");
+static_assert(AGG_MAX == HP_AGG_MAX && AGG_MIN == HP_AGG_MIN && AGG_COUNT == HP_AGG_COUNT && AGG_KINDS == HP_AGG_KINDS && OVERVIEW_PAIRS == 27, "hp_overview.hpp and hipims_mi.h disagree");
 
 // f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
 template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }
@@ -96,6 +97,16 @@ int read_back_blocked(hp_domain* d, const char* who, int count, size_t esize, vo
 			                       hipMemcpyDeviceToHost, d->stream));
 	}
 	return HP_OK;
+}
+
+// ---- the output stage's reduced form: the block grid of a row range (hp_overview_shape; pure arithmetic) ----
+constexpr int OVERVIEW_FACTOR_MAX = 4096;
+inline void overview_shape(const hp_domain* d, const int factor, const int64_t row0, const int64_t nrows, int64_t* first_block_row, int64_t* block_rows, int64_t* block_cols)
+{
+	const int64_t lo = d->desc.row_offset + row0;                              // global row of the first one
+	*first_block_row = lo / factor;
+	*block_rows = nrows == 0 ? 0 : (lo + nrows - 1) / factor - *first_block_row + 1;
+	*block_cols = (d->desc.cols + factor - 1) / factor;
 }
 
 // ---- the output stage ----
@@ -374,6 +385,96 @@ int hp_domain_stats(hp_domain_t* d, int64_t row0, int64_t nrows, hp_domain_stats
 	out->volume = d->desc.dx * d->desc.dx * s.sum;
 	if (s.depth_cell != ~0ull) { out->max_depth = s.max_depth; out->max_depth_cell = s.depth_cell; }
 	if (s.speed_cell != ~0ull) { out->max_speed = s.max_speed; out->max_speed_cell = s.speed_cell; }
+	return HP_OK;
+}
+
+// ---- the output stage's reduced form (hp_overview.hpp) ----
+int hp_overview_shape(hp_domain_t* d, int factor, int64_t row0, int64_t nrows, int64_t* first_block_row, int64_t* block_rows, int64_t* block_cols)
+{
+	if (!first_block_row || !block_rows || !block_cols) return fail(HP_ERR_INVALID, "hp_overview_shape: an output pointer == NULL");
+	if (factor < 1 || factor > OVERVIEW_FACTOR_MAX) return fail(HP_ERR_INVALID, "hp_overview_shape: factor outside 1..4096");
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	overview_shape(d, factor, row0, nrows, first_block_row, block_rows, block_cols);
+	return HP_OK;
+}
+
+int hp_domain_overview(hp_domain_t* d, const int* values, const int* aggregates, int count, int factor, int element_bytes, void* const* rasters,
+                       int64_t row0, int64_t nrows)
+{
+	// argument checks first, as in hp_domain_derive: none of them touches the device, and those that do not need the domain come before it
+	const std::string who = "hp_domain_overview";
+	if (count < 1 || count > OVERVIEW_PAIRS) return fail(HP_ERR_INVALID, who + ": count outside 1..27");
+	if (!values || !aggregates || !rasters) return fail(HP_ERR_INVALID, who + ": values / aggregates / rasters == NULL");
+	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, who + ": element_bytes must be 4 or 8");
+	if (factor < 1 || factor > OVERVIEW_FACTOR_MAX) return fail(HP_ERR_INVALID, who + ": factor outside 1..4096");
+	OverviewPlan plan;
+	std::memset(plan.slot, -1, sizeof plan.slot);
+	plan.values = 0;
+	unsigned long long kinds = 0;
+	for (int k = 0; k < count; ++k) {
+		if (values[k] < 0 || values[k] >= HP_OUT_COUNT) return fail(HP_ERR_INVALID, who + ": unknown value " + std::to_string(values[k]));
+		if (aggregates[k] < 0 || aggregates[k] >= HP_AGG_KINDS) return fail(HP_ERR_INVALID, who + ": unknown aggregate " + std::to_string(aggregates[k]));
+		if (plan.slot[values[k]][aggregates[k]] >= 0)
+			return fail(HP_ERR_INVALID, who + ": pair (" + std::to_string(values[k]) + ", " + std::to_string(aggregates[k]) + ") listed twice");
+		if (!rasters[k]) return fail(HP_ERR_INVALID, who + ": rasters[" + std::to_string(k) + "] == NULL");
+		plan.slot[values[k]][aggregates[k]] = (signed char)k;
+		plan.values |= 1u << values[k];
+		kinds |= (unsigned long long)aggregates[k] << (2 * k);
+	}
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	if (nrows == 0) return HP_OK;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	int64_t first_block_row, block_rows, block_cols;
+	overview_shape(d, factor, row0, nrows, &first_block_row, &block_rows, &block_cols);
+	// Scratch of a block row: its accumulator words, pair after pair, and behind them the elements that go to the host.  A request
+	// that needs more than the cap is worked through in runs of whole block rows -- cut at multiples of `factor` in GLOBAL rows, so
+	// no block is shared between two runs -- queued one after the other like hp_domain_derive's blocks of rows.
+	const size_t esize = (size_t)element_bytes, brow_bytes = (size_t)block_cols * (size_t)count * (8 + esize);
+	const int64_t run_rows = std::max<int64_t>(1, std::min<int64_t>(block_rows, (int64_t)(OUT_SCRATCH_CAP / brow_bytes)));
+	if ((rc = out_scratch_reserve(d, (size_t)run_rows * brow_bytes, who)) != HP_OK) return rc;
+	OverviewGeom g = {};
+	g.cols = d->desc.cols;
+	g.row_offset = d->desc.row_offset;
+	g.factor = factor;
+	g.block_cols = block_cols;
+	g.col_groups = (g.cols + 255) / 256;
+	g.resolution = d->desc.dx;
+	const long long global_lo = d->desc.row_offset + row0, global_hi = global_lo + nrows;
+	for (int64_t b = 0; b < block_rows; b += run_rows) {
+		const long long rows_now = std::min<int64_t>(run_rows, block_rows - b);
+		g.by0 = first_block_row + b;
+		g.g_lo = std::max<long long>(global_lo, g.by0 * factor);
+		g.g_hi = std::min<long long>(global_hi, (g.by0 + rows_now) * factor);
+		g.blocks = rows_now * block_cols;
+		// bands of at most 32 rows, shorter ones while the launch would otherwise leave most of the device idle (the result does
+		// not depend on the choice)
+		g.band = std::min<long long>(factor, 32);
+		const auto items = [&](const long long band) { return rows_now * ((factor + band - 1) / band) * g.col_groups; };
+		while (g.band > 4 && items(g.band) < 2048) g.band = (g.band + 1) / 2;
+		g.nsub = (factor + g.band - 1) / g.band;
+		g.items = items(g.band);
+		const size_t words = (size_t)count * (size_t)g.blocks;
+		unsigned long long* acc = (unsigned long long*)d->out.scratch;
+		char* out = (char*)d->out.scratch + words * 8;
+		HIP_TRY(hipMemsetAsync(acc, 0, words * 8, d->stream));                   // "no cell yet" of all three aggregates
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			hipLaunchKernelGGL((overview_blocks<T>), dim3((unsigned)std::min<long long>(g.items, 2048)), dim3(256), 0, d->stream,
+			                   (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed, g, acc, plan);      // what hp_domain_download(HP_ARRAY_STATE) reads
+		});
+		HIP_TRY(hipGetLastError());
+		const dim3 finish((unsigned)std::min<size_t>(((size_t)g.blocks + 255) / 256, 1024), (unsigned)count);
+		if (element_bytes == 8) hipLaunchKernelGGL((overview_finish<double>), finish, dim3(256), 0, d->stream, acc, (double*)out, (size_t)g.blocks, kinds);
+		else hipLaunchKernelGGL((overview_finish<float>), finish, dim3(256), 0, d->stream, acc, (float*)out, (size_t)g.blocks, kinds);
+		HIP_TRY(hipGetLastError());
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)b * (size_t)block_cols * esize, out + (size_t)k * (size_t)g.blocks * esize,
+			                       (size_t)g.blocks * esize, hipMemcpyDeviceToHost, d->stream));
+	}
 	return HP_OK;
 }
 

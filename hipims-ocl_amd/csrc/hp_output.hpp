@@ -5,6 +5,7 @@
 // root, compare), so the rasters equal the host derivation (frontend.derive_output) bit for bit.
 #pragma once
 #include "hp_math.hpp"
+#include <type_traits>
 
 namespace hp {
 
@@ -18,6 +19,74 @@ struct DeriveTargets {
 	void*    raster[OUT_VALUES];                  // [value] -> first element of that value's raster for this launch's first cell
 	unsigned mask;                                // bit v: raster[v] is written (the same in every lane: a scalar branch per value)
 };
+
+// -------------------------------------------------------------------------------------------------
+// The per-cell value of every HP_OUT_* code in fp64, before any rounding: the one definition derive_rasters (which stores it)
+// and overview_blocks (hp_overview.hpp, which aggregates it over blocks) share.  out_cell widens the cell and forms what the
+// values have in common; out_value<V> is value V of that cell, NODATA where CRasterDataset.cpp masks it.
+// -------------------------------------------------------------------------------------------------
+struct OutCell {
+	double z, zmax, qx, qy, zb;
+	double depth, div;                            // Z - zb; the velocities' divisor
+	double vx, vy;                                // Q / div (formed only where a velocity or the Froude number is asked for)
+	bool   wet;                                   // depth > OUT_WET
+};
+
+constexpr unsigned OUT_NEEDS_VELOCITY = (1u << OUT_VELOCITY_X) | (1u << OUT_VELOCITY_Y) | (1u << OUT_FROUDE);
+
+template <typename T>
+__device__ __forceinline__ OutCell out_cell(const State4<T>& c, const T bed, const bool velocity)
+{
+	OutCell o;
+	o.z = (double)c.z; o.zmax = (double)c.zmax; o.qx = (double)c.qx; o.qy = (double)c.qy;
+	o.zb = (double)bed;
+	o.depth = o.z - o.zb;
+	o.wet = o.depth > OUT_WET;
+	// a dry cell's quotient (by zero, or by a negative depth) is never formed: the divisor is replaced before the division
+	o.div = o.wet ? o.depth : 1.0;
+	o.vx = o.vy = 0.0;
+	if (velocity) { o.vx = o.qx / o.div; o.vy = o.qy / o.div; }
+	return o;
+}
+
+template <int V>
+__device__ __forceinline__ double out_value(const OutCell& o, const double resolution)
+{
+	if constexpr (V == OUT_DEPTH) {
+		const double d = o.depth > 0.0 ? o.depth : 0.0;
+		return d < OUT_WET ? OUT_NODATA : d;
+	} else if constexpr (V == OUT_MAXDEPTH) {
+		const double dm = o.zmax - o.zb;
+		const double d = dm > 0.0 ? dm : 0.0;
+		return (d < OUT_WET || d <= -9990.0 || d >= 9999.0) ? OUT_NODATA : d;
+	} else if constexpr (V == OUT_FSL) {
+		return (o.z < o.zb + OUT_WET || o.zb > 9999.0) ? OUT_NODATA : o.z;
+	} else if constexpr (V == OUT_MAXFSL) {
+		return (o.zmax < o.zb + OUT_WET || o.zb > 9999.0) ? OUT_NODATA : o.zmax;
+	} else if constexpr (V == OUT_DISCHARGE_X) {
+		return o.qx * resolution;
+	} else if constexpr (V == OUT_DISCHARGE_Y) {
+		return o.qy * resolution;
+	} else if constexpr (V == OUT_VELOCITY_X) {
+		return o.wet ? o.vx : OUT_NODATA;
+	} else if constexpr (V == OUT_VELOCITY_Y) {
+		return o.wet ? o.vy : OUT_NODATA;
+	} else {
+		static_assert(V == OUT_FROUDE, "unknown HP_OUT_* code");
+		const double fr = sqrt_(o.vx * o.vx + o.vy * o.vy) / sqrt_(9.81 * o.div);
+		return o.wet ? fr : OUT_NODATA;
+	}
+}
+
+// f(integral_constant<int, V>) for every value V whose bit is set in `mask` (the same in every lane: a scalar branch per value)
+template <int V = 0, typename F>
+__device__ __forceinline__ void out_for_each(const unsigned mask, F&& f)
+{
+	if constexpr (V < OUT_VALUES) {
+		if (mask & (1u << V)) f(std::integral_constant<int, V>{});
+		out_for_each<V + 1>(mask, f);
+	}
+}
 
 // -------------------------------------------------------------------------------------------------
 // derive_rasters : one pass over cells [first, first + n) (whole rows of the local array, so the range is contiguous).
@@ -34,40 +103,8 @@ __global__ __launch_bounds__(256) void derive_rasters(const State4<T>* __restric
 	const unsigned mask = t.mask;
 	for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
 		const State4<T> c = state[first + k];
-		const double z = (double)c.z, zmax = (double)c.zmax, qx = (double)c.qx, qy = (double)c.qy;
-		const double zb = (double)bed[first + k];
-		const double depth = z - zb;
-		const bool wet = depth > OUT_WET;
-		// a dry cell's quotient (by zero, or by a negative depth) is never formed: the divisor is replaced before the division
-		const double div = wet ? depth : 1.0;
-		if (mask & (1u << OUT_DEPTH)) {
-			const double d = depth > 0.0 ? depth : 0.0;
-			((O*)t.raster[OUT_DEPTH])[k] = (O)(d < OUT_WET ? OUT_NODATA : d);
-		}
-		if (mask & (1u << OUT_MAXDEPTH)) {
-			const double dm = zmax - zb;
-			const double d = dm > 0.0 ? dm : 0.0;
-			((O*)t.raster[OUT_MAXDEPTH])[k] = (O)((d < OUT_WET || d <= -9990.0 || d >= 9999.0) ? OUT_NODATA : d);
-		}
-		if (mask & (1u << OUT_FSL))
-			((O*)t.raster[OUT_FSL])[k] = (O)((z < zb + OUT_WET || zb > 9999.0) ? OUT_NODATA : z);
-		if (mask & (1u << OUT_MAXFSL))
-			((O*)t.raster[OUT_MAXFSL])[k] = (O)((zmax < zb + OUT_WET || zb > 9999.0) ? OUT_NODATA : zmax);
-		if (mask & (1u << OUT_DISCHARGE_X))
-			((O*)t.raster[OUT_DISCHARGE_X])[k] = (O)(qx * resolution);
-		if (mask & (1u << OUT_DISCHARGE_Y))
-			((O*)t.raster[OUT_DISCHARGE_Y])[k] = (O)(qy * resolution);
-		if (mask & ((1u << OUT_VELOCITY_X) | (1u << OUT_VELOCITY_Y) | (1u << OUT_FROUDE))) {
-			const double vx = qx / div, vy = qy / div;
-			if (mask & (1u << OUT_VELOCITY_X))
-				((O*)t.raster[OUT_VELOCITY_X])[k] = (O)(wet ? vx : OUT_NODATA);
-			if (mask & (1u << OUT_VELOCITY_Y))
-				((O*)t.raster[OUT_VELOCITY_Y])[k] = (O)(wet ? vy : OUT_NODATA);
-			if (mask & (1u << OUT_FROUDE)) {
-				const double fr = sqrt_(vx * vx + vy * vy) / sqrt_(9.81 * div);
-				((O*)t.raster[OUT_FROUDE])[k] = (O)(wet ? fr : OUT_NODATA);
-			}
-		}
+		const OutCell o = out_cell(c, bed[first + k], (mask & OUT_NEEDS_VELOCITY) != 0);
+		out_for_each(mask, [&](auto v) { constexpr int V = decltype(v)::value; ((O*)t.raster[V])[k] = (O)out_value<V>(o, resolution); });
 	}
 }
 

@@ -32,6 +32,10 @@ PTR_STATE_NEXT_SRC, PTR_STATE_OTHER, PTR_BED, PTR_MANNING, PTR_CFL_MAX, PTR_SCAL
 # the front end's value names (frontend.data_value_code) -> HP_OUT_*
 OUT_CODES = {"depth": OUT_DEPTH, "maxdepth": OUT_MAXDEPTH, "fsl": OUT_FSL, "maxfsl": OUT_MAXFSL, "dischargex": OUT_DISCHARGE_X,
              "dischargey": OUT_DISCHARGE_Y, "velocityx": OUT_VELOCITY_X, "velocityy": OUT_VELOCITY_Y, "froude": OUT_FROUDE}
+AGG_MAX, AGG_MIN, AGG_COUNT, AGG_KINDS = range(4)
+# the aggregates' names (a <dataTarget>'s aggregate attribute) -> HP_AGG_*
+AGG_CODES = {"max": AGG_MAX, "min": AGG_MIN, "count": AGG_COUNT}
+OVERVIEW_FACTOR_MAX = 4096
 (PEAK_SPEED, PEAK_UNIT_DISCHARGE, PEAK_HAZARD, PEAK_ARRIVAL_TIME, PEAK_WET_DURATION, PEAK_COUNT) = range(6)
 # the front end's peak value names (frontend.peak_value_code) -> HP_PEAK_*
 PEAK_CODES = {"peakspeed": PEAK_SPEED, "peakunitdischarge": PEAK_UNIT_DISCHARGE, "hazard": PEAK_HAZARD,
@@ -41,7 +45,7 @@ NO_CELL = 2 ** 64 - 1          # hp_domain_stats_t: "no such cell"
 EXPORTS = [
     "hp_abi_version", "hp_device_count", "hp_device_info", "hp_last_error", "hp_set_log_sink", "hp_domain_desc_default",
     "hp_domain_create", "hp_domain_destroy", "hp_domain_upload", "hp_domain_download", "hp_domain_upload_rows", "hp_state_save", "hp_state_restore",
-    "hp_domain_derive", "hp_domain_stats",
+    "hp_domain_derive", "hp_domain_stats", "hp_overview_shape", "hp_domain_overview",
     "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
@@ -160,6 +164,10 @@ def load_library(path: str | None = None):
     if hasattr(lib, "hp_domain_derive"):                # (absent from older builds loaded through HIPIMS_MI_LIB for A/B runs: calling it there raises)
         lib.hp_domain_derive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
         lib.hp_domain_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DomainStats)]
+    if hasattr(lib, "hp_domain_overview"):              # (absent from older builds, as above)
+        lib.hp_overview_shape.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.hp_domain_overview.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                           C.c_int64, C.c_int64]
     if hasattr(lib, "hp_peaks_enable"):                 # (absent from older builds, as above)
         lib.hp_peaks_enable.argtypes = [C.c_void_p, C.POINTER(PeaksDesc)]
         lib.hp_peaks_disable.argtypes = [C.c_void_p]
@@ -240,6 +248,40 @@ def split_probe_records(records, gauges, sections):
     """[n, 1 + 4 G + S] probe records (hp_probes_read's layout) as {"t": [n], "gauges": [n, G, 4], "sections": [n, S]}."""
     rec = np.asarray(records, dtype=np.float64).reshape(-1, 1 + 4 * gauges + sections)
     return dict(t=rec[:, 0].copy(), gauges=rec[:, 1:1 + 4 * gauges].reshape(-1, gauges, 4).copy(), sections=rec[:, 1 + 4 * gauges:].copy())
+
+
+def overview_shape(cols, factor, row_offset=0, row0=0, nrows=0):
+    """hp_overview_shape's arithmetic: (first_block_row, block_rows, block_cols) of rows [row0, row0 + nrows) of a local array of
+    `cols` columns whose row 0 is row `row_offset` of the global grid, in blocks of factor x factor cells anchored to that grid."""
+    cols, factor, lo, nrows = int(cols), int(factor), int(row_offset) + int(row0), int(nrows)
+    if not 1 <= factor <= OVERVIEW_FACTOR_MAX:
+        raise ValueError("factor outside 1..4096")
+    if cols < 1 or lo < 0 or nrows < 0:
+        raise ValueError("row range out of bounds")
+    first = lo // factor
+    return first, (0 if nrows == 0 else (lo + nrows - 1) // factor - first + 1), -(-cols // factor)
+
+
+def overview_pairs(values, aggregates):
+    """The (value, aggregate) pairs of Domain.overview as HP_OUT_* / HP_AGG_* codes: `values` are the front end's value names
+    (frontend.data_value_code) or codes, `aggregates` names of AGG_CODES or codes -- one per value, or one for all of them."""
+    from .frontend import data_value_code
+    values = [values] if isinstance(values, (str, int)) else list(values)
+    aggregates = [aggregates] * len(values) if isinstance(aggregates, (str, int)) else list(aggregates)
+    if len(aggregates) != len(values):
+        raise ValueError("one aggregate per value, or one for all of them")
+    pairs = []
+    for v, a in zip(values, aggregates):
+        vc = v if isinstance(v, int) else OUT_CODES.get(data_value_code(v))
+        ac = a if isinstance(a, int) else AGG_CODES.get(str(a).lower())
+        if vc is None or not 0 <= vc < OUT_COUNT:
+            raise ValueError(f"unknown output {v}")
+        if ac is None or not 0 <= ac < AGG_KINDS:
+            raise ValueError(f"unknown aggregate {a}")
+        if (vc, ac) in pairs:
+            raise ValueError(f"the pair ({v}, {a}) is listed twice")
+        pairs.append((vc, ac))
+    return pairs
 
 
 ZONE_WORDS = 7                 # HP_ZONE_WORDS: cells, wet, flooded, depth_hi, depth_lo, max_depth, max_speed
@@ -505,6 +547,37 @@ class Domain:
             out[name] = arrays[k].copy() if k in used else arrays[k]        # (two names of one value: separate arrays)
             used.add(k)
         return out
+
+    def overview_shape(self, factor, row0=0, nrows=None):
+        """(first_block_row, block_rows, block_cols) of Domain.overview's arrays for rows [row0, row0 + nrows): the library's own
+        arithmetic (hp_overview_shape; the module's overview_shape restates it)."""
+        nrows = self.rows - row0 if nrows is None else nrows
+        first, brows, bcols = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(self.lib, self.lib.hp_overview_shape(self.h, int(factor), row0, nrows, C.byref(first), C.byref(brows), C.byref(bcols)),
+               "hp_overview_shape")
+        return first.value, brows.value, bcols.value
+
+    def overview(self, values, aggregates, factor, dtype=np.float64, row0=0, nrows=None):
+        """Block-aggregated overview rasters derived on the device, without a state download: one array [block_rows, block_cols]
+        per (value, aggregate) pair (overview_pairs), in order.  Blocks of factor x factor cells anchored to the global grid; row 0
+        of the arrays is block row overview_shape(...)[0].  fp64 arrays are bit-identical to frontend.overview(frontend.
+        derive_output(name, self.download(), bed, dx), factor, aggregate, row_offset); dtype=np.float32 gives those rounded once."""
+        pairs = overview_pairs(values, aggregates)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32")
+        nrows = self.rows - row0 if nrows is None else nrows
+        if not pairs:
+            return []
+        _, brows, bcols = self.overview_shape(factor, row0, nrows)       # (also checks the factor and the row range)
+        arrays = [np.empty((brows, bcols), dtype) for _ in pairs]
+        c_values = (C.c_int * len(pairs))(*[v for v, _ in pairs])
+        c_aggs = (C.c_int * len(pairs))(*[a for _, a in pairs])
+        c_rasters = (C.c_void_p * len(pairs))(*[a.ctypes.data for a in arrays])
+        _check(self.lib, self.lib.hp_domain_overview(self.h, c_values, c_aggs, len(pairs), int(factor), dtype.itemsize, c_rasters, row0, nrows),
+               "hp_domain_overview")
+        self.sync()
+        return arrays
 
     def stats(self, row0=0, nrows=None):
         """cells, cells_wet, volume (m3), max_depth, max_speed and the local flat cell id of each maximum (None where no

@@ -116,6 +116,7 @@ class Configuration:
     device_number: int = 1
     gauges: list = field(default_factory=list)     # (name, x, y): <gauge> elements, cell indices (no reference counterpart)
     sections: list = field(default_factory=list)   # (name, x0, y0, x1, y1): <section> elements, cell indices
+    overviews: list = field(default_factory=list)  # (value, aggregate, factor, target pattern, format): <dataTarget overview="...">
 
 
 def _params(elem):
@@ -157,6 +158,10 @@ def parse_configuration(xml_path):
                             ds.get("source")))
     cfg.target_formats = []                  # GDAL driver names of the <dataTarget format=...> attributes (CDomainCartesian.cpp:300)
     for dt in data.findall("dataTarget"):
+        if dt.get("overview") is not None:   # a block-aggregated overview of the value (no reference counterpart): not a full raster
+            cfg.overviews.append(((dt.get("value") or "").lower(), aggregate_name(dt.get("aggregate") or "max"), int(dt.get("overview")),
+                                  dt.get("target"), (dt.get("format") or "").upper()))
+            continue
         cfg.targets.append(((dt.get("value") or "").lower(), dt.get("target")))
         cfg.target_formats.append((dt.get("format") or "").upper())
     # the probe recorder's elements (no reference counterpart): cell indices, the convention of a cell boundary's mapFile
@@ -625,6 +630,99 @@ def derive_output(what, state, bed, resolution=1.0):
         if code == "froude":
             return np.where(depth > 1e-8, np.sqrt((qx / depth) ** 2 + (qy / depth) ** 2) / np.sqrt(9.81 * depth), NODATA)
     raise ValueError(f"unknown output {what}")
+
+
+# ------------------------------------------------------------------------------------------------ overviews
+AGGREGATES = ("max", "min", "count")                # = hipims_mi.AGG_CODES, in code order
+
+
+def aggregate_name(aggregate):
+    """"max" | "min" | "count" for a name (case-insensitive) or an HP_AGG_* code."""
+    if isinstance(aggregate, (int, np.integer)) and not isinstance(aggregate, bool) and 0 <= int(aggregate) < len(AGGREGATES):
+        return AGGREGATES[int(aggregate)]
+    if isinstance(aggregate, str) and aggregate.lower() in AGGREGATES:
+        return aggregate.lower()
+    raise ValueError(f"unknown aggregate {aggregate}")
+
+
+def _order_keys(a):
+    """The elements of a float64 / float32 array in their own order as unsigned integers of the same width (csrc/hp_overview.hpp:
+    overview_key): negative values complemented, the others with the sign bit set; -0.0 lies below +0.0.  Elements that do not take
+    part -- NODATA and NaN -- get 0, which lies below every key."""
+    a = np.ascontiguousarray(a)
+    if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        a = a.astype(np.float64)
+    u = np.uint64 if a.dtype == np.float64 else np.uint32
+    bits = a.view(u)
+    top = u(1) << u(8 * a.itemsize - 1)
+    keys = np.where(bits & top != 0, ~bits, bits | top)
+    return np.where((a != NODATA) & ~np.isnan(a), keys, u(0)), a.dtype
+
+
+def _from_keys(keys, dtype, complemented=False):
+    """The values of _order_keys' keys (their complements with complemented=True); NODATA where the key is 0."""
+    u = keys.dtype.type
+    top = u(1) << u(8 * keys.itemsize - 1)
+    k = ~keys if complemented else keys
+    values = np.where(k & top != 0, k ^ top, ~k).view(dtype)
+    return np.where(keys == 0, dtype.type(NODATA), values)
+
+
+def overview(raster, factor, aggregate, row_offset=0):
+    """hp_domain_overview in NumPy: `raster` is a full-resolution raster as derive_output delivers it, [nrows, cols] with row 0 =
+    row `row_offset` of the global grid; the result is float64 [block_rows, block_cols] over blocks of factor x factor cells
+    anchored to that grid (hipims_mi.overview_shape), edge blocks partial.  A cell takes part iff its value is neither NODATA nor
+    NaN; "max" / "min": the largest / smallest participating value (NODATA if none; -0.0 below +0.0), "count": their number."""
+    from . import overview_shape
+    kind = aggregate_name(aggregate)
+    a = np.asarray(raster)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError("the raster must be [rows, cols]")
+    a = a.astype(np.float64)
+    nrows, cols = a.shape
+    first, brows, bcols = overview_shape(cols, factor, row_offset, 0, nrows)
+    if nrows == 0:
+        return np.empty((0, bcols), np.float64)
+    # where the blocks start, as indices into the raster (the first block row may start below the raster's row 0)
+    row_cuts = np.maximum(0, np.arange(first, first + brows) * int(factor) - int(row_offset))
+    col_cuts = np.arange(bcols) * int(factor)
+    keys, dtype = _order_keys(a)
+    if kind == "count":
+        part = (keys != 0).astype(np.int64)
+        return np.add.reduceat(np.add.reduceat(part, row_cuts, axis=0), col_cuts, axis=1).astype(np.float64)
+    if kind == "min":
+        keys = np.where(keys != 0, ~keys, np.uint64(0))
+    folded = np.maximum.reduceat(np.maximum.reduceat(keys, row_cuts, axis=0), col_cuts, axis=1)
+    return _from_keys(folded, dtype, complemented=kind == "min")
+
+
+def combine_overviews(parts, aggregate):
+    """The overview of a row range from those of its parts, each a (first_block_row, array[block_rows, block_cols]) pair laid on the
+    global block grid (None entries are skipped); a block that two parts touch -- a cut inside a block -- gets the larger / smaller
+    of its two values, ignoring NODATA, or the sum of its two counts.  -> (first_block_row, array) over the block rows the parts
+    span; block rows that no part touches hold NODATA (0 for counts).  Order-independent like the device's own fold: equal to the
+    uncut overview in every bit, whatever the cut."""
+    kind = aggregate_name(aggregate)
+    parts = [(int(f), np.asarray(a)) for f, a in (p for p in parts if p is not None)]
+    if not parts:
+        raise ValueError("no part")
+    dtype, bcols = parts[0][1].dtype, parts[0][1].shape[1]
+    if any(a.ndim != 2 or a.dtype != dtype or a.shape[1] != bcols for _, a in parts):
+        raise ValueError("the parts' overviews differ in type or block columns")
+    lo, hi = min(f for f, _ in parts), max(f + len(a) for f, a in parts)
+    if kind == "count":
+        out = np.zeros((hi - lo, bcols), dtype)
+        for f, a in parts:
+            out[f - lo:f - lo + len(a)] += a
+        return lo, out
+    keys0, kdtype = _order_keys(np.zeros((1, 1), dtype))
+    folded = np.zeros((hi - lo, bcols), keys0.dtype)
+    for f, a in parts:
+        keys, _ = _order_keys(a)
+        if kind == "min":
+            keys = np.where(keys != 0, ~keys, keys.dtype.type(0))
+        folded[f - lo:f - lo + len(a)] = np.maximum(folded[f - lo:f - lo + len(a)], keys)
+    return lo, _from_keys(folded, kdtype, complemented=kind == "min")
 
 
 def run_model(xml_path, make_sim=None, batch=None, output_format=".npy", max_outputs=None, log=None):

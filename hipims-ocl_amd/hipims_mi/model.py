@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import frontend
+from . import OUT_CODES, frontend
 
 
 def seconds_to_time(s: float) -> str:
@@ -173,7 +173,7 @@ class Model:
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
-                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096):
+                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -277,6 +277,18 @@ class Model:
             else:
                 self.host_zones = frontend.ZoneRecorder(self.zone_ids, self.zone_count, zone_flood_depth, self.res)
                 self.scheme.samplers.append(self.sample_zones_on_host)
+        # Overviews (no reference counterpart): the <dataTarget overview="16" aggregate="max|min|count"> elements of the model file
+        # and the (value, aggregate, factor) triples of `overviews`; at every output time each is the value's raster aggregated over
+        # blocks of factor x factor cells, written through write_raster with resolution factor * dx.  On the device
+        # (Domain.overview) wherever the output rasters are derived there; otherwise frontend.overview of the host derivation.
+        self.overview_list = [tuple(o) for o in cfg.overviews] + \
+            [(str(v).lower(), frontend.aggregate_name(a), int(f), None, "") for v, a, f in overviews or []]
+        for what, _, factor, _, _ in self.overview_list:
+            if frontend.data_value_code(what) not in OUT_CODES:
+                raise ValueError(f"unknown output {what}")
+            if not 1 <= factor <= 4096:
+                raise ValueError(f"overview of {what}: factor outside 1..4096")
+        self.device_overviews = bool(self.overview_list) and self.device_outputs and hasattr(sim, "overview")
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
 
@@ -341,6 +353,17 @@ class Model:
             derived = self.sim.derive(plain) if plain else {}
         elif plain or not self.cfg.targets:
             final = self.sim.download()
+        overviews = {}                                             # {(value, aggregate, factor): array}
+        if self.device_overviews:                                  # one call per factor, coarse rasters only over the host link
+            for factor in sorted({o[2] for o in self.overview_list}):
+                mine = [o for o in self.overview_list if o[2] == factor]
+                arrays = self.sim.overview([o[0] for o in mine], [o[1] for o in mine], factor)
+                overviews.update({o[:3]: a for o, a in zip(mine, arrays)})
+        elif self.overview_list:
+            if self.device_outputs or not (plain or not self.cfg.targets):
+                final = self.sim.download()
+            for what, aggregate, factor, _, _ in self.overview_list:
+                overviews[(what, aggregate, factor)] = frontend.overview(frontend.derive_output(what, final, self.bed, self.res), factor, aggregate)
         peaks = self.peaks()                                       # the peaks so far, written like maxdepth at every output time
         out = {}
         for k, (what, pattern) in enumerate(self.cfg.targets):
@@ -358,6 +381,12 @@ class Model:
                 frontend.write_raster(os.path.join(self.cfg.target_dir, fname), arr, self.res)
         for name, arr in peaks.items():                            # (asked for through Model(peaks=...) only: no file)
             out.setdefault(name, arr)
+        for what, aggregate, factor, pattern, fmt in self.overview_list:
+            out[(what, aggregate, factor)] = arr = overviews[(what, aggregate, factor)]
+            if pattern and self.cfg.target_dir and self.output_format:
+                ext = self.output_format if self.output_format != "xml" else (".img" if fmt == "HFA" else ".asc")
+                fname = os.path.splitext(pattern.replace("%t", str(int(round(self.current_time)))))[0] + ext
+                frontend.write_raster(os.path.join(self.cfg.target_dir, fname), arr, factor * self.res)
         self.write_probes()
         self.write_zones()
         self.outputs.append((self.current_time, out))

@@ -59,6 +59,19 @@ def assemble_outputs(parts):
     return {name: np.concatenate([p[name] for p in parts], axis=0) for name in parts[0]}
 
 
+def assemble_overviews(parts, aggregates):
+    """[per rank: (first_block_row, [one overview per pair])] -> [one overview of the whole grid per pair]: the ranks' owned rows
+    cover the grid, so the combined block rows start at 0 (frontend.combine_overviews: integer folds, equal to the single domain's
+    overview in every bit wherever the strips are cut)."""
+    from . import frontend
+    out = []
+    for k, aggregate in enumerate(aggregates):
+        first, combined = frontend.combine_overviews([(f, arrays[k]) for f, arrays in parts], aggregate)
+        assert first == 0, first
+        out.append(combined)
+    return out
+
+
 def combine_stats(parts, local_los, cols):
     """Domain.stats() of every rank's OWNED rows (rank order) as the statistics of the whole grid: counts added and maxima
     combined exactly -- equal maxima go to the lowest cell id, i.e. to the first rank that has them --, volumes added in
@@ -170,6 +183,12 @@ class HipEngine:
 
     def derive(self, values, dtype=np.float64, row0=0, nrows=None):
         return self.domain.derive(values, dtype=dtype, row0=row0, nrows=nrows)
+
+    def overview(self, values, aggregates, factor, dtype=np.float64, row0=0, nrows=None):
+        return self.domain.overview(values, aggregates, factor, dtype=dtype, row0=row0, nrows=nrows)
+
+    def overview_shape(self, factor, row0=0, nrows=None):
+        return self.domain.overview_shape(factor, row0=row0, nrows=nrows)
 
     def stats(self, row0=0, nrows=None):
         return self.domain.stats(row0=row0, nrows=nrows)
@@ -537,6 +556,19 @@ class StripRunner:
         parts = [None] * self.world if self.rank == 0 else None
         self.dist.gather_object(mine, parts, dst=0)                 # rasters travel to rank 0 only
         return assemble_outputs(parts) if self.rank == 0 else None
+
+    def gather_overview(self, values, aggregates, factor, dtype=np.float64):
+        """Block-aggregated overviews of the whole grid (Domain.overview): every rank aggregates its OWNED rows on its device --
+        blocks are anchored to the global grid, so a block that a strip border cuts comes in two parts --, rank 0 puts the parts
+        together (assemble_overviews) and gets one array [ceil(rows / factor), ceil(cols / factor)] per (value, aggregate) pair,
+        equal to the single domain's in every bit; the other ranks None.  Collective."""
+        from . import overview_pairs
+        pairs = overview_pairs(values, aggregates)
+        row0, nrows = self.own_lo - self.local_lo, self.own_hi - self.own_lo
+        mine = (self.engine.overview_shape(factor, row0=row0, nrows=nrows)[0],
+                self.engine.overview([v for v, _ in pairs], [a for _, a in pairs], factor, dtype=dtype, row0=row0, nrows=nrows))
+        parts = self._gather_parts(mine)
+        return assemble_overviews(parts, [a for _, a in pairs]) if self.rank == 0 else None
 
     def _gather_parts(self, mine):
         """Every rank's `mine` in rank order on rank 0, None on the other ranks: pickled over the process group, which a single

@@ -181,6 +181,36 @@ enum { HP_OUT_DEPTH = 0, HP_OUT_MAXDEPTH = 1, HP_OUT_FSL = 2, HP_OUT_MAXFSL = 3,
  * stays usable.  Argument errors are HP_ERR_INVALID before any device call; nrows == 0 is HP_OK. */
 int hp_domain_derive(hp_domain_t* d, const int* values, int count, int element_bytes,
                      void* const* rasters, int64_t row0, int64_t nrows);
+/* The same nine values aggregated over square blocks of factor x factor cells on the device: an overview of the run (a progress
+ * map, the frames of an animation) for 1 / factor^2 of the bytes a full raster moves to the host.  No reference counterpart.
+ *   Blocks.  Block (bx, by) holds the cells with x / factor == bx and (row_offset + y) / factor == by: blocks are anchored to the
+ * GLOBAL grid, so that the overviews of strips can be put together.  factor is any integer in 1..4096 -- no power of two, no
+ * divisor of the grid; it may exceed cols or rows.  block_cols = ceil(cols / factor), first_block_row = (row_offset + row0) /
+ * factor, block_rows = the block rows touched by rows [row0, row0 + nrows) of the LOCAL array (0 for nrows == 0):
+ * hp_overview_shape, pure arithmetic without a device call.  rasters[i] receives block_rows * block_cols elements, row 0 = south.
+ * Only cells inside the row range take part (a strip's caller picks the owned range): edge blocks are partial.
+ *   Per-cell value.  That of values[i] (HP_OUT_*) is exactly what hp_domain_derive forms in fp64 before it rounds: the same
+ * expressions, NODATA rules and 1e-8 wet test (one definition in csrc/hp_output.hpp serves both).
+ *   Aggregation.  A cell takes part in a block iff its value is neither -9999.0 nor a NaN.  HP_AGG_MAX / HP_AGG_MIN: the largest /
+ * smallest participating value (values are signed; -0.0 lies below +0.0), -9999.0 if there is none.  HP_AGG_COUNT: the number of
+ * participating cells, as an exactly representable floating-point number.  element_bytes 8 delivers these fp64 results, 4 the same
+ * results rounded once, after the aggregation.  All three are order-independent -- what is accumulated is integers: an
+ * order-preserving key of the double, and counts; there is no floating-point atomic and no floating-point sum -- so the result
+ * depends neither on the launch shape nor on how a large request is cut into runs of block rows nor on how the grid is cut into
+ * strips (frontend.overview restates it in NumPy, frontend.combine_overviews puts the parts of strips or row ranges together).
+ *   Each (value, aggregate) pair at most once; count is 1..27.  Everything else follows hp_domain_derive: reads the buffer
+ * hp_domain_download(HP_ARRAY_STATE) reads, in stream order behind whatever is queued, changes nothing the steps depend on, is
+ * enqueued on the domain's stream and never blocks; the host memory must stay alive until hp_sync().  The accumulators and the
+ * elements come out of the same bounded scratch (256 MiB; larger requests are worked through in runs of whole block rows).
+ * Argument errors -- a NULL pointer, an unknown value or aggregate, a repeated pair, a factor outside 1..4096, a bad
+ * element_bytes, a row range outside the array -- are HP_ERR_INVALID before any device call; between hp_step_begin and
+ * hp_step_end the call returns HP_ERR_STATE; nrows == 0 is HP_OK. */
+enum { HP_AGG_MAX = 0, HP_AGG_MIN = 1, HP_AGG_COUNT = 2, HP_AGG_KINDS = 3 };
+int hp_overview_shape(hp_domain_t* d, int factor, int64_t row0, int64_t nrows,
+                      int64_t* first_block_row, int64_t* block_rows, int64_t* block_cols);
+int hp_domain_overview(hp_domain_t* d, const int* values, const int* aggregates, int count,
+                       int factor, int element_bytes, void* const* rasters,
+                       int64_t row0, int64_t nrows);
 /* Statistics of rows [row0, row0 + nrows) of the same buffer: what the reference's progress log takes from
  * CDomainCartesian::getVolume (CDomainCartesian.cpp:743-760, CSchemeGodunov.cpp:1060, CModel.cpp:1127) and what a user
  * reads next to it.  A deterministic two-stage reduction (no floating-point atomics: the same state gives the same bits). */
