@@ -9,6 +9,7 @@
 #include "hp_probes.hpp"
 #include "hp_zones.hpp"
 #include "hp_overview.hpp"
+#include "hp_sparse.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <atomic>
@@ -57,10 +58,12 @@ struct Boundary {
 };
 
 // ---- the observers' state (their code: hp_observers.hpp) ----
-// the output stage (hp_output.hpp, hp_overview.hpp; hp_domain_derive / hp_domain_overview / hp_domain_stats): allocated on first use
+// the output stage (hp_output.hpp, hp_overview.hpp, hp_sparse.hpp; hp_domain_derive / hp_domain_overview / hp_domain_sparse / hp_domain_stats):
+// allocated on first use
 struct OutputStage {
 	void*            scratch = nullptr;               // rasters of one block of rows, value after value -- or, of hp_domain_overview, the accumulator
-	                                                  // words and elements of one run of block rows, pair after pair -- (at most OUT_SCRATCH_CAP bytes)
+	                                                  // words and elements of one run of block rows, pair after pair; of hp_domain_sparse, the selection words and offsets of the range
+	                                                  // and the entries of one run -- (at most OUT_SCRATCH_CAP bytes)
 	size_t           scratch_bytes = 0;
 	void*            stats = nullptr;                 // STATS_MAX_BLOCKS block partials + the folded result
 	void*            stats_host = nullptr;            // pinned: the folded result

@@ -1,4 +1,4 @@
-// hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp, hp_overview.hpp), the peak tracker
+// hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp, hp_overview.hpp, hp_sparse.hpp), the peak tracker
 // (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
 // (*_save, *_restore, *_destroy).  The two recorders share one record log (log_*): their own entry points keep the argument
@@ -474,6 +474,97 @@ int hp_domain_overview(hp_domain_t* d, const int* values, const int* aggregates,
 		for (int k = 0; k < count; ++k)
 			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + (size_t)b * (size_t)block_cols * esize, out + (size_t)k * (size_t)g.blocks * esize,
 			                       (size_t)g.blocks * esize, hipMemcpyDeviceToHost, d->stream));
+	}
+	return HP_OK;
+}
+
+// ---- the output stage's selected form (hp_sparse.hpp) ----
+int hp_domain_sparse(hp_domain_t* d, int select_value, double above, const int* values, int count, int element_bytes, uint64_t capacity,
+                     uint64_t* selected, uint64_t* row_ptr, uint32_t* col, void* const* rasters, int64_t row0, int64_t nrows)
+{
+	// argument checks first, as in hp_domain_derive: none of them touches the device, and those that do not need the domain come before it
+	const std::string who = "hp_domain_sparse";
+	if (!selected || !row_ptr) return fail(HP_ERR_INVALID, who + ": selected / row_ptr == NULL");
+	if (count < 1 || count > HP_OUT_COUNT) return fail(HP_ERR_INVALID, who + ": count outside 1..HP_OUT_COUNT");
+	if (!values) return fail(HP_ERR_INVALID, who + ": values == NULL");
+	if (element_bytes != 4 && element_bytes != 8) return fail(HP_ERR_INVALID, who + ": element_bytes must be 4 or 8");
+	if (select_value < 0 || select_value >= HP_OUT_COUNT) return fail(HP_ERR_INVALID, who + ": unknown select_value " + std::to_string(select_value));
+	if (above != above) return fail(HP_ERR_INVALID, who + ": above is a NaN");
+	if (capacity > 0 && (!col || !rasters)) return fail(HP_ERR_INVALID, who + ": capacity > 0 with col / rasters == NULL");
+	unsigned seen = 0;
+	for (int k = 0; k < count; ++k) {
+		if (values[k] < 0 || values[k] >= HP_OUT_COUNT) return fail(HP_ERR_INVALID, who + ": unknown value " + std::to_string(values[k]));
+		if (seen & (1u << values[k])) return fail(HP_ERR_INVALID, who + ": value " + std::to_string(values[k]) + " listed twice");
+		seen |= 1u << values[k];
+		if (capacity > 0 && !rasters[k]) return fail(HP_ERR_INVALID, who + ": rasters[" + std::to_string(k) + "] == NULL");
+	}
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	if ((uint64_t)d->desc.cols >= (1ull << 32)) return fail(HP_ERR_INVALID, who + ": cols >= 2^32 do not fit the column type");
+	if (nrows == 0) { *selected = 0; row_ptr[0] = 0; return HP_OK; }
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	// Scratch: the selection words and the offsets of the range's segments, the device's row_ptr and the scan's tile sums (all 64-bit
+	// words), and behind them the entries of one run: value after value, then the columns.
+	const uint64_t spr = ((uint64_t)d->desc.cols + 63) / 64, nseg = (uint64_t)nrows * spr;
+	const uint64_t tiles = (nseg + SPARSE_SCAN_TILE - 1) / SPARSE_SCAN_TILE;
+	const uint64_t fixed = 8 * (2 * nseg + (uint64_t)nrows + 1 + tiles + 1);
+	if (nseg > OUT_SCRATCH_CAP / 16 || fixed > OUT_SCRATCH_CAP)
+		return fail(HP_ERR_UNSUPPORTED, who + ": the selection words of " + std::to_string(nseg) + " segments exceed the 256 MiB raster scratch");
+	const uint64_t esize = (uint64_t)element_bytes, entry_bytes = 4 + (uint64_t)count * esize;
+	const uint64_t fit = std::min<uint64_t>(capacity, (OUT_SCRATCH_CAP - fixed) / entry_bytes);      // entries of the largest run
+	if (capacity > 0 && fit == 0) return fail(HP_ERR_UNSUPPORTED, who + ": the selection words leave no room for an entry in the 256 MiB raster scratch");
+	if ((rc = out_scratch_reserve(d, (size_t)(fixed + fit * entry_bytes), who)) != HP_OK) return rc;
+	unsigned long long* const words = (unsigned long long*)d->out.scratch;
+	unsigned long long* const offsets = words + nseg;
+	unsigned long long* const row_ptr_dev = offsets + nseg;
+	unsigned long long* const sums = row_ptr_dev + nrows + 1;
+	char* const entries = (char*)(sums + tiles + 1);
+	SparseGeom g = {};
+	g.cols = d->desc.cols;
+	g.row0 = row0;
+	g.segs_per_row = (unsigned)spr;
+	g.seg_lo = 0;
+	g.seg_hi = (unsigned)nseg;
+	g.resolution = d->desc.dx;
+	const auto wave_blocks = [](const uint64_t segments) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((segments + 3) / 4, 8192))); };
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((sparse_select<T>), wave_blocks(nseg), dim3(256), 0, d->stream,
+		                   (const State4<T>*)d->state[d->facts->use_alt], (const T*)d->bed, g, select_value, above, words);      // what hp_domain_download(HP_ARRAY_STATE) reads
+	});
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(sparse_scan_sums, dim3((unsigned)tiles), dim3(256), 0, d->stream, words, (unsigned)nseg, sums);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(sparse_scan_top, dim3(1), dim3(256), 0, d->stream, sums, (unsigned)tiles);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(sparse_scan_offsets, dim3((unsigned)tiles), dim3(256), 0, d->stream, words, (unsigned)nseg, sums, (unsigned)tiles, (unsigned)spr, offsets, row_ptr_dev);
+	HIP_TRY(hipGetLastError());
+	// the one wait of the call: the runs are cut from row_ptr, and the copies are of exactly the selected entries
+	HIP_TRY(hipMemcpyAsync(row_ptr, row_ptr_dev, (size_t)(nrows + 1) * 8, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	*selected = row_ptr[nrows];
+	if (*selected == 0 || *selected > capacity) return HP_OK;
+	for (const SparseRun& run : sparse_plan_runs(row_ptr, nrows, entry_bytes, fit * entry_bytes)) {
+		SparseTargets t = {};
+		for (int k = 0; k < count; ++k) {
+			t.raster[values[k]] = entries + (uint64_t)k * run.count * esize;
+			t.mask |= 1u << values[k];
+		}
+		t.col = (unsigned*)(entries + (uint64_t)count * run.count * esize);
+		t.first = run.first;
+		t.count = run.count;
+		g.seg_lo = (unsigned)((uint64_t)run.row_lo * spr);
+		g.seg_hi = (unsigned)((uint64_t)run.row_hi * spr);
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			const State4<T>* state = (const State4<T>*)d->state[d->facts->use_alt];
+			if (element_bytes == 8) hipLaunchKernelGGL((sparse_scatter<T, double>), wave_blocks(g.seg_hi - g.seg_lo), dim3(256), 0, d->stream, state, (const T*)d->bed, g, words, offsets, t);
+			else hipLaunchKernelGGL((sparse_scatter<T, float>), wave_blocks(g.seg_hi - g.seg_lo), dim3(256), 0, d->stream, state, (const T*)d->bed, g, words, offsets, t);
+		});
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(col + run.first, t.col, (size_t)run.count * 4, hipMemcpyDeviceToHost, d->stream));
+		for (int k = 0; k < count; ++k)
+			HIP_TRY(hipMemcpyAsync((char*)rasters[k] + run.first * esize, t.raster[values[k]], (size_t)(run.count * esize), hipMemcpyDeviceToHost, d->stream));
 	}
 	return HP_OK;
 }

@@ -45,7 +45,7 @@ NO_CELL = 2 ** 64 - 1          # hp_domain_stats_t: "no such cell"
 EXPORTS = [
     "hp_abi_version", "hp_device_count", "hp_device_info", "hp_last_error", "hp_set_log_sink", "hp_domain_desc_default",
     "hp_domain_create", "hp_domain_destroy", "hp_domain_upload", "hp_domain_download", "hp_domain_upload_rows", "hp_state_save", "hp_state_restore",
-    "hp_domain_derive", "hp_domain_stats", "hp_overview_shape", "hp_domain_overview",
+    "hp_domain_derive", "hp_domain_stats", "hp_overview_shape", "hp_domain_overview", "hp_domain_sparse",
     "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
@@ -168,6 +168,9 @@ def load_library(path: str | None = None):
         lib.hp_overview_shape.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.hp_domain_overview.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                            C.c_int64, C.c_int64]
+    if hasattr(lib, "hp_domain_sparse"):                # (absent from older builds, as above)
+        lib.hp_domain_sparse.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.c_int64, C.c_int64]
     if hasattr(lib, "hp_peaks_enable"):                 # (absent from older builds, as above)
         lib.hp_peaks_enable.argtypes = [C.c_void_p, C.POINTER(PeaksDesc)]
         lib.hp_peaks_disable.argtypes = [C.c_void_p]
@@ -578,6 +581,44 @@ class Domain:
                "hp_domain_overview")
         self.sync()
         return arrays
+
+    def sparse(self, values, select="depth", above=0.0, dtype=np.float64, row0=0, nrows=None):
+        """The values at the selected cells only, compacted on the device (hp_domain_sparse): (row_ptr, col, [one array per value])
+        in CSR over rows [row0, row0 + nrows) -- row_ptr uint64 [nrows + 1], col uint32 [selected], entries ascending by (row,
+        column).  A cell is selected iff its `select` value v (fp64, before any rounding) satisfies v != -9999 and v > above.
+        Bit-identical to frontend.sparse([frontend.derive_output(name, self.download(), bed, dx) ...], derive_output(select, ...),
+        above); dtype=np.float32 gives those values rounded once.  One call with room for the previous call's total x 1.25 (the
+        first call only counts), a second one if the total has outgrown that."""
+        from .frontend import data_value_code
+        names = [values] if isinstance(values, str) else list(values)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("dtype must be float64 or float32")
+        codes = [OUT_CODES.get(data_value_code(name)) for name in names]
+        select_code = OUT_CODES.get(data_value_code(select))
+        if None in codes or select_code is None:
+            raise ValueError(f"unknown output {select if select_code is None else names[codes.index(None)]}")
+        if len(set(codes)) != len(codes) or not codes:
+            raise ValueError("one to nine values, each at most once")
+        nrows = self.rows - row0 if nrows is None else nrows
+        row_ptr = np.zeros(max(0, nrows) + 1, np.uint64)
+        selected = C.c_uint64(0)
+        c_values = (C.c_int * len(codes))(*codes)
+        capacity = -(-getattr(self, "_sparse_total", 0) * 5 // 4)
+        while True:
+            col = np.empty(capacity, np.uint32)
+            arrays = [np.empty(capacity, dtype) for _ in codes]
+            c_rasters = (C.c_void_p * len(codes))(*[a.ctypes.data for a in arrays]) if capacity else None
+            _check(self.lib, self.lib.hp_domain_sparse(self.h, select_code, float(above), c_values, len(codes), dtype.itemsize, capacity, C.byref(selected),
+                                                       row_ptr.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       col.ctypes.data_as(C.POINTER(C.c_uint32)) if capacity else None, c_rasters, row0, nrows),
+                   "hp_domain_sparse")
+            if selected.value <= capacity:
+                break
+            capacity = selected.value                   # (the total has outgrown the guess: once more, with exactly that)
+        self.sync()
+        self._sparse_total = n = selected.value
+        return row_ptr, col[:n], [a[:n] for a in arrays]
 
     def stats(self, row0=0, nrows=None):
         """cells, cells_wet, volume (m3), max_depth, max_speed and the local flat cell id of each maximum (None where no

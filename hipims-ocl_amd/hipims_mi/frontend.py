@@ -117,6 +117,7 @@ class Configuration:
     gauges: list = field(default_factory=list)     # (name, x, y): <gauge> elements, cell indices (no reference counterpart)
     sections: list = field(default_factory=list)   # (name, x0, y0, x1, y1): <section> elements, cell indices
     overviews: list = field(default_factory=list)  # (value, aggregate, factor, target pattern, format): <dataTarget overview="...">
+    sparse: dict = None                            # select, above, values, target pattern: the <sparseTarget> element (the last one wins)
 
 
 def _params(elem):
@@ -164,6 +165,10 @@ def parse_configuration(xml_path):
             continue
         cfg.targets.append(((dt.get("value") or "").lower(), dt.get("target")))
         cfg.target_formats.append((dt.get("format") or "").upper())
+    for sp in data.findall("sparseTarget"):   # the values at the selected cells only, as CSR in one .npz (no reference counterpart)
+        cfg.sparse = dict(select=(sp.get("select") or "depth").lower(), above=float(sp.get("above") or 0.0),
+                          values=[v.strip().lower() for v in (sp.get("values") or sp.get("select") or "depth").split(",") if v.strip()],
+                          target=sp.get("target"))
     # the probe recorder's elements (no reference counterpart): cell indices, the convention of a cell boundary's mapFile
     for k, g in enumerate(data.findall("gauge")):
         cfg.gauges.append((g.get("name") or f"gauge{k}", int(g.get("x")), int(g.get("y"))))
@@ -723,6 +728,54 @@ def combine_overviews(parts, aggregate):
             keys = np.where(keys != 0, ~keys, keys.dtype.type(0))
         folded[f - lo:f - lo + len(a)] = np.maximum(folded[f - lo:f - lo + len(a)], keys)
     return lo, _from_keys(folded, kdtype, complemented=kind == "min")
+
+
+# ------------------------------------------------------------------------------------------------ selected cells (CSR)
+def sparse(rasters, select_raster, above):
+    """hp_domain_sparse in NumPy: `rasters` are full-resolution rasters [nrows, cols] as derive_output delivers them (or those
+    rounded to float32), `select_raster` the float64 raster of the selecting value.  A cell is selected iff its selecting value v
+    satisfies v != NODATA and v > above (a NaN fails).  -> (row_ptr uint64 [nrows + 1], col uint32 [selected], [the rasters' values
+    at the selected cells, in their own type]), entries ascending by (row, column)."""
+    sel = np.asarray(select_raster, np.float64)
+    if sel.ndim != 2:
+        raise ValueError("the select raster must be [rows, cols]")
+    if np.isnan(above):
+        raise ValueError("above is a NaN")
+    rasters = [np.asarray(a) for a in rasters]
+    if any(a.shape != sel.shape for a in rasters):
+        raise ValueError("the rasters differ in shape from the select raster")
+    with np.errstate(invalid="ignore"):
+        chosen = (sel != NODATA) & (sel > above)
+    row_ptr = np.zeros(sel.shape[0] + 1, np.uint64)
+    row_ptr[1:] = np.cumsum(chosen.sum(axis=1, dtype=np.uint64), dtype=np.uint64)
+    rows, cols = np.nonzero(chosen)                   # (row-major: ascending by row, then column)
+    return row_ptr, cols.astype(np.uint32), [a[rows, cols] for a in rasters]
+
+
+def combine_sparse(parts):
+    """The (row_ptr, col, values) results of consecutive row ranges, south to north, as the result of the whole range: the entries
+    concatenated, each part's row_ptr shifted by the entries in front of it."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no part")
+    if any(len(p[2]) != len(parts[0][2]) for p in parts):
+        raise ValueError("the parts differ in their number of values")
+    row_ptrs, shift = [np.zeros(1, np.uint64)], np.uint64(0)
+    for row_ptr, _, _ in parts:
+        row_ptr = np.asarray(row_ptr, np.uint64)
+        row_ptrs.append(row_ptr[1:] + shift)
+        shift = shift + row_ptr[-1]
+    return (np.concatenate(row_ptrs), np.concatenate([np.asarray(p[1], np.uint32) for p in parts]),
+            [np.concatenate([p[2][k] for p in parts]) for k in range(len(parts[0][2]))])
+
+
+def sparse_to_dense(row_ptr, col, values, cols, fill=NODATA):
+    """The raster [len(row_ptr) - 1, cols] that holds `values` at the entries of (row_ptr, col) and `fill` elsewhere."""
+    row_ptr, col, values = np.asarray(row_ptr, np.uint64), np.asarray(col), np.asarray(values)
+    out = np.full((len(row_ptr) - 1, int(cols)), fill, values.dtype)
+    rows = np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr.astype(np.int64)))
+    out[rows, col.astype(np.int64)] = values
+    return out
 
 
 def run_model(xml_path, make_sim=None, batch=None, output_format=".npy", max_outputs=None, log=None):

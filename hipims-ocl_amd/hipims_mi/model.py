@@ -173,7 +173,7 @@ class Model:
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
-                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None):
+                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -289,6 +289,27 @@ class Model:
             if not 1 <= factor <= 4096:
                 raise ValueError(f"overview of {what}: factor outside 1..4096")
         self.device_overviews = bool(self.overview_list) and self.device_outputs and hasattr(sim, "overview")
+        # The selected cells (no reference counterpart): the model file's <sparseTarget select="depth" above="0.01"
+        # values="depth,velocityx,velocityy" target="sparse_%t.npz"/> or `sparse` (a dict of select, above, values and optionally
+        # target); one selection per model.  At every output time the values at the cells whose `select` value lies above `above`,
+        # in CSR, written as one .npz (row_ptr, col, one array per value, shape, nodata, select, above).  On the device
+        # (Domain.sparse) wherever the output rasters are derived there; otherwise frontend.sparse of the host derivation.
+        self.sparse_spec = None
+        if sparse is not None or cfg.sparse is not None:
+            spec = dict(cfg.sparse or {}, **(sparse or {}))
+            values = spec.get("values") or [spec.get("select", "depth")]
+            values = [values] if isinstance(values, str) else list(values)
+            self.sparse_spec = spec = dict(select=str(spec.get("select", "depth")).lower(), above=float(spec.get("above", 0.0)),
+                                           values=[str(v).lower() for v in values], target=spec.get("target"))
+            codes = [frontend.data_value_code(v) for v in spec["values"]]
+            for what in [spec["select"]] + spec["values"]:
+                if frontend.data_value_code(what) not in OUT_CODES:
+                    raise ValueError(f"unknown output {what}")
+            if len(set(codes)) != len(codes):
+                raise ValueError("sparse: a value is listed twice")
+            if math.isnan(spec["above"]):
+                raise ValueError("sparse: above is a NaN")
+        self.device_sparse = self.sparse_spec is not None and self.device_outputs and hasattr(sim, "sparse")
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
 
@@ -364,6 +385,14 @@ class Model:
                 final = self.sim.download()
             for what, aggregate, factor, _, _ in self.overview_list:
                 overviews[(what, aggregate, factor)] = frontend.overview(frontend.derive_output(what, final, self.bed, self.res), factor, aggregate)
+        selection = None                                           # (row_ptr, col, [values])
+        if self.device_sparse:                                     # the selected entries only over the host link
+            selection = self.sim.sparse(self.sparse_spec["values"], self.sparse_spec["select"], self.sparse_spec["above"])
+        elif self.sparse_spec is not None:
+            if self.device_outputs or ((not self.overview_list or self.device_overviews) and not (plain or not self.cfg.targets)):
+                final = self.sim.download()
+            selection = frontend.sparse([frontend.derive_output(v, final, self.bed, self.res) for v in self.sparse_spec["values"]],
+                                        frontend.derive_output(self.sparse_spec["select"], final, self.bed, self.res), self.sparse_spec["above"])
         peaks = self.peaks()                                       # the peaks so far, written like maxdepth at every output time
         out = {}
         for k, (what, pattern) in enumerate(self.cfg.targets):
@@ -387,6 +416,14 @@ class Model:
                 ext = self.output_format if self.output_format != "xml" else (".img" if fmt == "HFA" else ".asc")
                 fname = os.path.splitext(pattern.replace("%t", str(int(round(self.current_time)))))[0] + ext
                 frontend.write_raster(os.path.join(self.cfg.target_dir, fname), arr, factor * self.res)
+        if selection is not None:
+            spec = self.sparse_spec
+            out["sparse"] = dict(row_ptr=selection[0], col=selection[1], **dict(zip(spec["values"], selection[2])))
+            if spec["target"] and self.cfg.target_dir and self.output_format:
+                os.makedirs(self.cfg.target_dir, exist_ok=True)
+                fname = os.path.splitext(spec["target"].replace("%t", str(int(round(self.current_time)))))[0] + ".npz"
+                np.savez(os.path.join(self.cfg.target_dir, fname), shape=np.array([self.rows, self.cols], np.int64), nodata=np.float64(frontend.NODATA),
+                         select=np.array(spec["select"]), above=np.float64(spec["above"]), **out["sparse"])
         self.write_probes()
         self.write_zones()
         self.outputs.append((self.current_time, out))

@@ -190,6 +190,9 @@ class HipEngine:
     def overview_shape(self, factor, row0=0, nrows=None):
         return self.domain.overview_shape(factor, row0=row0, nrows=nrows)
 
+    def sparse(self, values, select="depth", above=0.0, dtype=np.float64, row0=0, nrows=None):
+        return self.domain.sparse(values, select=select, above=above, dtype=dtype, row0=row0, nrows=nrows)
+
     def stats(self, row0=0, nrows=None):
         return self.domain.stats(row0=row0, nrows=nrows)
 
@@ -569,6 +572,15 @@ class StripRunner:
                 self.engine.overview([v for v, _ in pairs], [a for _, a in pairs], factor, dtype=dtype, row0=row0, nrows=nrows))
         parts = self._gather_parts(mine)
         return assemble_overviews(parts, [a for _, a in pairs]) if self.rank == 0 else None
+
+    def gather_sparse(self, values, select="depth", above=0.0, dtype=np.float64):
+        """The selected cells of the whole grid in CSR (Domain.sparse): every rank compacts its OWNED rows on its device, rank 0
+        concatenates the parts in rank order (frontend.combine_sparse) and gets (row_ptr, col, [one array per value]), equal to
+        the single domain's in every word; the other ranks None.  Collective."""
+        from . import frontend
+        mine = self.engine.sparse(values, select=select, above=above, dtype=dtype, row0=self.own_lo - self.local_lo, nrows=self.own_hi - self.own_lo)
+        parts = self._gather_parts(mine)
+        return frontend.combine_sparse(parts) if self.rank == 0 else None
 
     def _gather_parts(self, mine):
         """Every rank's `mine` in rank order on rank 0, None on the other ranks: pickled over the process group, which a single

@@ -211,6 +211,40 @@ int hp_overview_shape(hp_domain_t* d, int factor, int64_t row0, int64_t nrows,
 int hp_domain_overview(hp_domain_t* d, const int* values, const int* aggregates, int count,
                        int factor, int element_bytes, void* const* rasters,
                        int64_t row0, int64_t nrows);
+/* The same nine values at the SELECTED cells only, at full resolution, in CSR: a flood map is mostly -9999, and what a user
+ * takes away from an output time is depth and velocity where there is water.  Only the selected share of a raster's bytes crosses
+ * the host link.  No reference counterpart.
+ *   Selection.  Cell (x, y) of rows [row0, row0 + nrows) of the LOCAL array is selected iff v, the value select_value (HP_OUT_*)
+ * of that cell exactly as hp_domain_derive forms it in fp64 before it rounds (one definition in csrc/hp_output.hpp serves both),
+ * satisfies v != -9999.0 && v > above.  A NaN v fails the comparison.  above may be -inf (HP_OUT_DISCHARGE_X, -inf selects every
+ * cell: that value is never NODATA); typical use is HP_OUT_DEPTH, 0.01.
+ *   Result.  row_ptr[0 .. nrows]: row_ptr[0] = 0 and row_ptr[r + 1] - row_ptr[r] = the selected cells of local row row0 + r;
+ * *selected = row_ptr[nrows].  col[k] is the column of entry k; entries ascend by (row, column).  rasters[i][k] is value values[i]
+ * of entry k: element_bytes 8 delivers the fp64 value, 4 the same value rounded once -- the elements hp_domain_derive stores.  A
+ * selected cell's other values may themselves be -9999 (maxdepth at a wall): they are delivered as they are.  Each value at most
+ * once; count is 1..9.
+ *   Capacity.  row_ptr and *selected are always delivered.  If *selected > capacity, nothing is written to col or rasters and the
+ * call still returns HP_OK: the caller grows its arrays and calls again.  capacity == 0 with col and rasters NULL is the counting
+ * call.
+ *   The call BLOCKS, like hp_domain_stats: behind the scan the host reads row_ptr, and only then are the copies queued, of exactly
+ * *selected entries each.  On return row_ptr and *selected are valid; col and rasters are valid after hp_sync() -- their copies
+ * are enqueued on the domain's stream and the host memory must stay alive until then, as for hp_domain_derive.
+ *   Everything else follows hp_domain_overview: reads the buffer hp_domain_download(HP_ARRAY_STATE) reads, in stream order behind
+ * whatever is queued, and changes nothing the steps depend on.  What is accumulated is integers (a ballot per 64 columns, its
+ * population counts, their prefix sums), so the result depends neither on the launch shape nor on how a large request is cut into
+ * runs nor on how the grid is cut into strips (frontend.sparse restates it in NumPy, frontend.combine_sparse concatenates the parts
+ * of consecutive row ranges).  The selection words and offsets (16 B per 64 cells) and the entries (4 + count * element_bytes B
+ * each) come out of the same bounded scratch (256 MiB): a range whose words alone exceed it is HP_ERR_UNSUPPORTED, entries that
+ * exceed what is left are worked through in runs of whole rows (a row larger than that in runs of entries).  If an allocation
+ * fails the call returns HP_ERR_HIP and the domain stays usable.  Argument errors -- a NULL selected or row_ptr; capacity > 0 with
+ * a NULL col, rasters or rasters[i]; an unknown or repeated value; an unknown select_value; a bad element_bytes; a NaN above; a
+ * row range outside the array; cols >= 2^32 -- are HP_ERR_INVALID before any device call; between hp_step_begin and hp_step_end
+ * the call returns HP_ERR_STATE; nrows == 0 is HP_OK with *selected = 0 and row_ptr[0] = 0. */
+int hp_domain_sparse(hp_domain_t* d, int select_value, double above,
+                     const int* values, int count, int element_bytes,
+                     uint64_t capacity, uint64_t* selected,
+                     uint64_t* row_ptr, uint32_t* col, void* const* rasters,
+                     int64_t row0, int64_t nrows);
 /* Statistics of rows [row0, row0 + nrows) of the same buffer: what the reference's progress log takes from
  * CDomainCartesian::getVolume (CDomainCartesian.cpp:743-760, CSchemeGodunov.cpp:1060, CModel.cpp:1127) and what a user
  * reads next to it.  A deterministic two-stage reduction (no floating-point atomics: the same state gives the same bits). */
