@@ -10,6 +10,7 @@
 #include "hp_zones.hpp"
 #include "hp_overview.hpp"
 #include "hp_sparse.hpp"
+#include "hp_bed.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <atomic>
@@ -102,6 +103,29 @@ struct ProbeRecorder {
 struct ZoneRecorder {
 	RecordLog        log;
 	double           flood_depth = 0.0;
+};
+
+// the moving bed (hp_bed.hpp; hp_bed_*): nothing of it exists while the domain has no shape.  Not an observer: an apply writes the
+// bed and the state -- by contract exactly what the two uploads of the host round trip it replaces write
+struct BedShapes {
+	unsigned         shapes = 0;
+	void*            block = nullptr;                 // the lists, one allocation (BedLists points into it)
+	BedLists         lists = {};
+	BedBlock*        info = nullptr;                  // device: what the applies leave for hp_bed_info
+	uint64_t         applies = 0;                     // applies queued since the first shape was added (its parity picks the counter word)
+	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's beds belong to one epoch
+	// host copies of the lists: a new shape rewrites the device block as a whole
+	std::vector<uint64_t> listed;                     // GLOBAL ids of every cell of every shape, sorted: the repeated-cell check
+	std::vector<uint64_t> cells;                      // LOCAL ids, shape after shape
+	std::vector<double>   target;
+	std::vector<unsigned char> shape_of;
+	std::vector<double>   series;
+	std::vector<unsigned> series_off = {0u};
+	// hp_state_save's copy of the bed at the listed cells
+	void*            saved = nullptr;
+	size_t           saved_room = 0;                  // cells it holds
+	bool             saved_taken = false;             // a checkpoint exists (with or without shapes) ...
+	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
 } // namespace
@@ -219,6 +243,7 @@ struct hp_domain {
 	PeakTracker      peaks;
 	ProbeRecorder    probes;
 	ZoneRecorder     zones;
+	BedShapes        beds;
 };
 
 namespace {

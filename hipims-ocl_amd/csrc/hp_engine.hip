@@ -1006,6 +1006,90 @@ int check_domain(hp_domain* d)
 	return HP_OK;
 }
 
+// ---- the moving bed (hp_bed.hpp): the device block of the shapes' lists, and what a checkpoint does for the listed cells ----
+static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, "hp_bed_*_t layout");
+// [cells: n x 8 | target: n x 8 | series: pairs x 16 | base: n elements, to 8 | series_off: (shapes + 1) x 4, to 8 | shape_of: n]
+struct BedLayout { size_t cells, target, series, base, series_off, shape_of, bytes; };
+BedLayout bed_layout(const size_t n, const size_t pairs, const size_t shapes, const size_t esize)
+{
+	BedLayout l;
+	l.cells = 0;
+	l.target = l.cells + n * 8;
+	l.series = l.target + n * 8;
+	l.base = l.series + pairs * 16;
+	l.series_off = l.base + (n * esize + 7) / 8 * 8;
+	l.shape_of = l.series_off + ((shapes + 1) * 4 + 7) / 8 * 8;
+	l.bytes = l.shape_of + std::max<size_t>(n, 1);
+	return l;
+}
+BedLists bed_lists(void* block, const BedLayout& l, const size_t n, const unsigned shapes)
+{
+	char* b = (char*)block;
+	BedLists L = {};
+	L.cells = (const unsigned long long*)(b + l.cells);
+	L.target = (const double*)(b + l.target);
+	L.series = (const double*)(b + l.series);
+	L.base = b + l.base;
+	L.series_off = (const unsigned*)(b + l.series_off);
+	L.shape_of = (const unsigned char*)(b + l.shape_of);
+	L.count = n;
+	L.shapes = shapes;
+	return L;
+}
+void bed_destroy(hp_domain* d) { hipFree(d->beds.block); hipFree(d->beds.info); hipFree(d->beds.saved); }
+
+// hp_state_save, before it touches anything: room for the bed at the listed cells (peaks_save_reserve's rule: a failure leaves the
+// checkpoint before it untouched)
+int bed_save_reserve(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	if (!B.shapes || B.lists.count <= B.saved_room) return HP_OK;
+	void* grown = nullptr;
+	int rc = alloc_or_fail(&grown, (size_t)B.lists.count * d->esize, "hp_state_save: cannot allocate the copy of the listed cells' bed: ");
+	if (rc != HP_OK) return rc;
+	if (B.saved) {
+		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
+		hipFree(B.saved);
+	}
+	B.saved = grown;
+	B.saved_room = (size_t)B.lists.count;
+	return HP_OK;
+}
+// ... and behind the state's copies: hp_state_restore brings back neither the bed nor the boundary list, and levels of one bed over
+// another are no state
+int bed_save(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	B.saved_taken = true;
+	B.saved_epoch = B.epoch;
+	if (!B.shapes || !B.lists.count) return HP_OK;
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (const T*)d->bed, B.lists.cells, 0ull, B.lists.count, (T*)B.saved);
+	});
+	HIP_TRY(hipGetLastError());
+	return HP_OK;
+}
+// hp_state_restore, behind the state's copies
+int bed_restore(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	if (!B.saved_taken) return HP_OK;
+	if (B.saved_epoch != B.epoch) {                                           // (the probe recorder's rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: bed shapes were added or cleared after the state was saved: the bed is left as it is");
+		return HP_OK;
+	}
+	if (!B.shapes) return HP_OK;
+	d->facts.boundaries_or_bed_changed();
+	if (B.lists.count) {
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			hipLaunchKernelGGL((bed_scatter<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (T*)d->bed, B.lists.cells, B.lists.count, (const T*)B.saved);
+		});
+		HIP_TRY(hipGetLastError());
+	}
+	d->facts.bed_uploaded();
+	return HP_OK;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -1188,7 +1272,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES);
+	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); bed_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1256,6 +1340,7 @@ int hp_state_save(hp_domain_t* d)
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_save between hp_step_begin and hp_step_end");
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
 	if ((rc = peaks_save_reserve(d)) != HP_OK) return rc;            // (first: a failure leaves the checkpoint before it untouched)
+	if ((rc = bed_save_reserve(d)) != HP_OK) return rc;
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1269,7 +1354,7 @@ int hp_state_save(hp_domain_t* d)
 	if ((rc = peaks_save(d)) != HP_OK) return rc;
 	log_save(d, PROBES);
 	log_save(d, ZONES);
-	return HP_OK;
+	return bed_save(d);
 }
 
 int hp_state_restore(hp_domain_t* d)
@@ -1304,6 +1389,184 @@ int hp_state_restore(hp_domain_t* d)
 	if ((rc = peaks_restore(d)) != HP_OK) return rc;
 	log_restore(d, PROBES);
 	log_restore(d, ZONES);
+	return bed_restore(d);
+}
+
+// ---- the moving bed (hp_bed.hpp) ----
+int hp_bed_shape_add(hp_domain_t* d, const hp_bed_shape_desc_t* desc)
+{
+	// argument checks first: none of them touches the device, and those that do not need the domain come before it
+	const std::string who = "hp_bed_shape_add";
+	if (!desc) return fail(HP_ERR_INVALID, who + ": desc == NULL");
+	if (desc->struct_size != sizeof(hp_bed_shape_desc_t)) return fail(HP_ERR_INVALID, "hp_bed_shape_desc_t size mismatch (ABI)");
+	if (!desc->cells || !desc->target || !desc->series) return fail(HP_ERR_INVALID, who + ": cells / target / series == NULL");
+	if (desc->series_entries < 1 || desc->series_entries > BED_MAX_SERIES) return fail(HP_ERR_INVALID, who + ": series_entries outside 1..4096");
+	if (desc->cell_count < 1 || desc->cell_count > BED_MAX_CELLS) return fail(HP_ERR_INVALID, who + ": cell_count outside 1..1048576");
+	const uint64_t n = desc->cell_count;
+	const unsigned m = desc->series_entries;
+	for (uint64_t k = 0; k < n; ++k)
+		if (!std::isfinite(desc->target[k]) || std::fabs(desc->target[k]) > BED_MAX_LEVEL)
+			return fail(HP_ERR_INVALID, who + ": target " + std::to_string(k) + " is not a finite elevation of at most 9999");
+	for (unsigned k = 0; k < m; ++k) {
+		const double t = desc->series[2 * k], f = desc->series[2 * k + 1];
+		if (!std::isfinite(t) || (k > 0 && !(t > desc->series[2 * k - 2])))
+			return fail(HP_ERR_INVALID, who + ": series entry " + std::to_string(k) + ": times must be finite and strictly increasing");
+		if (!(f >= 0.0 && f <= 1.0)) return fail(HP_ERR_INVALID, who + ": series entry " + std::to_string(k) + ": fraction outside [0, 1]");
+	}
+	std::vector<uint64_t> sorted(desc->cells, desc->cells + n);
+	std::sort(sorted.begin(), sorted.end());
+	{
+		const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+		if (twice != sorted.end()) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(*twice) + " is listed twice");
+	}
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	BedShapes& B = d->beds;
+	const uint64_t cols = (uint64_t)d->desc.cols;
+	if (sorted.back() >= cols * (uint64_t)d->desc.global_rows) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(sorted.back()) + " lies outside the grid");
+	if (B.shapes >= BED_MAX_SHAPES) return fail(HP_ERR_INVALID, who + ": more than 64 shapes");
+	if (B.listed.size() + n > BED_MAX_CELLS) return fail(HP_ERR_INVALID, who + ": more than 1048576 cells over all shapes");
+	std::vector<uint64_t> listed(B.listed.size() + (size_t)n);
+	std::merge(B.listed.begin(), B.listed.end(), sorted.begin(), sorted.end(), listed.begin());
+	{
+		const auto twice = std::adjacent_find(listed.begin(), listed.end());
+		if (twice != listed.end()) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(*twice) + " is listed twice (another shape has it)");
+	}
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	// this strip's share: the cells whose row lies in its local array, ghost rows included
+	std::vector<uint64_t> cells(B.cells);
+	std::vector<double> target(B.target);
+	for (uint64_t k = 0; k < n; ++k) {
+		const uint64_t gy = desc->cells[k] / cols, x = desc->cells[k] - gy * cols;
+		if (gy < (uint64_t)d->desc.row_offset || gy >= (uint64_t)(d->desc.row_offset + d->desc.rows)) continue;
+		cells.push_back((gy - (uint64_t)d->desc.row_offset) * cols + x);
+		target.push_back(desc->target[k]);
+	}
+	const size_t n_old = B.cells.size(), n_all = cells.size(), pairs_old = B.series.size() / 2, pairs_all = pairs_old + m;
+	const unsigned shapes = B.shapes + 1;
+	// the new block first: if it cannot be had, the domain keeps the shapes it has
+	const BedLayout l = bed_layout(n_all, pairs_all, shapes, d->esize);
+	void* fresh = nullptr;
+	if ((rc = alloc_or_fail(&fresh, l.bytes, who + ": cannot allocate the lists: ")) != HP_OK) return rc;
+	BedBlock* info = B.info;
+	if (!info) {
+		if ((rc = alloc_or_fail((void**)&info, sizeof(BedBlock), who + ": cannot allocate the counters: ")) != HP_OK) { hipFree(fresh); return rc; }
+	}
+	std::vector<unsigned char> image(l.bytes, 0);
+	if (n_all) {
+		std::memcpy(image.data() + l.cells, cells.data(), n_all * 8);
+		std::memcpy(image.data() + l.target, target.data(), n_all * 8);
+		if (n_old) std::memcpy(image.data() + l.shape_of, B.shape_of.data(), n_old);
+		std::memset(image.data() + l.shape_of + n_old, (int)B.shapes, n_all - n_old);
+	}
+	if (pairs_old) std::memcpy(image.data() + l.series, B.series.data(), pairs_old * 16);
+	std::memcpy(image.data() + l.series + pairs_old * 16, desc->series, (size_t)m * 16);
+	std::memcpy(image.data() + l.series_off, B.series_off.data(), (size_t)shapes * 4);
+	const unsigned end = (unsigned)pairs_all;
+	std::memcpy(image.data() + l.series_off + (size_t)shapes * 4, &end, 4);
+	const BedLists L = bed_lists(fresh, l, n_all, shapes);
+	hipError_t e = hipMemcpyAsync(fresh, image.data(), l.bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess && !B.info) e = hipMemsetAsync(info, 0, sizeof(BedBlock), d->stream);
+	// the base of the shapes that are there moves over; the new shape's is the bed as it is now, gathered on the domain's stream
+	if (e == hipSuccess && n_old) e = hipMemcpyAsync((char*)fresh + l.base, B.lists.base, n_old * d->esize, hipMemcpyDeviceToDevice, d->stream);
+	if (e == hipSuccess && n_all > n_old) {
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks(n_all - n_old)), dim3(256), 0, d->stream, (const T*)d->bed, L.cells, (unsigned long long)n_old,
+			                   (unsigned long long)(n_all - n_old), (T*)((char*)fresh + l.base));
+		});
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (queued applies still read the old block; the caller's arrays are free on return)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(fresh);
+		if (!B.info) hipFree(info);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the lists: " + hipGetErrorString(e));
+	}
+	hipFree(B.block);
+	B.block = fresh;
+	B.info = info;
+	B.lists = L;
+	B.shape_of.resize(n_all, (unsigned char)B.shapes);
+	B.shapes = shapes;
+	B.listed.swap(listed);
+	B.cells.swap(cells);
+	B.target.swap(target);
+	B.series.insert(B.series.end(), desc->series, desc->series + 2 * (size_t)m);
+	B.series_off.push_back(end);
+	++B.epoch;
+	return HP_OK;
+}
+
+int hp_bed_shapes_clear(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	BedShapes& B = d->beds;
+	if (!B.shapes) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_shapes_clear between hp_step_begin and hp_step_end");
+	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (queued applies still use the lists)
+	bed_destroy(d);
+	BedShapes none;
+	none.epoch = B.epoch + 1;
+	none.saved_taken = B.saved_taken;
+	none.saved_epoch = B.saved_epoch;
+	B = none;
+	return HP_OK;
+}
+
+// By contract exactly the host round trip it replaces -- download state and bed, move the bed and shift the levels, hp_domain_upload
+// of the bed, hp_domain_upload of the state --: the kernel patches the buffer hp_domain_download(HP_ARRAY_STATE) reads, and what
+// follows it is what the two uploads do, in their order (hp_domain_upload above).
+int hp_bed_apply(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: an apply never patches a state that is re-run)
+	if (rc != HP_OK) return rc;
+	BedShapes& B = d->beds;
+	if (!B.shapes) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_apply between hp_step_begin and hp_step_end");
+	if (d->facts->ghost_valid != d->ghost_rows)
+		return fail(HP_ERR_STATE, "hp_bed_apply: the strip's ghost rows are not all valid (two reaches after an odd number of iterations): apply after an even batch");
+	const int cur = d->facts->use_alt;
+	const unsigned slot = (unsigned)(B.applies & 1u);
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((bed_apply<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (State4<T>*)d->state[cur], (T*)d->bed,
+		                   (const Scalars<T>*)d->scalars, B.lists, B.info, slot);
+	});
+	HIP_TRY(hipGetLastError());
+	++B.applies;
+	d->facts.boundaries_or_bed_changed();
+	d->facts.buffers_written_outside();
+	d->facts.bed_uploaded();
+	// both ping-pong buffers hold the patched state, as after hp_domain_upload(HP_ARRAY_STATE)
+	HIP_TRY(hipMemcpyAsync(d->state[cur ^ 1], d->state[cur], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
+	d->tune_phase = 0;
+	d->facts.full_state_uploaded(d->ghost_rows);
+	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
+	return HP_OK;
+}
+
+int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out)
+{
+	if (!out) return fail(HP_ERR_INVALID, "hp_bed_info: out == NULL");
+	if (out->struct_size != sizeof(hp_bed_info_t)) return fail(HP_ERR_INVALID, "hp_bed_info_t size mismatch (ABI)");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	const BedShapes& B = d->beds;
+	out->shapes = B.shapes;
+	out->cells_local = B.lists.count;
+	out->applies = B.applies;
+	out->changed_last = out->changed_total = 0;
+	out->t_last = 0.0;
+	if (!B.shapes) return HP_OK;
+	BedBlock host;
+	HIP_TRY(hipMemcpyAsync(&host, B.info, sizeof host, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	if (B.applies) out->changed_last = host.changed[(B.applies - 1) & 1u];
+	out->changed_total = host.changed_total;
+	out->t_last = host.t_last;
 	return HP_OK;
 }
 

@@ -49,6 +49,7 @@ EXPORTS = [
     "hp_peaks_enable", "hp_peaks_disable", "hp_peaks_reset", "hp_peaks_sample", "hp_peaks_read", "hp_peaks_info",
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
+    "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -129,6 +130,16 @@ class ZonesDesc(C.Structure):
                 ("zone_of_cell", C.POINTER(C.c_uint16)), ("flood_depth", C.c_double)]
 
 
+class BedShapeDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("series_entries", C.c_uint32), ("cell_count", C.c_uint64),
+                ("cells", C.POINTER(C.c_uint64)), ("target", C.POINTER(C.c_double)), ("series", C.POINTER(C.c_double))]
+
+
+class BedInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("shapes", C.c_uint32), ("cells_local", C.c_uint64), ("applies", C.c_uint64),
+                ("changed_last", C.c_uint64), ("changed_total", C.c_uint64), ("t_last", C.c_double)]
+
+
 _lib = None
 
 
@@ -192,6 +203,11 @@ def load_library(path: str | None = None):
         lib.hp_zones_sample.argtypes = [C.c_void_p]
         lib.hp_zones_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.hp_zones_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_bed_shape_add"):                # (absent from older builds, as above)
+        lib.hp_bed_shape_add.argtypes = [C.c_void_p, C.POINTER(BedShapeDesc)]
+        lib.hp_bed_shapes_clear.argtypes = [C.c_void_p]
+        lib.hp_bed_apply.argtypes = [C.c_void_p]
+        lib.hp_bed_info.argtypes = [C.c_void_p, C.POINTER(BedInfo)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -828,6 +844,38 @@ class Domain:
         _check(self.lib, self.lib.hp_state_restore(self.h), "hp_state_restore")
         self._probe_log.restored()
         self._zone_log.restored()
+
+    # ---- the moving bed (hp_bed_*): the bed at listed cells follows a schedule, applied between batches on the device ----
+    def bed_shape_add(self, cells, target, series):
+        """One shape: `cells` are flat ids y * cols + x of the GLOBAL grid or (x, y) pairs, `target` one elevation per cell (or one
+        for all of them), `series` [n, 2] rows of (time, fraction).  The shape's base is the bed as it is now."""
+        c = np.asarray(cells)
+        if c.ndim == 2 and c.shape[1] == 2:
+            c = c.astype(np.int64)
+            if c.size and (c.min() < 0 or (c[:, 0] >= self.cols).any()):
+                raise ValueError("a bed shape's cell lies outside the grid")
+            c = c[:, 1] * self.cols + c[:, 0]
+        c = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(target, dtype=np.float64), c.shape))
+        s = np.ascontiguousarray(series, dtype=np.float64).reshape(-1, 2)
+        desc = BedShapeDesc(C.sizeof(BedShapeDesc), len(s), c.size, c.ctypes.data_as(C.POINTER(C.c_uint64)),
+                            t.ctypes.data_as(C.POINTER(C.c_double)), s.ctypes.data_as(C.POINTER(C.c_double)))
+        _check(self.lib, self.lib.hp_bed_shape_add(self.h, C.byref(desc)), "hp_bed_shape_add")
+
+    def bed_shapes_clear(self):
+        _check(self.lib, self.lib.hp_bed_shapes_clear(self.h), "hp_bed_shapes_clear")
+
+    def bed_apply(self):
+        """Move the bed of the listed cells to where the shapes' series put it at the device's own time: one launch and one
+        device copy of the state on the domain's stream, equal in every bit to download, frontend.BedShapes.apply and upload of
+        bed and state.  Does not block."""
+        _check(self.lib, self.lib.hp_bed_apply(self.h), "hp_bed_apply")
+
+    def bed_info(self):
+        """dict(shapes, cells_local, applies, changed_last, changed_total, t_last); blocks."""
+        info = BedInfo(C.sizeof(BedInfo))
+        _check(self.lib, self.lib.hp_bed_info(self.h, C.byref(info)), "hp_bed_info")
+        return {k: getattr(info, k) for k, _ in BedInfo._fields_ if k != "struct_size"}
 
     # ---- boundaries ----
     def add_uniform(self, definition, series, interval, length):

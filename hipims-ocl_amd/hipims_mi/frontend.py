@@ -118,6 +118,7 @@ class Configuration:
     sections: list = field(default_factory=list)   # (name, x0, y0, x1, y1): <section> elements, cell indices
     overviews: list = field(default_factory=list)  # (value, aggregate, factor, target pattern, format): <dataTarget overview="...">
     sparse: dict = None                            # select, above, values, target pattern: the <sparseTarget> element (the last one wins)
+    bed_shapes: list = field(default_factory=list)  # dict(name, cells [(x, y)], target [n], series [m, 2]): <bedShape> elements
 
 
 def _params(elem):
@@ -174,6 +175,12 @@ def parse_configuration(xml_path):
         cfg.gauges.append((g.get("name") or f"gauge{k}", int(g.get("x")), int(g.get("y"))))
     for k, e in enumerate(data.findall("section")):
         cfg.sections.append((e.get("name") or f"section{k}", int(e.get("x0")), int(e.get("y0")), int(e.get("x1")), int(e.get("y1"))))
+    # the moving bed's elements (no reference counterpart): mapFile rows are x, y, target elevation; source rows time, fraction
+    for k, e in enumerate(data.findall("bedShape")):
+        cells = _read_csv(os.path.join(cfg.source_dir, e.get("mapFile"))).reshape(-1, 3)
+        series = _read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2)
+        cfg.bed_shapes.append(dict(name=e.get("name") or f"bedShape{k}", cells=[(int(r[0]), int(r[1])) for r in cells],
+                                   target=cells[:, 2].copy(), series=series))
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -605,6 +612,119 @@ def write_zone_file(target_dir, series, dx, zone_names=None):
                 f.write(",".join([repr(float(t)), name, str(int(series["cells"][n, k])), repr(float(int(series["wet"][n, k]) * area)),
                                   repr(float(int(series["flooded"][n, k]) * area)), repr(float(series["volume"][n, k])),
                                   repr(float(series["max_depth"][n, k])), repr(float(series["max_speed"][n, k]))]) + "\n")
+
+
+class BedShapes:
+    """The moving bed on the host (hp_bed_shape_add / hp_bed_apply restated in NumPy, in exactly the kernel's operation order --
+    csrc/hp_bed.hpp): shapes of cells with a target elevation each and one (time, fraction) series per shape.  `apply` acts in
+    place on state[rows, cols, 4] and bed[rows, cols]; their dtype decides the single rounding.  All arithmetic is fp64 -- separate,
+    correctly rounded multiplies, adds and divides -- so the arrays equal the device's bit for bit.  The GPU tests' reference, and
+    what engines without the device path run (Model with the oracle's simulation objects)."""
+
+    MAX_SHAPES, MAX_SERIES, MAX_CELLS, MAX_LEVEL = 64, 4096, 1048576, 9999.0
+
+    def __init__(self, rows, cols):
+        self.rows, self.cols = int(rows), int(cols)
+        self.shapes = []                                # (flat cells, target, series, base or None)
+        self.applies = 0
+
+    def add(self, cells, target, series, bed=None):
+        """`cells`: flat ids y * cols + x or (x, y) pairs.  `bed`: the bed the shape's base is captured from now (as the device does);
+        without it the base is taken from the bed of the first apply."""
+        c = np.asarray(cells)
+        if c.ndim == 2 and c.shape[1] == 2:
+            c = c[:, 1].astype(np.int64) * self.cols + c[:, 0].astype(np.int64)
+        c = np.asarray(c, dtype=np.int64).reshape(-1)
+        t = np.array(np.broadcast_to(np.asarray(target, dtype=np.float64), c.shape))
+        s = np.array(series, dtype=np.float64).reshape(-1, 2)
+        if not 1 <= len(s) <= self.MAX_SERIES:
+            raise ValueError("series entries outside 1..4096")
+        if not 1 <= c.size or sum(len(x[0]) for x in self.shapes) + c.size > self.MAX_CELLS:
+            raise ValueError("cell count outside 1..1048576 over all shapes")
+        if len(self.shapes) >= self.MAX_SHAPES:
+            raise ValueError("more than 64 shapes")
+        if not np.isfinite(t).all() or (np.abs(t) > self.MAX_LEVEL).any():
+            raise ValueError("a target is not a finite elevation of at most 9999")
+        if not np.isfinite(s[:, 0]).all() or not (np.diff(s[:, 0]) > 0).all():
+            raise ValueError("times must be finite and strictly increasing")
+        if not ((s[:, 1] >= 0.0) & (s[:, 1] <= 1.0)).all():
+            raise ValueError("a fraction lies outside [0, 1]")
+        if c.min() < 0 or c.max() >= self.rows * self.cols:
+            raise ValueError("a cell lies outside the grid")
+        everyone = np.concatenate([x[0] for x in self.shapes] + [c])
+        uniq, counts = np.unique(everyone, return_counts=True)
+        if (counts > 1).any():
+            raise ValueError(f"cell {int(uniq[counts > 1][0])} is listed twice")
+        base = None if bed is None else np.asarray(bed).reshape(-1)[c].astype(np.float64)
+        self.shapes.append([c, t, s, base])
+
+    @staticmethod
+    def series_fraction(series, t):
+        """bed_fraction of csrc/hp_bed.hpp: Python floats are IEEE doubles and nothing is fused."""
+        s, t = np.asarray(series, dtype=np.float64).reshape(-1, 2), float(t)
+        n = len(s)
+        if not t > float(s[0, 0]):
+            return float(s[0, 1])
+        if t >= float(s[n - 1, 0]):
+            return float(s[n - 1, 1])
+        lo, hi = 0, n - 1
+        while hi - lo > 1:
+            mid = lo + (hi - lo) // 2
+            if float(s[mid, 0]) <= t:
+                lo = mid
+            else:
+                hi = mid
+        t0, f0, t1, f1 = float(s[lo, 0]), float(s[lo, 1]), float(s[hi, 0]), float(s[hi, 1])
+        df = f1 - f0
+        part = (t - t0) / (t1 - t0)
+        step = df * part
+        return f0 + step
+
+    @staticmethod
+    def level(base, target, f):
+        """bed_level of csrc/hp_bed.hpp on fp64 arrays: the new bed before it is rounded to the domain's precision."""
+        base, target = np.asarray(base, dtype=np.float64), np.asarray(target, dtype=np.float64)
+        if f <= 0.0:
+            return base.copy()
+        if f >= 1.0:
+            return target.copy()
+        rise = target - base
+        part = np.float64(f) * rise
+        return base + part
+
+    def fraction(self, t):
+        """One fraction per shape at time t."""
+        return [self.series_fraction(s, t) for _, _, s, _ in self.shapes]
+
+    def apply(self, state, bed, t):
+        """One apply at time t, in place; returns the number of cells changed (skipped cells do not count)."""
+        if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or state.dtype != bed.dtype or \
+                not (state.flags.c_contiguous and bed.flags.c_contiguous):
+            raise ValueError("state must be [rows, cols, 4] and bed [rows, cols], contiguous and of one dtype")
+        real = bed.dtype.type
+        st, zb = state.reshape(-1, 4), bed.reshape(-1)
+        changed = 0
+        for shape in self.shapes:
+            c, target, series, base = shape
+            if base is None:
+                base = shape[3] = zb[c].astype(np.float64)
+            f = self.series_fraction(series, t)
+            b1_ = self.level(base, target, f).astype(real)
+            b0_ = zb[c]
+            b0, b1 = b0_.astype(np.float64), b1_.astype(np.float64)
+            z0, zmax0 = st[c, 0].astype(np.float64), st[c, 1].astype(np.float64)
+            with np.errstate(invalid="ignore"):
+                move = (zmax0 > -9999.0) & (b0 <= 9999.0) & ~(b1_ == b0_)
+                depth = z0 - b0
+                z1 = b1 + depth
+                zmax1 = np.where(zmax0 > z1, zmax0, z1)
+            k = c[move]
+            st[k, 0] = z1[move].astype(real)
+            st[k, 1] = zmax1[move].astype(real)
+            zb[k] = b1_[move]
+            changed += int(move.sum())
+        self.applies += 1
+        return changed
 
 
 def derive_output(what, state, bed, resolution=1.0):

@@ -53,6 +53,7 @@ class SchemeDriver:
         self.running = False
         self.peak_sampler = None                                   # Model's: called after every batch queued (the peak tracker)
         self.samplers = []                                         # ... and these after it, in order (the probe recorder)
+        self.bed_stage = None                                      # Model's: called with (t_before, t_after) behind every batch, in front of the samplers (the moving bed)
         self.prepare_simulation()
 
     # ---- adapters: Domain (HIP engine) and OracleSim spell a few things differently ----
@@ -133,6 +134,7 @@ class SchemeDriver:
             self.queue_addition_size = max(1, self.queue_addition_size)
         self.batch_started = real_time
         self.running = True
+        stats_read = False
         try:
             if self.update_target:                                 # :1163-1209
                 self.update_target = False
@@ -150,15 +152,21 @@ class SchemeDriver:
                 self.override_timestep = False
             if self.iterations_since_sync < self.rollback_limit and self.current_time < self.target_time:   # :1285-1304
                 n = self.queue_addition_size
+                t_before = self.current_time
                 self._call("step_batch", "run")(n)
                 self.iterations_since_sync += n
                 self.iterations += n
                 self.cells_calculated += n * self.cells            # :1299: cols x rows per iteration, skipped or not
+                if self.bed_stage is not None:                     # the bed moves before anything samples: the statistics are read here
+                    self.read_key_statistics()                     # instead of below (an apply changes none of them)
+                    stats_read = True
+                    self.bed_stage(t_before, self.current_time)
                 if self.peak_sampler is not None:                  # one sample per batch, queued behind it (no reference counterpart)
                     self.peak_sampler()
                 for sampler in self.samplers:
                     sampler()
-            self.read_key_statistics()                             # :1309-1313, blockUntilFinished, :1350
+            if not stats_read:
+                self.read_key_statistics()                         # :1309-1313, blockUntilFinished, :1350
         finally:
             self.running = False
 
@@ -173,7 +181,7 @@ class Model:
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
-                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None):
+                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -310,8 +318,46 @@ class Model:
             if math.isnan(spec["above"]):
                 raise ValueError("sparse: above is a NaN")
         self.device_sparse = self.sparse_spec is not None and self.device_outputs and hasattr(sim, "sparse")
+        # The moving bed (no reference counterpart): the model file's <bedShape name="breach" mapFile="cells.csv" source="progress.csv"/>
+        # elements (mapFile rows: x, y, target elevation; source rows: time, fraction) and the dict(cells=, target=, series=) entries
+        # of `bed_shapes`.  One apply after the initial upload, then one behind every batch in which a shape can have moved, always
+        # in front of the observers' samples: a sample sees the bed of its time.  On the device (Domain.bed_apply) wherever the
+        # engine has it; otherwise frontend.BedShapes on the downloaded state, uploaded again.
+        self.bed_shape_list = [dict(b) for b in list(cfg.bed_shapes) + list(bed_shapes or [])]
+        self.host_beds, self.device_beds, self.bed_applies = None, False, 0
+        if self.bed_shape_list:
+            self.device_beds = hasattr(sim, "bed_apply")
+            if not self.device_beds:
+                self.host_beds = frontend.BedShapes(self.rows, self.cols)
+                self._bed_real = np.ascontiguousarray(self.bed, dtype=sim.download().dtype)      # the bed as the engine holds it
+            for b in self.bed_shape_list:
+                b["series"] = np.array(b["series"], dtype=np.float64).reshape(-1, 2)
+                if self.device_beds:
+                    sim.bed_shape_add(b["cells"], b["target"], b["series"])
+                else:
+                    self.host_beds.add(b["cells"], b["target"], b["series"], bed=self._bed_real)
+            self.apply_bed()
+            self.scheme.bed_stage = self.bed_stage
         self.domain_stats = []                                     # [(time, stats())]: start, then every output time
         self.log_domain_stats(initial=True)
+
+    def bed_stage(self, t_before, t_after):
+        """Behind a batch from t_before to t_after: an apply iff some shape can have moved in it."""
+        if any(t_after > b["series"][0, 0] and t_before < b["series"][-1, 0] for b in self.bed_shape_list):
+            self.apply_bed()
+
+    def apply_bed(self):
+        if self.device_beds:
+            self.sim.bed_apply()
+            if not self.device_outputs:                            # whatever is derived on the host takes the bed the domain holds now
+                self.bed = self.sim.download(1).astype(np.float64)
+        else:
+            s = self.scheme._call("read_scalars", "scalars")()
+            state = np.ascontiguousarray(self.sim.download())
+            self.host_beds.apply(state, self._bed_real, s["time"] if "time" in s else s["t"])
+            self.sim.upload(state, self._bed_real)                 # (always: an apply IS the two uploads, whatever it moved)
+            self.bed = self._bed_real.astype(np.float64)
+        self.bed_applies += 1
 
     def sample_peaks_on_host(self):
         s = self.scheme._call("read_scalars", "scalars")()
@@ -430,7 +476,8 @@ class Model:
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()
         if self.log:
-            self.log(f"Output files written at {seconds_to_time(self.current_time)} ({len(out)} rasters)")
+            applies = f", {self.bed_applies} bed applies" if self.bed_shape_list else ""
+            self.log(f"Output files written at {seconds_to_time(self.current_time)} ({len(out)} rasters{applies})")
         self.log_domain_stats()
         return True
 

@@ -196,6 +196,20 @@ class HipEngine:
     def stats(self, row0=0, nrows=None):
         return self.domain.stats(row0=row0, nrows=nrows)
 
+    # the moving bed (Domain.bed_*)
+    def bed_shape_add(self, cells, target, series):
+        self.domain.bed_shape_add(cells, target, series)
+
+    def bed_shapes_clear(self):
+        self.domain.bed_shapes_clear()
+
+    def bed_apply(self):
+        self.domain.bed_apply()
+
+    def download_bed(self):
+        from . import ARRAY_BED
+        return self.domain.download(ARRAY_BED)
+
     # the peak tracker (Domain.peaks_*)
     def peaks_enable(self, values, arrival_depth=0.01):
         self.domain.peaks_enable(values, arrival_depth=arrival_depth)
@@ -547,6 +561,33 @@ class StripRunner:
     def gather_owned(self):
         """All ranks' owned rows assembled on every rank (tests)."""
         local = self.engine.download()
+        mine = np.ascontiguousarray(local[self.own_lo - self.local_lo:self.own_hi - self.local_lo])
+        out = [None] * self.world
+        self.dist.all_gather_object(out, mine)
+        return np.concatenate(out, axis=0)
+
+    # ---- the moving bed: every rank adds every shape with GLOBAL cell ids and keeps the cells on its local rows, ghost rows included
+    #      (the library drops the others), so that an apply moves a ghost row exactly as its owner moves the row; nothing is exchanged ----
+    def _bed_engine(self, what):
+        if not hasattr(self.engine, "bed_apply"):
+            raise RuntimeError(f"{what}: this engine has no moving bed (the HIP engine's hp_bed_*)")
+        return self.engine
+
+    def bed_shape_add(self, cells, target, series):
+        """`cells`: flat ids y * cols + x of the WHOLE grid or (x, y) pairs; every rank calls it with the same arguments."""
+        self._bed_engine("bed_shape_add").bed_shape_add(cells, target, series)
+
+    def bed_shapes_clear(self):
+        self._bed_engine("bed_shapes_clear").bed_shapes_clear()
+
+    def bed_apply(self):
+        """Every rank, between batches.  With two reaches of ghost rows (exchange_period 2) after an even batch only: the library
+        refuses an apply while a strip's ghost rows are not all valid."""
+        self._bed_engine("bed_apply").bed_apply()
+
+    def gather_bed(self):
+        """All ranks' owned rows of the bed assembled on every rank, as gather_owned does for the state (tests)."""
+        local = self._bed_engine("gather_bed").download_bed()
         mine = np.ascontiguousarray(local[self.own_lo - self.local_lo:self.own_hi - self.local_lo])
         out = [None] * self.world
         self.dist.all_gather_object(out, mine)

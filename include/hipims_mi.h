@@ -427,6 +427,66 @@ int hp_zones_read(hp_domain_t* d, uint64_t first, uint64_t count, uint64_t* reco
  * Any of the three pointers may be NULL.  HP_ERR_STATE before hp_zones_enable. */
 int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_t* stride);
 
+/* ---- the moving bed: time-varying breaches and barriers (no reference counterpart: its bed is loaded once,
+ *      CDomainCartesian::loadInitialConditions, Domain/Cartesian/CDomainCartesian.cpp:163-283).  Every other forcing of the engine is
+ *      a source term; this one moves the terrain: an embankment that fails over twenty minutes, a barrier that closes at a given
+ *      time, a defence that goes in stages.  Opt-in.  A SHAPE is a list of cells, one target elevation per cell and one progress
+ *      series {time, fraction} shared by the shape's cells.  hp_bed_apply evaluates every shape's fraction from the device's own
+ *      "Time" scalar, in stream order behind whatever is queued, without any host synchronisation, and moves the bed of the listed
+ *      cells; the host calls it between batches (never inside one: the peak tracker's rule).
+ *      THE CONTRACT: an apply is exactly the host round trip it replaces -- hp_domain_download of state and bed, the bed moved and the
+ *      levels shifted on the host (frontend.BedShapes.apply restates it in NumPy), hp_domain_upload(HP_ARRAY_BED),
+ *      hp_domain_upload(HP_ARRAY_STATE) -- in every bit of the state, the bed and the scalars of the run that follows, with
+ *      iteration pairs, STRICT arithmetic and strips included.  A domain without shapes, or one that never applies, queues exactly
+ *      what it queues without this block.
+ *        Fraction.  All arithmetic in fp64, correctly rounded multiply, add, divide and compare only, never fused.  With t the
+ *      "Time" scalar widened and the series (t_0, f_0) ... (t_last, f_last): t <= t_0 gives f_0; t >= t_last gives f_last; otherwise,
+ *      in the segment with t_k <= t < t_k+1, f = f_k + (f_k+1 - f_k) * ((t - t_k) / (t_k+1 - t_k)), in that order.  Fractions
+ *      need not be monotone: a gate reopens.
+ *        New bed of a listed cell.  base = the cell's bed when its shape was added.  f <= 0 gives base; f >= 1 gives target
+ *      (base + (target - base) need not be target); otherwise base + f * (target - base).  Rounded once to the domain's
+ *      precision: b1.
+ *        The apply.  A listed cell is skipped if it is not counted in the sense of hp_domain_stats (Zmax > -9999 and bed <= 9999
+ *      counts) or if b1 equals its stored bed b0.  For every other listed cell, with the values of the buffer
+ *      hp_domain_download(HP_ARRAY_STATE) reads widened to fp64 and every result rounded once on store:
+ *      Z1 = b1 + (Z0 - b0) (the depth is kept raw: no clamp, no wet test), Zmax1 = Zmax0 > Z1 ? Zmax0 : Z1, Qx and Qy unchanged,
+ *      bed = b1.  Then both ping-pong buffers hold the patched state and the engine forgets what an upload of bed and state makes
+ *      it forget (the cost: one device-to-device copy of the whole state per apply). ---- */
+typedef struct {
+	uint32_t struct_size;              /* = sizeof(hp_bed_shape_desc_t) */
+	uint32_t series_entries;           /* 1 .. 4096 */
+	uint64_t cell_count;               /* >= 1; all shapes of a domain together <= 1048576 */
+	const uint64_t* cells;             /* flat ids y * cols + x in the GLOBAL grid, as hp_boundary_add_cell */
+	const double*   target;            /* cell_count elevations, finite, |target| <= 9999 */
+	const double*   series;            /* series_entries x {time, fraction}: times strictly increasing, fractions in [0, 1] */
+} hp_bed_shape_desc_t;
+typedef struct {
+	uint32_t struct_size;              /* = sizeof(hp_bed_info_t), set by the caller */
+	uint32_t shapes;                   /* shapes on the domain */
+	uint64_t cells_local;              /* listed cells this domain (strip) keeps */
+	uint64_t applies;                  /* applies queued since the first shape was added (hp_bed_shapes_clear starts over) */
+	uint64_t changed_last;             /* cells the last apply changed (skipped cells do not count); 0 before the first */
+	uint64_t changed_total;            /* ... and all applies together */
+	double   t_last;                   /* the device time the last apply saw; 0 before the first */
+} hp_bed_info_t;
+/* Adds a shape (at most 64).  Copies the lists to the device (the caller's arrays are free again on return) and captures
+ * base[k] = bed[cell_k] with a gather on the domain's stream: the bed is not read back to the host.  A strip keeps the cells whose
+ * row lies in its local array, ghost rows included, and drops the others silently: every rank adds every shape with global ids.
+ * A cell may be listed at most once over all shapes of a domain (the message names the first repeated id).  A LATER
+ * hp_domain_upload(HP_ARRAY_BED) TOUCHES NEITHER THE SHAPES NOR THEIR base: a host that replaces the bed clears the shapes and adds
+ * them again.  Argument errors -- a bad struct_size, a NULL pointer, a count over its limit, a target that is not finite or beyond
+ * 9999, a time that is not finite or does not increase, a fraction outside [0, 1] or NaN, a repeated cell, an id at or above
+ * cols * global_rows -- are HP_ERR_INVALID before any device call; between hp_step_begin and hp_step_end the call returns
+ * HP_ERR_STATE.  If an allocation fails the call returns HP_ERR_HIP and the domain stays usable with the shapes it had. */
+int hp_bed_shape_add(hp_domain_t* d, const hp_bed_shape_desc_t* desc);
+int hp_bed_shapes_clear(hp_domain_t* d);               /* frees; idempotent (also done by hp_domain_destroy) */
+/* One apply: one kernel launch over the listed cells (csrc/hp_bed.hpp: bed_apply), then what the two uploads do.  Enqueued on the
+ * domain's stream, never blocks.  With no shape on the domain: HP_OK, nothing is enqueued.  HP_ERR_STATE between hp_step_begin
+ * and hp_step_end, and on a strip whose ghost rows are not all valid (two reaches of ghost rows after an odd number of iterations:
+ * apply after an even batch). */
+int hp_bed_apply(hp_domain_t* d);
+int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out);   /* BLOCKS */
+
 /* Device-side checkpoint: what saveCurrentState + rollbackSimulation do through host memory (CSchemeGodunov.cpp:1720-1736,
  * :1474-1518), kept in HBM instead (two more copies of a 4096^2 fp64 state are 1 GB of 288).  hp_state_save copies BOTH
  * ping-pong buffers and the time-control block; hp_state_restore puts each buffer, the time-control block, the ping-pong phase
@@ -441,7 +501,11 @@ int hp_zones_info(hp_domain_t* d, uint64_t* samples, uint64_t* capacity, uint64_
  * While the probe recorder is on, hp_state_save remembers its sample count and hp_state_restore puts it back: the records taken
  * since then are re-recorded by the samples that are repeated.  If the recorder was enabled, disabled, re-enabled or reset since
  * the snapshot, hp_state_restore sets the count to 0 and sends one HP_LOG_WARNING to the log sink.  The zone recorder's sample
- * count follows the same rule, with a warning of its own. */
+ * count follows the same rule, with a warning of its own.
+ * While the domain has bed shapes, hp_state_save also keeps the bed at the listed cells (hp_state_restore brings back neither the
+ * bed nor the boundary list, and a roll-back across an hp_bed_apply would leave levels of one bed over another) and
+ * hp_state_restore puts it back.  If shapes were added or cleared since the snapshot, hp_state_restore leaves the bed as it is
+ * and sends one HP_LOG_WARNING to the log sink. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
