@@ -11,6 +11,7 @@
 #include "hp_overview.hpp"
 #include "hp_sparse.hpp"
 #include "hp_bed.hpp"
+#include "hp_links.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <atomic>
@@ -48,7 +49,7 @@ void log_line(int level, const std::string& msg)
 	} while (0)
 
 struct Boundary {
-	int      kind;         // 0 uniform, 1 gridded, 2 cell
+	int      kind;         // 0 uniform, 1 gridded, 2 cell, 3 link group (cells: its LinkDev array, entries: its first record)
 	int      definition;
 	int      discharge_def;
 	void*    cells;        // device: global cell ids (cell boundaries)
@@ -125,6 +126,19 @@ struct BedShapes {
 	void*            saved = nullptr;
 	size_t           saved_room = 0;                  // cells it holds
 	bool             saved_taken = false;             // a checkpoint exists (with or without shapes) ...
+	uint64_t         saved_epoch = 0;                 // ... of this epoch
+};
+
+// link groups (hp_links.hpp; hp_boundary_add_links): the groups themselves are Boundary entries of kind 3, in the order added; this
+// is what they share.  Nothing of it exists while the domain has never had a link
+struct LinkStore {
+	uint64_t         links = 0;                       // links of all groups
+	unsigned         groups = 0;
+	hp_link_record_t* records = nullptr;              // device: LINK_MAX records, in the order the links were added
+	std::vector<uint64_t> taken;                      // GLOBAL ids of every end of every link, sorted: the repeated-cell check
+	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's records belong to one epoch
+	hp_link_record_t* saved = nullptr;                // hp_state_save's copy (LINK_MAX records)
+	bool             saved_taken = false;             // a checkpoint exists (with or without links) ...
 	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
@@ -244,6 +258,7 @@ struct hp_domain {
 	ProbeRecorder    probes;
 	ZoneRecorder     zones;
 	BedShapes        beds;
+	LinkStore        links;
 };
 
 namespace {

@@ -101,6 +101,12 @@ template <typename T> int apply_boundaries(hp_domain* d, void* target)
 		list.count = 0;
 	};
 	for (const Boundary& b : d->bdy) {
+		if (b.kind == 3) {
+			flush();
+			hipLaunchKernelGGL(bdy_links<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
+			                   (const LinkDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->links.records + b.entries);
+			continue;
+		}
 		if (b.kind == 2) {
 			flush();
 			CellBdy<T> c{(const unsigned long long*)b.cells, b.count, (const T*)b.data, b.entries, b.definition,
@@ -942,7 +948,7 @@ template <typename T> int set_scalar_field(hp_domain* d, size_t offset, double v
 
 
 // Which area boundaries the flux kernel carries itself (K1 FUSED, hp_kernels.hpp): Godunov scheme, tuned kernel, nothing but
-// uniform / gridded boundaries (a cell boundary in between has its place in the order added), at most FUSED_BDY_MAX of
+// uniform / gridded boundaries (a cell boundary or a link group in between has its place in the order added), at most FUSED_BDY_MAX of
 // them, and rain grids coarse enough for a tile to meet at most two grid rows and a wavefront two grid columns.  Everything
 // else keeps the stand-alone pass.  HP_FUSE_BDY=0 switches the fusion off (A/B runs).
 template <typename T> int refresh_fusable_t(hp_domain* d)
@@ -954,7 +960,7 @@ template <typename T> int refresh_fusable_t(hp_domain* d)
 	AreaBdyList<T> list;
 	list.count = 0;
 	for (const Boundary& b : d->bdy) {
-		if (b.kind == 2) return HP_OK;
+		if (b.kind >= 2) return HP_OK;                                        // a cell boundary or a link group: its place in the order
 		AreaBdy<T>& a = list.b[list.count++];
 		a = AreaBdy<T>{};
 		if (b.kind == 0) {
@@ -1087,6 +1093,37 @@ int bed_restore(hp_domain* d)
 		HIP_TRY(hipGetLastError());
 	}
 	d->facts.bed_uploaded();
+	return HP_OK;
+}
+
+// ---- link groups (hp_links.hpp): what a checkpoint does for the links' records ----
+static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
+void links_destroy(hp_domain* d) { hipFree(d->links.records); hipFree(d->links.saved); }
+// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+int links_save_reserve(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	if (!L.links || L.saved) return HP_OK;
+	return alloc_or_fail((void**)&L.saved, (size_t)LINK_MAX * sizeof(hp_link_record_t), "hp_state_save: cannot allocate the copy of the links' records: ");
+}
+int links_save(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	L.saved_taken = true;
+	L.saved_epoch = L.epoch;
+	if (L.links) HIP_TRY(hipMemcpyAsync(L.saved, L.records, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+int links_restore(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	if (!L.saved_taken) return HP_OK;
+	if (L.saved_epoch != L.epoch) {                                           // (the probe recorder's rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: link groups were added or cleared after the state was saved: the links' records start from zero");
+		if (L.links) HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
+		return HP_OK;
+	}
+	if (L.links) HIP_TRY(hipMemcpyAsync(L.records, L.saved, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
 	return HP_OK;
 }
 
@@ -1272,7 +1309,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); bed_destroy(d);
+	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); bed_destroy(d); links_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1341,6 +1378,7 @@ int hp_state_save(hp_domain_t* d)
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
 	if ((rc = peaks_save_reserve(d)) != HP_OK) return rc;            // (first: a failure leaves the checkpoint before it untouched)
 	if ((rc = bed_save_reserve(d)) != HP_OK) return rc;
+	if ((rc = links_save_reserve(d)) != HP_OK) return rc;
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1354,7 +1392,8 @@ int hp_state_save(hp_domain_t* d)
 	if ((rc = peaks_save(d)) != HP_OK) return rc;
 	log_save(d, PROBES);
 	log_save(d, ZONES);
-	return bed_save(d);
+	if ((rc = bed_save(d)) != HP_OK) return rc;
+	return links_save(d);
 }
 
 int hp_state_restore(hp_domain_t* d)
@@ -1389,7 +1428,8 @@ int hp_state_restore(hp_domain_t* d)
 	if ((rc = peaks_restore(d)) != HP_OK) return rc;
 	log_restore(d, PROBES);
 	log_restore(d, ZONES);
-	return bed_restore(d);
+	if ((rc = bed_restore(d)) != HP_OK) return rc;
+	return links_restore(d);
 }
 
 // ---- the moving bed (hp_bed.hpp) ----
@@ -1698,7 +1738,85 @@ int hp_boundary_clear(hp_domain_t* d)
 	for (auto& b : d->bdy) { hipFree(b.data); hipFree(b.cells); }
 	d->bdy.clear();
 	d->bdy_on_ring = false;
+	if (d->links.groups) {                                                    // the link groups go with the list, and their records with them
+		LinkStore& L = d->links;
+		HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
+		L.links = 0;
+		L.groups = 0;
+		L.taken.clear();
+		++L.epoch;
+	}
 	return refresh_fusable(d);
+}
+
+int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count)
+{
+	// argument checks first: none of them touches the device (hp_links.hpp: validate_links)
+	const std::string who = "hp_boundary_add_links";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	LinkStore& L = d->links;
+	const uint64_t cols = (uint64_t)d->desc.cols, reach = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? 2 : 1;
+	std::vector<uint64_t> taken;
+	std::string why;
+	if (!validate_links(links, count, L.links, cols, (uint64_t)d->desc.global_rows, reach, L.taken, taken, why)) return fail(HP_ERR_INVALID, why);
+	// this strip's share: both ends of a link, or neither (links_strip_verdict)
+	const int64_t lo = d->desc.row_offset, hi = d->desc.row_offset + d->desc.rows;
+	const int64_t stale = d->ghost_rows > (int64_t)reach ? d->ghost_rows - (int64_t)reach : 0;      // (two reaches stored: the outer one)
+	const int64_t stale_lo = lo > 0 ? stale : 0, stale_hi = hi < d->desc.global_rows ? stale : 0;
+	std::vector<LinkDev> dev((size_t)count);
+	for (uint64_t k = 0; k < count; ++k) {
+		const hp_link_t& l = links[k];
+		const int64_t ya = (int64_t)(l.cell_a / cols), yb = (int64_t)(l.cell_b / cols);
+		const int verdict = links_strip_verdict(ya, yb, lo, hi, stale_lo, stale_hi);
+		if (verdict == LINK_ONE)
+			return fail(HP_ERR_UNSUPPORTED, who + ": link " + std::to_string(k) + " (cells " + std::to_string(l.cell_a) + " and " + std::to_string(l.cell_b) +
+			            "): this strip stores rows " + std::to_string(lo) + " to " + std::to_string(hi - 1) + " and would hold exactly one of its ends on every iteration");
+		LinkDev& o = dev[(size_t)k];
+		o.a = verdict == LINK_BOTH ? l.cell_a - (uint64_t)lo * cols : LINK_ABSENT;
+		o.b = verdict == LINK_BOTH ? l.cell_b - (uint64_t)lo * cols : LINK_ABSENT;
+		o.kind = l.kind; o.one_way = l.one_way; o.level = l.level; o.size = l.size; o.coeff = l.coeff; o.limit = l.limit;
+	}
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	if (!L.records) {
+		if ((rc = alloc_or_fail((void**)&L.records, (size_t)LINK_MAX * sizeof(hp_link_record_t), who + ": cannot allocate the records: ")) != HP_OK) return rc;
+		HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)LINK_MAX * sizeof(hp_link_record_t), d->stream));
+	}
+	Boundary b{};
+	b.kind = 3; b.count = count; b.entries = L.links;
+	if ((rc = alloc_or_fail(&b.cells, (size_t)count * sizeof(LinkDev), who + ": cannot allocate the links: ")) != HP_OK) return rc;
+	hipError_t e = hipMemcpyAsync(b.cells, dev.data(), (size_t)count * sizeof(LinkDev), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (`dev` goes with this call)
+	if (e != hipSuccess) { hipFree(b.cells); return fail(HP_ERR_HIP, who + ": writing the links: " + hipGetErrorString(e)); }
+	d->facts.boundaries_or_bed_changed();
+	d->bdy.push_back(b);
+	L.links += count;
+	L.groups += 1;
+	L.taken.swap(taken);
+	++L.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_links_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_link_record_t* out)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (first > d->links.links || count > d->links.links - first) return fail(HP_ERR_INVALID, "hp_links_read: first + count beyond the domain's links");
+	if (count == 0) return HP_OK;
+	if (!out) return fail(HP_ERR_INVALID, "hp_links_read: out == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_links_read between hp_step_begin and hp_step_end");
+	HIP_TRY(hipMemcpyAsync(out, d->links.records + first, (size_t)count * sizeof(hp_link_record_t), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (links) *links = d->links.links;
+	if (groups) *groups = d->links.groups;
+	return HP_OK;
 }
 
 int hp_boundaries_fused(hp_domain_t* d, int* fused)
@@ -1836,7 +1954,8 @@ bool spec_wanted(const hp_domain* d, uint32_t n)
 #else
 	const bool fusable_ok = !d->fusable;
 #endif
-	return enabled && n >= SPEC_MIN && d->desc.math_mode == HP_MATH_STRICT && d->desc.precision == 8 && !d->comm && fusable_ok &&
+	// Never with link groups: the batch that is queued again after a raised word would count their records twice.
+	return enabled && n >= SPEC_MIN && d->desc.math_mode == HP_MATH_STRICT && d->desc.precision == 8 && !d->comm && fusable_ok && !d->links.groups &&
 	       d->desc.kernel != HP_KERNEL_BASIC && (d->desc.scheme == HP_SCHEME_GODUNOV || d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK);
 }
 int spec_begin(hp_domain* d)

@@ -50,7 +50,7 @@ EXPORTS = [
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
     "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
-    "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
+    "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
     "hp_stream_halo", "hp_comm_load", "hp_comm_unique_id", "hp_strip_comm_init", "hp_strip_step_batch", "hp_strip_update_timestep",
@@ -140,6 +140,39 @@ class BedInfo(C.Structure):
                 ("changed_last", C.c_uint64), ("changed_total", C.c_uint64), ("t_last", C.c_double)]
 
 
+LINK_WEIR, LINK_ORIFICE, LINK_PUMP = 0, 1, 2         # HP_LINK_*
+LINK_KINDS = {"weir": LINK_WEIR, "orifice": LINK_ORIFICE, "culvert": LINK_ORIFICE, "pump": LINK_PUMP}
+# hp_link_t and hp_link_record_t as NumPy records: arrays of them go through the ABI as they are
+LINK_DTYPE = np.dtype([("cell_a", np.uint64), ("cell_b", np.uint64), ("kind", np.int32), ("one_way", np.int32),
+                       ("level", np.float64), ("size", np.float64), ("coeff", np.float64), ("limit", np.float64)])
+LINK_RECORD_DTYPE = np.dtype([("q_last", np.float64), ("volume", np.float64), ("active", np.uint64), ("reserved", np.uint64)])
+
+
+def pack_links(links, cols):
+    """Links as an array of LINK_DTYPE.  `links`: such an array, or a sequence of dicts / tuples (a, b, kind, one_way, level, size,
+    coeff, limit) where a and b are flat ids y * cols + x of the GLOBAL grid or (x, y) pairs and kind an HP_LINK_* code or its name;
+    one_way defaults to 0, coeff to 0 and limit to +inf for an orifice, 0 otherwise."""
+    if isinstance(links, np.ndarray) and links.dtype == LINK_DTYPE:
+        return np.ascontiguousarray(links).reshape(-1)
+    names = ("a", "b", "kind", "one_way", "level", "size", "coeff", "limit")
+    out = np.zeros(len(links), LINK_DTYPE)
+
+    def cell(c):
+        if np.ndim(c) == 0:
+            return int(c)
+        x, y = int(c[0]), int(c[1])
+        if not (0 <= x < cols and y >= 0):
+            raise ValueError("a link's cell lies outside the grid")
+        return y * cols + x
+    for k, l in enumerate(links):
+        l = dict(l) if isinstance(l, dict) else dict(zip(names, l))
+        kind = l["kind"]
+        kind = LINK_KINDS[kind.lower()] if isinstance(kind, str) else int(kind)
+        out[k] = (cell(l["a"]), cell(l["b"]), kind, int(l.get("one_way", 0)), float(l["level"]), float(l["size"]), float(l.get("coeff", 0.0)),
+                  float(l.get("limit", np.inf if kind == LINK_ORIFICE else 0.0)))
+    return out
+
+
 _lib = None
 
 
@@ -208,6 +241,10 @@ def load_library(path: str | None = None):
         lib.hp_bed_shapes_clear.argtypes = [C.c_void_p]
         lib.hp_bed_apply.argtypes = [C.c_void_p]
         lib.hp_bed_info.argtypes = [C.c_void_p, C.POINTER(BedInfo)]
+    if hasattr(lib, "hp_boundary_add_links"):           # (absent from older builds, as above)
+        lib.hp_boundary_add_links.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.hp_links_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.hp_links_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -898,6 +935,27 @@ class Domain:
         _check(self.lib, self.lib.hp_boundary_add_cell(self.h, depth_def, discharge_def, rel.ctypes.data_as(C.c_void_p),
                                                        rel.size, ser.ctypes.data_as(C.c_void_p), ser.shape[0], interval,
                                                        length), "hp_boundary_add_cell")
+
+    def add_links(self, links):
+        """One link group (hp_boundary_add_links): water passes between two distant cells as a function of their own levels -- weirs,
+        orifices / culverts, pumps.  `links`: see pack_links; ids are GLOBAL.  Applied per iteration at its place in the order the
+        boundaries were added; frontend.Links is the same arithmetic on the host, bit for bit."""
+        a = pack_links(links, self.cols)
+        _check(self.lib, self.lib.hp_boundary_add_links(self.h, a.ctypes.data_as(C.c_void_p), a.size), "hp_boundary_add_links")
+
+    def links_info(self):
+        """dict(links, groups): host counters."""
+        n, g = C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_links_info(self.h, C.byref(n), C.byref(g)), "hp_links_info")
+        return dict(links=n.value, groups=g.value)
+
+    def links_read(self, first=0, count=None):
+        """The links' records as an array of LINK_RECORD_DTYPE (q_last, volume, active), in the order added; blocks."""
+        count = self.links_info()["links"] - first if count is None else count
+        out = np.zeros(count, LINK_RECORD_DTYPE)
+        _check(self.lib, self.lib.hp_links_read(self.h, first, count, out.ctypes.data_as(C.c_void_p)), "hp_links_read")
+        self.sync()
+        return out
 
     def clear_boundaries(self):
         _check(self.lib, self.lib.hp_boundary_clear(self.h), "hp_boundary_clear")

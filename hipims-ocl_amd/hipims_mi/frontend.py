@@ -119,6 +119,7 @@ class Configuration:
     overviews: list = field(default_factory=list)  # (value, aggregate, factor, target pattern, format): <dataTarget overview="...">
     sparse: dict = None                            # select, above, values, target pattern: the <sparseTarget> element (the last one wins)
     bed_shapes: list = field(default_factory=list)  # dict(name, cells [(x, y)], target [n], series [m, 2]): <bedShape> elements
+    links: list = field(default_factory=list)      # dict(a (x, y), b (x, y), kind, one_way, level, size, coeff, limit): rows of the <links> elements' mapFiles
 
 
 def _params(elem):
@@ -208,7 +209,22 @@ def parse_configuration(xml_path):
             if kind == "cell" and ts.get("mapFile"):
                 b.cells = [(int(r[0]), int(r[1])) for r in _read_csv(os.path.join(bdir, ts.get("mapFile")))]
             cfg.boundaries.append(b)
+        # link groups (no reference counterpart): <links mapFile="links.csv"/>, rows xa, ya, xb, yb, kind, one_way, level, size, coeff, limit
+        # (kind: 0 weir, 1 orifice, 2 pump; "inf" is a number to float())
+        for e in bc.findall("links"):
+            for r in _read_csv(os.path.join(bdir, e.get("mapFile"))).reshape(-1, 10):
+                cfg.links.append(dict(a=(int(r[0]), int(r[1])), b=(int(r[2]), int(r[3])), kind=int(r[4]), one_way=int(r[5]),
+                                      level=float(r[6]), size=float(r[7]), coeff=float(r[8]), limit=float(r[9])))
     return cfg
+
+
+def write_links_csv(path, links):
+    """The mapFile of a <links> element: what parse_configuration reads back (repr round-trips every double)."""
+    with open(path, "w") as f:
+        f.write("xa,ya,xb,yb,kind,one_way,level,size,coeff,limit\n")
+        for l in links:
+            f.write(",".join([str(int(l["a"][0])), str(int(l["a"][1])), str(int(l["b"][0])), str(int(l["b"][1])), str(int(l["kind"])),
+                              str(int(l.get("one_way", 0)))] + [repr(float(l[k])) for k in ("level", "size", "coeff", "limit")]) + "\n")
 
 
 # ------------------------------------------------------------------------------------------------ domain arrays
@@ -725,6 +741,147 @@ class BedShapes:
             changed += int(move.sum())
         self.applies += 1
         return changed
+
+
+class Links:
+    """Link groups on the host (hp_boundary_add_links restated in NumPy, in exactly the operation order of csrc/hp_links.hpp:
+    link_flow and link_record): weirs, orifices / culverts and pumps between two distant cells.  `apply` acts in place on
+    state[rows, cols, 4], the iteration's source buffer, where the engine launches bdy_links; the arrays' dtype decides the single
+    rounding of a stored level.  All arithmetic is fp64 -- separate, correctly rounded adds, multiplies, divides and square roots
+    -- so state and records equal the device's bit for bit.  The GPU tests' reference; it also counts which branch each link took."""
+
+    WEIR, ORIFICE, PUMP = 0, 1, 2
+    MAX_LINKS = 65536
+    G = 9.81
+    BRANCHES = ("inert", "flap_shut", "weir_free", "weir_submerged", "weir_dry", "orifice_free", "orifice_capped", "orifice_dry",
+                "pump_on", "pump_off", "avail_cap", "avail_none", "equalised")
+
+    def __init__(self, rows, cols, dx, links, scheme_reach=1):
+        from . import pack_links
+        self.rows, self.cols, self.dx = int(rows), int(cols), float(dx)
+        L = pack_links(links, self.cols)
+        self.links = L
+        n = len(L)
+        if not 1 <= n <= self.MAX_LINKS:
+            raise ValueError("link count outside 1..65536")
+        if not np.isin(L["kind"], (0, 1, 2)).all():
+            raise ValueError("unknown link kind")
+        pump, weir, orifice = L["kind"] == 2, L["kind"] == 0, L["kind"] == 1
+        if not (np.isfinite(L["level"]) & np.isfinite(L["size"])).all() or (L["size"] < 0).any():
+            raise ValueError("level and size must be finite, size not negative")
+        if not np.isfinite(L["coeff"][~pump]).all() or (L["coeff"][~pump] < 0).any():
+            raise ValueError("coeff must be finite and not negative")
+        with np.errstate(over="ignore"):
+            if not np.isfinite((L["coeff"] * L["size"])[~pump]).all():
+                raise ValueError("coeff * size must be finite")
+        with np.errstate(invalid="ignore"):
+            if not ((L["limit"][weir] >= 0) & (L["limit"][weir] < 1)).all() or not (L["limit"][orifice] >= 0).all():
+                raise ValueError("a limit lies outside its range")
+        ends = np.concatenate([L["cell_a"], L["cell_b"]]).astype(np.int64)
+        if (L["cell_a"] == L["cell_b"]).any():
+            raise ValueError("a link joins a cell to itself")
+        if ends.max() >= self.rows * self.cols:
+            raise ValueError("a link's cell lies outside the grid")
+        y, x = ends // self.cols, ends % self.cols
+        w = int(scheme_reach)
+        if ((x < w) | (x + w >= self.cols) | (y < w) | (y + w >= self.rows)).any():
+            raise ValueError("a link's cell lies on the grid's ring")
+        uniq, counts = np.unique(ends, return_counts=True)
+        if (counts > 1).any():
+            raise ValueError(f"cell {int(uniq[counts > 1][0])} is an end of two links")
+        self.a, self.b = L["cell_a"].astype(np.int64), L["cell_b"].astype(np.int64)
+        self.q_last, self.volume, self.active = np.zeros(n), np.zeros(n), np.zeros(n, np.uint64)
+        self.applies = 0
+        self.branches = {k: np.zeros(n, np.int64) for k in self.BRANCHES}    # per link: iterations in which it took the branch
+
+    def records(self):
+        from . import LINK_RECORD_DTYPE
+        out = np.zeros(len(self.links), LINK_RECORD_DTYPE)
+        out["q_last"], out["volume"], out["active"] = self.q_last, self.volume, self.active
+        return out
+
+    def branch_totals(self):
+        return {k: int(v.sum()) for k, v in self.branches.items()}
+
+    def flow(self, za, zmax_a, bed_a, zb, zmax_b, bed_b, dt, dx, count=True):
+        """link_flow on fp64 arrays, one element per link -> (za1, zb1, dz, s, inert): the levels before they are rounded."""
+        L = self.links
+        kind, level, size, coeff, limit = L["kind"], L["level"], L["size"], L["coeff"], L["limit"]
+        dt, dx = np.float64(dt), np.float64(dx)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            inert = (dt <= 0.0) | ~((zmax_a > -9999.0) & (bed_a <= 9999.0)) | ~((zmax_b > -9999.0) & (bed_b <= 9999.0))
+            a_up = np.where(kind == self.PUMP, True, za >= zb)
+            zup, zdn, bed_up = np.where(a_up, za, zb), np.where(a_up, zb, za), np.where(a_up, bed_a, bed_b)
+            s = np.where(a_up, 1.0, -1.0)
+            shut = (L["one_way"] != 0) & ~a_up
+            # weir
+            hu = zup - level
+            w_wet = hu > 0.0
+            hu_ = np.where(w_wet, hu, 1.0)                                  # (lanes that take no root get a harmless operand)
+            q_w = ((coeff * size) * hu_) * np.sqrt(hu_)
+            hd = zdn - level
+            sub = w_wet & (hd > limit * hu_)
+            ratio = np.where(sub, (hu_ - hd) / (hu_ * (1.0 - limit)), 1.0)
+            q_w = np.where(sub, q_w * np.sqrt(ratio), q_w)
+            q_w = np.where(w_wet, q_w, 0.0)
+            # orifice
+            o_wet = zup > level
+            dh = np.where(o_wet, zup - np.where(zdn > level, zdn, level), 0.0)
+            free_q = (coeff * size) * np.sqrt((2.0 * self.G) * dh)
+            capped = o_wet & (limit < free_q)
+            q_o = np.where(o_wet, np.where(limit < free_q, limit, free_q), 0.0)
+            # pump
+            on = za > level
+            q_p = np.where(on, size, 0.0)
+            q = np.where(shut, 0.0, np.where(kind == self.WEIR, q_w, np.where(kind == self.ORIFICE, q_o, q_p)))
+            dz = (q * dt) / (dx * dx)
+            avail = zup - np.where(level > bed_up, level, bed_up)
+            none = ~(avail > 0.0)
+            cap = ~none & (avail < dz)
+            dz = np.where(none, 0.0, np.where(cap, avail, dz))
+            half = 0.5 * (zup - zdn)
+            equal = (kind != self.PUMP) & (half < dz)
+            dz = np.where(equal, half, dz)
+            dz = np.where(inert, 0.0, dz)
+            move = ~inert & (dz > 0.0)
+            zup1, zdn1 = zup - dz, zdn + dz
+            za1 = np.where(move, np.where(a_up, zup1, zdn1), za)
+            zb1 = np.where(move, np.where(a_up, zdn1, zup1), zb)
+        if count:
+            live, B = ~inert, self.branches
+            run = live & ~shut
+            for name, mask in (("inert", inert), ("flap_shut", live & shut),
+                               ("weir_free", run & (kind == 0) & w_wet & ~sub), ("weir_submerged", run & (kind == 0) & sub),
+                               ("weir_dry", run & (kind == 0) & ~w_wet),
+                               ("orifice_free", run & (kind == 1) & o_wet & ~capped), ("orifice_capped", run & (kind == 1) & capped),
+                               ("orifice_dry", run & (kind == 1) & ~o_wet),
+                               ("pump_on", run & (kind == 2) & on), ("pump_off", run & (kind == 2) & ~on),
+                               ("avail_cap", live & cap & (q > 0.0)), ("avail_none", live & none & (q > 0.0)),
+                               ("equalised", live & equal & (q > 0.0))):
+                B[name] += mask
+        return za1, zb1, dz, s, inert
+
+    def apply(self, state, bed, dt):
+        """One iteration's links, in place on `state` (the iteration's source buffer); `dt`: the timestep scalar of that iteration.
+        Returns the number of links that moved water."""
+        if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or not state.flags.c_contiguous:
+            raise ValueError("state must be a contiguous [rows, cols, 4] and bed [rows, cols]")
+        real = state.dtype.type
+        st, zb = state.reshape(-1, 4), np.asarray(bed).reshape(-1)
+        dt, dx = np.float64(real(dt)), np.float64(real(self.dx))
+        a, b = self.a, self.b
+        za1, zb1, dz, s, inert = self.flow(st[a, 0].astype(np.float64), st[a, 1].astype(np.float64), zb[a].astype(np.float64),
+                                           st[b, 0].astype(np.float64), st[b, 1].astype(np.float64), zb[b].astype(np.float64), dt, dx)
+        move = ~inert & (dz > 0.0)
+        st[a[move], 0] = za1[move].astype(real)
+        st[b[move], 0] = zb1[move].astype(real)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            moved = dz * (dx * dx)
+            self.q_last = np.where(inert, 0.0, s * (moved / dt))
+            self.volume = np.where(inert, self.volume, self.volume + s * moved)
+        self.active = self.active + move.astype(np.uint64)
+        self.applies += 1
+        return int(move.sum())
 
 
 def derive_output(what, state, bed, resolution=1.0):

@@ -181,7 +181,8 @@ class Model:
 
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
-                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None):
+                 probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None,
+                 links=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -196,6 +197,17 @@ class Model:
         self.sim = sim
         sim.upload(self.state0, self.bed, self.manning)
         frontend.attach_boundaries(cfg, sim, self.cols)
+        # Link groups (no reference counterpart): the rows of the model file's <links mapFile="links.csv"/> elements inside
+        # <boundaryConditions> and the dict(a=(x, y), b=(x, y), kind=, one_way=, level=, size=, coeff=, limit=) entries of `links`, one
+        # group behind the file's boundaries.  They act inside every iteration, so only an engine that has them on the device will do.
+        self.link_list = [dict(l) for l in list(cfg.links) + list(links or [])]
+        self.link_series = []                                      # [(time, records)]: one entry per output time
+        if self.link_list:
+            if not hasattr(sim, "add_links"):
+                raise NotImplementedError("link groups act inside every iteration: they need an engine with add_links (the HIP engine)")
+            if cfg.scheme == frontend.SCHEME_MUSCL_HANCOCK and log:
+                log("Warning: link groups are inert under MUSCL-Hancock, like every boundary condition (quirk Q8)")
+            sim.add_links(self.link_list)
         self.scheme = SchemeDriver(sim, cfg, self.cols * self.rows)
         self.output_format, self.log, self.clock = output_format, log, clock
         self.progress_interval = progress_interval
@@ -392,6 +404,18 @@ class Model:
         if (self.host_zones is not None or self.device_zones) and self.cfg.target_dir and self.output_format:
             frontend.write_zone_file(self.cfg.target_dir, self.zones(), self.res)
 
+    def write_links(self):
+        """links.csv in the target directory: a row per output time, t, then q_last and volume of every link in the order given."""
+        if not self.link_list:
+            return
+        self.link_series.append((self.current_time, self.sim.links_read()))
+        if self.cfg.target_dir and self.output_format:
+            os.makedirs(self.cfg.target_dir, exist_ok=True)
+            with open(os.path.join(self.cfg.target_dir, "links.csv"), "w") as f:
+                f.write(",".join(["t"] + [f"q_last_{k},volume_{k}" for k in range(len(self.link_list))]) + "\n")
+                for t, rec in self.link_series:
+                    f.write(",".join([repr(float(t))] + [f"{float(r['q_last'])!r},{float(r['volume'])!r}" for r in rec]) + "\n")
+
     def peaks(self):
         """{name: array} of the tracked peak values so far."""
         if not self.peak_names:
@@ -472,6 +496,7 @@ class Model:
                          select=np.array(spec["select"]), above=np.float64(spec["above"]), **out["sparse"])
         self.write_probes()
         self.write_zones()
+        self.write_links()
         self.outputs.append((self.current_time, out))
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()

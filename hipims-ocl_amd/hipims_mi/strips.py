@@ -125,6 +125,35 @@ def assemble_probes(parts, gauges, sections, dx):
     return dict(t=t, gauges=values[:, :G].copy(), sections=q)
 
 
+def links_strip_verdict(row_a, row_b, local_lo, local_hi, stale_lo=0, stale_hi=0):
+    """csrc/hp_links.hpp: links_strip_verdict.  0: the strip that stores the global rows [local_lo, local_hi) ignores the link
+    between rows row_a and row_b, 2: it computes it, 1: it cannot run it -- it stores one end only, or one end on a row of its
+    outermost reach of ghost rows (`stale_*` rows per side: valid on every second iteration only) and the other on a row that is
+    always valid."""
+    a_in, b_in = local_lo <= row_a < local_hi, local_lo <= row_b < local_hi
+    if not a_in and not b_in:
+        return 0
+    if a_in != b_in:
+        return 1
+    a_stale = row_a < local_lo + stale_lo or row_a >= local_hi - stale_hi
+    b_stale = row_b < local_lo + stale_lo or row_b >= local_hi - stale_hi
+    return 2 if a_stale == b_stale else 1
+
+
+def links_refused(links, cols, parts, reach):
+    """The first (link, rank) whose verdict is 1 over the strips `parts` (partition's), or None.  `reach`: the scheme's stencil
+    reach; a strip that stores more ghost rows than that holds the rest on every second iteration only."""
+    rows = parts[-1][1]
+    for k in range(len(links)):
+        ya, yb = int(links["cell_a"][k]) // cols, int(links["cell_b"][k]) // cols
+        for rank, (own_lo, own_hi, lo, hi) in enumerate(parts):
+            stale_lo = max(0, (own_lo - lo) - reach) if lo > 0 else 0
+            stale_hi = max(0, (hi - own_hi) - reach) if hi < rows else 0
+            if links_strip_verdict(ya, yb, lo, hi, stale_lo, stale_hi) == 1:
+                return k, rank
+    return None
+
+
 class HipEngine:
     """The HIP domain of one strip + zero-copy torch views of its device buffers."""
 
@@ -209,6 +238,13 @@ class HipEngine:
     def download_bed(self):
         from . import ARRAY_BED
         return self.domain.download(ARRAY_BED)
+
+    # link groups (Domain.add_links)
+    def add_links(self, links):
+        self.domain.add_links(links)
+
+    def links_read(self, first=0, count=None):
+        return self.domain.links_read(first, count)
 
     # the peak tracker (Domain.peaks_*)
     def peaks_enable(self, values, arrival_depth=0.01):
@@ -592,6 +628,41 @@ class StripRunner:
         out = [None] * self.world
         self.dist.all_gather_object(out, mine)
         return np.concatenate(out, axis=0)
+
+    # ---- link groups: every rank adds every group with GLOBAL ids; a strip computes the links whose two ends it stores (ghost rows
+    #      included), redundantly with its neighbours, and ignores the others.  A link with exactly one end on a strip cannot run ----
+    def add_links(self, links):
+        """`links`: see hipims_mi.pack_links; every rank calls it with the same arguments.  Every strip's verdict on every link is
+        looked at BEFORE any rank adds anything: a ValueError names the first link some strip would hold one end of."""
+        from . import pack_links
+        if not hasattr(self.engine, "add_links"):
+            raise RuntimeError("add_links: this engine has no link groups (the HIP engine's hp_boundary_add_links)")
+        L = pack_links(links, self.cols)
+        bad = links_refused(L, self.cols, self.parts, ghost_rows(self.scheme))
+        if bad is not None:
+            k, rank = bad
+            raise ValueError(f"link {k} (cells {int(L['cell_a'][k])} and {int(L['cell_b'][k])}): strip {rank} would hold exactly one of its ends "
+                             f"on every iteration (it stores rows {self.parts[rank][2]} to {self.parts[rank][3] - 1})")
+        self.engine.add_links(L)                        # (may still refuse the group: only what the engine took is remembered)
+        self._links = L if getattr(self, "_links", None) is None else np.concatenate([self._links, L])
+
+    def gather_links(self):
+        """The records of all links on rank 0 (an array of hipims_mi.LINK_RECORD_DTYPE, equal to the single domain's
+        Domain.links_read() in every bit), None on the other ranks: a link's record is the one of the strip that owns its end a.
+        Collective."""
+        from . import LINK_RECORD_DTYPE
+        L = getattr(self, "_links", None)
+        if L is None:
+            raise RuntimeError("gather_links: no link group was added")
+        rows_a = (L["cell_a"] // np.uint64(self.cols)).astype(np.int64)
+        mine = np.flatnonzero((rows_a >= self.own_lo) & (rows_a < self.own_hi))
+        parts = self._gather_parts((mine, self.engine.links_read()[mine]))
+        if self.rank != 0:
+            return None
+        out = np.zeros(len(L), LINK_RECORD_DTYPE)
+        for idx, rec in parts:
+            out[idx] = rec
+        return out
 
     def gather_outputs(self, values, dtype=np.float64):
         """Output rasters of the whole grid: every rank derives its OWNED rows on its device (Domain.derive), rank 0 gets

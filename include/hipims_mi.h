@@ -505,7 +505,11 @@ int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out);   /* BLOCKS */
  * While the domain has bed shapes, hp_state_save also keeps the bed at the listed cells (hp_state_restore brings back neither the
  * bed nor the boundary list, and a roll-back across an hp_bed_apply would leave levels of one bed over another) and
  * hp_state_restore puts it back.  If shapes were added or cleared since the snapshot, hp_state_restore leaves the bed as it is
- * and sends one HP_LOG_WARNING to the log sink. */
+ * and sends one HP_LOG_WARNING to the log sink.
+ * While the domain has link groups (hp_boundary_add_links), hp_state_save also keeps the links' records and hp_state_restore puts
+ * them back: the iterations that are repeated count again what they counted.  If link groups were added or cleared since the
+ * snapshot, hp_state_restore sets the records of the links the domain has now to zero and sends one HP_LOG_WARNING to the log
+ * sink: the probe recorder's rule. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
@@ -528,7 +532,74 @@ enum { HP_DEPTH_IGNORE = 0, HP_DEPTH_IS_FSL = 1, HP_DEPTH_IS_DEPTH = 2, HP_DEPTH
 enum { HP_DISCHARGE_IGNORE = 0, HP_DISCHARGE_IS_DISCHARGE = 1, HP_DISCHARGE_IS_VELOCITY = 2, HP_DISCHARGE_IS_VOLUME = 3 };   /* :39-42 */
 int hp_boundary_add_cell(hp_domain_t* d, int depth_definition, int discharge_definition, const uint64_t* cells,
                          uint64_t count, const void* series, uint64_t entries, double interval, double length);
-int hp_boundary_clear(hp_domain_t* d);
+/* ---- link groups: water passes THROUGH an embankment -- a culvert under a road, a weir into a storage basin, a flap-valved
+ *      outfall, a pumping station behind a defence (no reference counterpart: the reference moves water between face neighbours and
+ *      in and out of the model through prescribed sources only).  A LINK joins two cells a and b, anywhere in the grid, and moves
+ *      water between them as a function of their OWN levels; a link group is the fourth boundary kind, next to uniform, gridded and
+ *      cell: applied once per iteration on the iteration's source buffer, at its place in the order added, like a cell boundary.
+ *      The kernel is one thread per link (csrc/hp_links.hpp: bdy_links): a cell is an end of at most one link over all groups of a
+ *      domain, so it needs no atomics and does not depend on any order.
+ *      A domain with a link group is not fusable (hp_boundaries_fused is false, as with a cell boundary), so it runs single
+ *      iterations, never iteration pairs; and it never runs a speculative STRICT batch (a batch that is queued again would count
+ *      the records twice).  Under MUSCL-Hancock links are inert, like every boundary (quirk Q8).
+ *      THE CONTRACT.  All arithmetic in fp64 whatever the domain's precision, the stored values widened first; correctly rounded
+ *      add, multiply, divide, square root and compare only, never fused; each stored level is rounded once.  dt is the "Timestep"
+ *      scalar, dx the cell size as the kernels hold it (rounded to the domain's precision), g the engine's own constant (9.81).
+ *      Per link and iteration:
+ *        1. Inert cases.  The link is inert if dt <= 0 or if either end is not counted in the sense of hp_domain_stats (a cell is
+ *      counted when Zmax > -9999 and bed <= 9999).  An inert link sets q_last = +0.0 and changes nothing else.
+ *        2. Direction.  up = a if Za >= Zb, else b; dn the other end.  A pump always has up = a.  If one_way is set and up == b,
+ *      Q = 0.
+ *        3. Discharge Q in m3/s.  Weir: hu = Zup - level; Q = 0 unless hu > 0, otherwise Q = ((coeff * size) * hu) * sqrt(hu), and
+ *      with hd = Zdn - level, if hd > limit * hu then Q = Q * sqrt((hu - hd) / (hu * (1 - limit))).  Orifice: Q = 0 unless
+ *      Zup > level, otherwise dH = Zup - max(Zdn, level) and Q = min((coeff * size) * sqrt((2 * g) * dH), limit).  Pump: Q = size if
+ *      Za > level, else 0.
+ *        4. Level change.  dz = (Q * dt) / (dx * dx).  avail = Zup - max(level, bed_up): if !(avail > 0) then dz = 0, else
+ *      dz = min(dz, avail).  For weir and orifice also dz = min(dz, 0.5 * (Zup - Zdn)): a link cannot overshoot equal levels.
+ *        5. Stores.  If dz > 0: Zup = Zup - dz and Zdn = Zdn + dz.  Zmax, Qx and Qy are left as they are, as a cell boundary
+ *      leaves Zmax.
+ *        6. Record.  With s = +1 for a -> b (up == a) and -1 otherwise: q_last = s * ((dz * (dx * dx)) / dt);
+ *      volume = volume + s * (dz * (dx * dx)), one add per iteration, in iteration order; active += (dz > 0).
+ *      frontend.Links restates all of it in NumPy; tests/links_probe.cpp holds the two to each other bit for bit.
+ *      TWO THINGS TO KNOW.  A link acts on the source buffer only.  If it drains its upstream cell while that cell's whole
+ *      neighbourhood is dry, the flux kernel leaves the cell untouched in the OTHER ping-pong buffer, as the reference does with
+ *      every such cell (quirk Q3): the level the cell had two iterations earlier comes back with the next iteration and is passed on
+ *      once more.  A pump that empties an isolated polder therefore moves more than the polder held; keep such a cell's
+ *      neighbourhood wet or give the pump a switch-on level above the bed.  And the products of finite parameters must be finite:
+ *      coeff * size that overflows is an argument error (with dH == 0 it would leave a NaN in `volume` for good).
+ *      STRIPS.  Every rank adds every group with GLOBAL ids.  A strip must store both ends of a link, ghost rows included, or
+ *      neither: storing exactly one end is HP_ERR_UNSUPPORTED, and the message names the link.  A strip with two reaches of ghost
+ *      rows holds its outermost reach on every second iteration only: an end on such a row with the other end on a row that is
+ *      always valid is refused in the same way.  Two strips that both store a link compute the same bits redundantly; a link's
+ *      record is the one held by the strip that owns a. ---- */
+enum { HP_LINK_WEIR = 0, HP_LINK_ORIFICE = 1, HP_LINK_PUMP = 2 };
+typedef struct {
+	uint64_t cell_a, cell_b;           /* flat ids y * cols + x in the GLOBAL grid, as hp_boundary_add_cell; both interior */
+	int32_t  kind;                     /* HP_LINK_* */
+	int32_t  one_way;                  /* != 0: a -> b only (flap valve) */
+	double   level;                    /* weir: crest elevation; orifice: invert; pump: switch-on level at a */
+	double   size;                     /* weir: crest width, m; orifice: flow area, m2; pump: rate, m3/s (always a -> b) */
+	double   coeff;                    /* weir: m^0.5/s; orifice: dimensionless; pump: ignored */
+	double   limit;                    /* weir: modular limit in [0, 1); orifice: discharge cap, m3/s (+inf for none); pump: ignored */
+} hp_link_t;
+typedef struct {
+	double   q_last;                   /* the discharge the last iteration realised, m3/s, a -> b positive */
+	double   volume;                   /* what has passed since the group was added, m3, a -> b positive */
+	uint64_t active;                   /* iterations in which the link moved water */
+	uint64_t reserved;
+} hp_link_record_t;
+/* Adds one link group (at most 65536 links over all groups of a domain).  Both cells of a link must be interior: not within the
+ * scheme's reach of the grid's ring (the ring test of hp_boundary_add_cell; a ring cell is rejected, not flagged), and a cell may be
+ * an end of at most one link over all groups of the domain (the message names the first repeated id).  Argument errors -- a NULL
+ * pointer, count 0 or over the limit, an unknown kind, a level, size, coeff or coeff * size that is not finite, a negative size or coeff, a limit
+ * outside its range or NaN, a == b, a ring cell, a repeated cell, an id at or above cols * global_rows -- are HP_ERR_INVALID before
+ * any device call; between hp_step_begin and hp_step_end the call returns HP_ERR_STATE. */
+int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count);
+/* Records first .. first + count - 1, in the order the links were added over all groups.  Enqueued; valid after hp_sync (the host
+ * memory must stay alive until then).  first + count beyond the domain's links is HP_ERR_INVALID; count == 0 is HP_OK. */
+int hp_links_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_link_record_t* out);
+int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups);   /* host counters; either pointer may be NULL */
+int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups too (and their records) */
 /* Are the domain's area boundaries carried by the flux kernel itself (rain / loss of iteration n+1 added to the state
  * iteration n stores, no separate pass over the grid)?  True for the Godunov scheme with up to three uniform / gridded
  * boundaries, no cell boundary among them, and rain grids of at least 64 model cells per grid cell; everything else runs
