@@ -350,8 +350,9 @@ class OracleTwin:
         self.sim = None
 
 
-def execute(seq, sim):
-    """Run the sequence on `sim`; dict(points=[state at every download], scalars, finite)."""
+def execute(seq, sim, extra=None, point=None):
+    """Run the sequence on `sim`; dict(points=[state at every download], scalars, finite).  `extra(op, sim)` runs the operation kinds
+    this module does not draw and `point(sim)` is what a download compares, its first element the state (host_calls_actors.py)."""
     cfg = seq["cfg"]
     rows, cols, real = cfg["rows"], cfg["cols"], cfg["st"].dtype.type
     live = cfg["st"][..., 1] > -9000                          # (null cells stay what they are)
@@ -429,10 +430,10 @@ def execute(seq, sim):
         elif kind == "sample":
             sim.sample()
         elif kind == "download":
-            points.append(sim.download())
-        else:
+            points.append(sim.download() if point is None else point(sim))
+        elif extra is None or not extra(op, sim):
             raise ValueError(kind)
-    finite = all(bool(np.isfinite(p[live]).all()) for p in points)
+    finite = all(bool(np.isfinite((p if point is None else p[0])[live]).all()) for p in points)
     return dict(points=points, scalars=sim.scalars(), finite=finite, bed=sim.bed)
 
 
