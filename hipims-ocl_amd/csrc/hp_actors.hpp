@@ -1,0 +1,536 @@
+// hp_actors.hpp -- the actors of a domain, host side: what changes the state from outside the flux kernels.  Three kinds: the
+// boundaries (uniform, gridded and cell: hp_kernels.hpp), the link groups among them (hp_links.hpp) and the bed shapes (hp_bed.hpp).
+// Here: their entry points of include/hipims_mi.h, the boundary pass the engine queues in front of an iteration (apply_boundaries)
+// and the choice of what the flux kernel carries of it instead (refresh_fusable), and what hp_state_save / hp_state_restore /
+// hp_domain_destroy do for the bed and the links (*_save, *_restore, *_destroy; actors_* calls them in order).  Their state is
+// declared in hp_domain.hpp (Boundary, BedShapes, LinkStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
+// stays one translation unit.
+#pragma once
+#include "hp_domain.hpp"
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, "hp_bed_*_t layout");
+static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
+
+// ---- the boundaries ----
+// an area boundary as the kernels read it: the stand-alone pass and the fused one are handed the same descriptor
+template <typename T> AreaBdy<T> area_bdy(const Boundary& b)
+{
+	AreaBdy<T> a = AreaBdy<T>{};
+	if (b.kind == BDY_UNIFORM) {
+		a.kind = 0;
+		a.u = UniformBdy<T>{(const T*)b.data, (uint32_t)b.entries, b.definition, (T)b.interval, (T)b.length};
+	} else {
+		a.kind = 1;
+		a.g = GriddedBdy<T>{(const T*)b.data, b.entries, b.grows, b.gcols, b.definition,
+		                    (T)b.resolution, (T)b.off_x, (T)b.off_y, (T)b.interval};
+	}
+	return a;
+}
+
+template <typename T> int apply_boundaries(hp_domain* d, void* target)
+{
+	const Params<T> p = make_params<T>(d);
+	const bool truncated = (d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0;
+	size_t want = ((size_t)p.cols * p.rows + 255) / 256;
+	const dim3 block(256), grid((unsigned)(want < 1024 ? want : 1024));
+	// consecutive uniform / gridded boundaries go out as ONE launch (bdy_area); cell boundaries keep their place in
+	// the order added (the reference's order is unspecified, quirk Q7; ours is the order of the hp_boundary_add_* calls)
+	AreaBdyList<T> list;
+	list.count = 0;
+	auto flush = [&]() {
+		if (list.count == 0) return;
+		hipLaunchKernelGGL(bdy_area<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, list, (State4<T>*)target,
+		                   (const T*)d->bed, truncated, d->fusable ? (const T*)d->cfl_slot + SLOT_BDY : (const T*)nullptr);
+		list.count = 0;
+	};
+	for (const Boundary& b : d->bdy) {
+		if (b.kind == BDY_LINKS) {
+			flush();
+			hipLaunchKernelGGL(bdy_links<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
+			                   (const LinkDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->links.records + b.entries);
+			continue;
+		}
+		if (b.kind == BDY_CELL) {
+			flush();
+			CellBdy<T> c{(const unsigned long long*)b.cells, b.count, (const T*)b.data, b.entries, b.definition,
+			             b.discharge_def, (T)b.interval, (T)b.length};
+			hipLaunchKernelGGL(bdy_cell<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p,
+			                   (const Scalars<T>*)d->scalars, c, (State4<T>*)target, (const T*)d->bed);
+			continue;
+		}
+		if (list.count == AREA_BDY_MAX) flush();
+		list.b[list.count++] = area_bdy<T>(b);
+	}
+	flush();
+	HIP_TRY(hipGetLastError());
+	return HP_OK;
+}
+
+// Which area boundaries the flux kernel carries itself (K1 FUSED, hp_kernels.hpp): Godunov scheme, tuned kernel, nothing but
+// uniform / gridded boundaries (a cell boundary or a link group in between has its place in the order added), at most FUSED_BDY_MAX of
+// them, and rain grids coarse enough for a tile to meet at most two grid rows and a wavefront two grid columns.  Everything
+// else keeps the stand-alone pass.  HP_FUSE_BDY=0 switches the fusion off (A/B runs).
+template <typename T> int refresh_fusable_t(hp_domain* d)
+{
+	static const bool enabled = !(std::getenv("HP_FUSE_BDY") && std::atoi(std::getenv("HP_FUSE_BDY")) == 0);
+	d->fusable = false;
+	if (!enabled || d->desc.scheme != HP_SCHEME_GODUNOV || d->desc.kernel == HP_KERNEL_BASIC) return HP_OK;
+	if (d->bdy.empty() || d->bdy.size() > (size_t)FUSED_BDY_MAX) return HP_OK;
+	AreaBdyList<T> list;
+	list.count = 0;
+	for (const Boundary& b : d->bdy) {
+		if (!is_area(b)) return HP_OK;                                        // a cell boundary or a link group: its place in the order
+		if (b.kind == BDY_GRIDDED && b.resolution < 64.0 * d->desc.dx) return HP_OK;
+		list.b[list.count++] = area_bdy<T>(b);
+	}
+	if (!d->fused_list) HIP_TRY(hipMalloc(&d->fused_list, sizeof(AreaBdyList<double>)));
+	// the flux launches of a batch still in flight read this list: wait for them before it changes (hp_step_batch returns
+	// without waiting, and a blocking copy is not ordered behind a non-blocking stream -- a boundary added right after a
+	// batch call used to rain on that batch's remaining iterations; found by the fuzz's boundary-added-mid-run cases)
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	if (d->stream_halo) HIP_TRY(hipStreamSynchronize(d->stream_halo));
+	HIP_TRY(hipMemcpy(d->fused_list, &list, sizeof list, hipMemcpyHostToDevice));
+	d->fusable = true;
+	return HP_OK;
+}
+
+int refresh_fusable(hp_domain* d)
+{
+	int rc = d->desc.precision == 8 ? refresh_fusable_t<double>(d) : refresh_fusable_t<float>(d);
+	// nothing of a next iteration is in any buffer at this point (a batch's last iteration never fuses)
+	return rc != HP_OK ? rc : zero_bdy_slot(d);
+}
+
+// ---- the moving bed (hp_bed.hpp): the device block of the shapes' lists, and what a checkpoint does for the listed cells ----
+BedLists bed_lists(void* block, const BedLayout& l, const size_t n, const unsigned shapes)
+{
+	char* b = (char*)block;
+	BedLists L = {};
+	L.cells = (const unsigned long long*)(b + l.cells);
+	L.target = (const double*)(b + l.target);
+	L.series = (const double*)(b + l.series);
+	L.base = b + l.base;
+	L.series_off = (const unsigned*)(b + l.series_off);
+	L.shape_of = (const unsigned char*)(b + l.shape_of);
+	L.count = n;
+	L.shapes = shapes;
+	return L;
+}
+void bed_destroy(hp_domain* d) { hipFree(d->beds.block); hipFree(d->beds.info); hipFree(d->beds.saved); }
+
+// hp_state_save, before it touches anything: room for the bed at the listed cells (peaks_save_reserve's rule: a failure leaves the
+// checkpoint before it untouched)
+int bed_save_reserve(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	if (!B.shapes || B.lists.count <= B.saved_room) return HP_OK;
+	void* grown = nullptr;
+	int rc = alloc_or_fail(&grown, (size_t)B.lists.count * d->esize, "hp_state_save: cannot allocate the copy of the listed cells' bed: ");
+	if (rc != HP_OK) return rc;
+	if (B.saved) {
+		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
+		hipFree(B.saved);
+	}
+	B.saved = grown;
+	B.saved_room = (size_t)B.lists.count;
+	return HP_OK;
+}
+// ... and behind the state's copies: hp_state_restore brings back neither the bed nor the boundary list, and levels of one bed over
+// another are no state
+int bed_save(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	B.saved_taken = true;
+	B.saved_epoch = B.epoch;
+	if (!B.shapes || !B.lists.count) return HP_OK;
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (const T*)d->bed, B.lists.cells, 0ull, B.lists.count, (T*)B.saved);
+	});
+	HIP_TRY(hipGetLastError());
+	return HP_OK;
+}
+// hp_state_restore, behind the state's copies
+int bed_restore(hp_domain* d)
+{
+	BedShapes& B = d->beds;
+	if (!B.saved_taken) return HP_OK;
+	if (B.saved_epoch != B.epoch) {                                           // (the probe recorder's rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: bed shapes were added or cleared after the state was saved: the bed is left as it is");
+		return HP_OK;
+	}
+	if (!B.shapes) return HP_OK;
+	d->facts.boundaries_or_bed_changed();
+	if (B.lists.count) {
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			hipLaunchKernelGGL((bed_scatter<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (T*)d->bed, B.lists.cells, B.lists.count, (const T*)B.saved);
+		});
+		HIP_TRY(hipGetLastError());
+	}
+	d->facts.bed_uploaded();
+	return HP_OK;
+}
+
+// ---- link groups (hp_links.hpp): what a checkpoint and hp_boundary_clear do for the links' records ----
+void links_destroy(hp_domain* d) { hipFree(d->links.records); hipFree(d->links.saved); }
+// hp_boundary_clear: the link groups go with the list, and their records with them
+int links_clear(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	if (!L.groups) return HP_OK;
+	HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
+	L.links = 0;
+	L.groups = 0;
+	L.taken.clear();
+	++L.epoch;
+	return HP_OK;
+}
+// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+int links_save_reserve(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	if (!L.links || L.saved) return HP_OK;
+	return alloc_or_fail((void**)&L.saved, (size_t)LINK_MAX * sizeof(hp_link_record_t), "hp_state_save: cannot allocate the copy of the links' records: ");
+}
+int links_save(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	L.saved_taken = true;
+	L.saved_epoch = L.epoch;
+	if (L.links) HIP_TRY(hipMemcpyAsync(L.saved, L.records, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+int links_restore(hp_domain* d)
+{
+	LinkStore& L = d->links;
+	if (!L.saved_taken) return HP_OK;
+	if (L.saved_epoch != L.epoch) {                                           // (the probe recorder's rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: link groups were added or cleared after the state was saved: the links' records start from zero");
+		if (L.links) HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
+		return HP_OK;
+	}
+	if (L.links) HIP_TRY(hipMemcpyAsync(L.records, L.saved, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+
+// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the two ----
+int actors_save_reserve(hp_domain* d) { const int rc = bed_save_reserve(d); return rc != HP_OK ? rc : links_save_reserve(d); }
+int actors_save(hp_domain* d) { const int rc = bed_save(d); return rc != HP_OK ? rc : links_save(d); }
+int actors_restore(hp_domain* d) { const int rc = bed_restore(d); return rc != HP_OK ? rc : links_restore(d); }
+void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); }
+
+} // namespace
+
+// =================================================================================================
+extern "C" {
+
+// ---- the moving bed (hp_bed.hpp) ----
+int hp_bed_shape_add(hp_domain_t* d, const hp_bed_shape_desc_t* desc)
+{
+	// argument checks first: none of them touches the device, and those that do not need the domain come before it (validate_bed_shape)
+	const std::string who = "hp_bed_shape_add";
+	if (!desc) return fail(HP_ERR_INVALID, who + ": desc == NULL");
+	if (desc->struct_size != sizeof(hp_bed_shape_desc_t)) return fail(HP_ERR_INVALID, "hp_bed_shape_desc_t size mismatch (ABI)");
+	std::vector<uint64_t> listed;
+	std::string why;
+	if (!validate_bed_shape(desc, d ? &d->beds.host : nullptr, d ? (uint64_t)d->desc.cols : 0, d ? (uint64_t)d->desc.global_rows : 0, listed, why))
+		return fail(HP_ERR_INVALID, why);
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	BedShapes& B = d->beds;
+	const uint64_t n = desc->cell_count, cols = (uint64_t)d->desc.cols;
+	const unsigned m = desc->series_entries;
+	// this strip's share: the cells whose row lies in its local array, ghost rows included
+	std::vector<uint64_t> cells(B.host.cells);
+	std::vector<double> target(B.host.target);
+	for (uint64_t k = 0; k < n; ++k) {
+		const uint64_t gy = desc->cells[k] / cols, x = desc->cells[k] - gy * cols;
+		if (gy < (uint64_t)d->desc.row_offset || gy >= (uint64_t)(d->desc.row_offset + d->desc.rows)) continue;
+		cells.push_back((gy - (uint64_t)d->desc.row_offset) * cols + x);
+		target.push_back(desc->target[k]);
+	}
+	const size_t n_old = B.host.cells.size(), n_all = cells.size(), pairs_all = B.host.series.size() / 2 + m;
+	const unsigned shapes = B.shapes + 1;
+	// the new block first: if it cannot be had, the domain keeps the shapes it has
+	const BedLayout l = bed_layout(n_all, pairs_all, shapes, d->esize);
+	void* fresh = nullptr;
+	if ((rc = alloc_or_fail(&fresh, l.bytes, who + ": cannot allocate the lists: ")) != HP_OK) return rc;
+	BedBlock* info = B.info;
+	if (!info) {
+		if ((rc = alloc_or_fail((void**)&info, sizeof(BedBlock), who + ": cannot allocate the counters: ")) != HP_OK) { hipFree(fresh); return rc; }
+	}
+	const std::vector<unsigned char> image = bed_image(l, B.host, cells, target, desc->series, m);
+	const BedLists L = bed_lists(fresh, l, n_all, shapes);
+	hipError_t e = hipMemcpyAsync(fresh, image.data(), l.bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess && !B.info) e = hipMemsetAsync(info, 0, sizeof(BedBlock), d->stream);
+	// the base of the shapes that are there moves over; the new shape's is the bed as it is now, gathered on the domain's stream
+	if (e == hipSuccess && n_old) e = hipMemcpyAsync((char*)fresh + l.base, B.lists.base, n_old * d->esize, hipMemcpyDeviceToDevice, d->stream);
+	if (e == hipSuccess && n_all > n_old) {
+		with_real(d, [&](auto zero) { using T = decltype(zero);
+			hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks(n_all - n_old)), dim3(256), 0, d->stream, (const T*)d->bed, L.cells, (unsigned long long)n_old,
+			                   (unsigned long long)(n_all - n_old), (T*)((char*)fresh + l.base));
+		});
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (queued applies still read the old block; the caller's arrays are free on return)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(fresh);
+		if (!B.info) hipFree(info);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the lists: " + hipGetErrorString(e));
+	}
+	hipFree(B.block);
+	B.block = fresh;
+	B.info = info;
+	B.lists = L;
+	B.host.shape_of.resize(n_all, (unsigned char)B.shapes);
+	B.shapes = shapes;
+	B.host.listed.swap(listed);
+	B.host.cells.swap(cells);
+	B.host.target.swap(target);
+	B.host.series.insert(B.host.series.end(), desc->series, desc->series + 2 * (size_t)m);
+	B.host.series_off.push_back((unsigned)pairs_all);
+	++B.epoch;
+	return HP_OK;
+}
+
+int hp_bed_shapes_clear(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	BedShapes& B = d->beds;
+	if (!B.shapes) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_shapes_clear between hp_step_begin and hp_step_end");
+	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (queued applies still use the lists)
+	bed_destroy(d);
+	BedShapes none;
+	none.epoch = B.epoch + 1;
+	none.saved_taken = B.saved_taken;
+	none.saved_epoch = B.saved_epoch;
+	B = none;
+	return HP_OK;
+}
+
+// By contract exactly the host round trip it replaces -- download state and bed, move the bed and shift the levels, hp_domain_upload
+// of the bed, hp_domain_upload of the state --: the kernel patches the buffer hp_domain_download(HP_ARRAY_STATE) reads, and what
+// follows it is what the two uploads do, in their order (hp_engine.hip: hp_domain_upload; state_replaced is the state upload's own tail).
+int hp_bed_apply(hp_domain_t* d)
+{
+	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: an apply never patches a state that is re-run)
+	if (rc != HP_OK) return rc;
+	BedShapes& B = d->beds;
+	if (!B.shapes) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_apply between hp_step_begin and hp_step_end");
+	if (d->facts->ghost_valid != d->ghost_rows)
+		return fail(HP_ERR_STATE, "hp_bed_apply: the strip's ghost rows are not all valid (two reaches after an odd number of iterations): apply after an even batch");
+	const int cur = d->facts->use_alt;
+	const unsigned slot = (unsigned)(B.applies & 1u);
+	with_real(d, [&](auto zero) { using T = decltype(zero);
+		hipLaunchKernelGGL((bed_apply<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (State4<T>*)d->state[cur], (T*)d->bed,
+		                   (const Scalars<T>*)d->scalars, B.lists, B.info, slot);
+	});
+	HIP_TRY(hipGetLastError());
+	++B.applies;
+	d->facts.boundaries_or_bed_changed();
+	d->facts.buffers_written_outside();
+	d->facts.bed_uploaded();
+	// both ping-pong buffers hold the patched state, as after hp_domain_upload(HP_ARRAY_STATE)
+	HIP_TRY(hipMemcpyAsync(d->state[cur ^ 1], d->state[cur], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
+	return state_replaced(d);
+}
+
+int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out)
+{
+	if (!out) return fail(HP_ERR_INVALID, "hp_bed_info: out == NULL");
+	if (out->struct_size != sizeof(hp_bed_info_t)) return fail(HP_ERR_INVALID, "hp_bed_info_t size mismatch (ABI)");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	const BedShapes& B = d->beds;
+	out->shapes = B.shapes;
+	out->cells_local = B.lists.count;
+	out->applies = B.applies;
+	out->changed_last = out->changed_total = 0;
+	out->t_last = 0.0;
+	if (!B.shapes) return HP_OK;
+	BedBlock host;
+	HIP_TRY(hipMemcpyAsync(&host, B.info, sizeof host, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	if (B.applies) out->changed_last = host.changed[(B.applies - 1) & 1u];
+	out->changed_total = host.changed_total;
+	out->t_last = host.t_last;
+	return HP_OK;
+}
+
+// ---- the boundaries ----
+int hp_boundary_add_uniform(hp_domain_t* d, int definition, const void* series, uint32_t entries,
+                            double interval, double length)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	d->facts.boundaries_or_bed_changed();
+	if (!series || entries == 0 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad uniform boundary");
+	if (definition != HP_UNIFORM_RAIN_INTENSITY && definition != HP_UNIFORM_LOSS_RATE)
+		return fail(HP_ERR_INVALID, "unknown uniform boundary definition");
+	Boundary b{};
+	b.kind = BDY_UNIFORM; b.definition = definition; b.entries = entries; b.interval = interval; b.length = length;
+	if ((rc = upload_or_fail(&b.data, series, (size_t)entries * 2 * d->esize, "hp_boundary_add_uniform: cannot upload the series: ")) != HP_OK) return rc;
+	d->bdy.push_back(b);
+	return refresh_fusable(d);
+}
+
+int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, uint64_t entries,
+                            uint64_t grid_rows, uint64_t grid_cols, double resolution,
+                            double offset_x, double offset_y, double interval)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	d->facts.boundaries_or_bed_changed();
+	if (!grids || entries == 0 || grid_rows == 0 || grid_cols == 0 || !(resolution > 0) || !(interval > 0))
+		return fail(HP_ERR_INVALID, "bad gridded boundary");
+	{
+		// bdy_Gridded indexes floor((x dx - off) / res) without a range check (CLBoundaries.clc:231-236): a grid that
+		// does not cover the interior cells reads outside the buffer.  Rejected here instead.
+		const double dx = d->desc.dx;
+		const double x_lo = 1.0 * dx - offset_x, x_hi = (double)(d->desc.cols - 2) * dx - offset_x;
+		const double y_lo = 1.0 * dx - offset_y, y_hi = (double)(d->desc.global_rows - 2) * dx - offset_y;
+		if (x_lo < 0.0 || y_lo < 0.0 || std::floor(x_hi / resolution) >= (double)grid_cols ||
+		    std::floor(y_hi / resolution) >= (double)grid_rows)
+			return fail(HP_ERR_INVALID, "gridded boundary does not cover the domain's interior cells");
+	}
+	Boundary b{};
+	b.kind = BDY_GRIDDED; b.definition = definition; b.entries = entries; b.grows = grid_rows; b.gcols = grid_cols;
+	b.resolution = resolution; b.off_x = offset_x; b.off_y = offset_y; b.interval = interval;
+	if ((rc = upload_or_fail(&b.data, grids, (size_t)entries * grid_rows * grid_cols * d->esize, "hp_boundary_add_gridded: cannot upload the grids: ")) != HP_OK) return rc;
+	d->bdy.push_back(b);
+	return refresh_fusable(d);
+}
+
+int hp_boundary_add_cell(hp_domain_t* d, int depth_definition, int discharge_definition, const uint64_t* cells,
+                         uint64_t count, const void* series, uint64_t entries, double interval, double length)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	d->facts.boundaries_or_bed_changed();
+	if (!cells || count == 0 || !series || entries < 2 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad cell boundary");
+	if (depth_definition < 0 || depth_definition > 3 || discharge_definition < 0 || discharge_definition > 3)
+		return fail(HP_ERR_INVALID, "unknown cell boundary definition");
+	const uint64_t global_cells = (uint64_t)d->desc.cols * (uint64_t)d->desc.global_rows;
+	bool on_ring = false;
+	{
+		const uint64_t w = (uint64_t)stencil_reach(d->desc), cols = (uint64_t)d->desc.cols, grows = (uint64_t)d->desc.global_rows;
+		for (uint64_t i = 0; i < count; ++i) {
+			if (cells[i] >= global_cells) return fail(HP_ERR_INVALID, "cell boundary id outside the grid");
+			const uint64_t gy = cells[i] / cols, x = cells[i] - gy * cols;
+			on_ring = on_ring || x < w || x + w >= cols || gy < w || gy + w >= grows;
+		}
+	}
+	if (length > (double)(entries - 1) * interval + 1e-9)
+		return fail(HP_ERR_INVALID, "cell boundary series shorter than its length (interpolation reads entry n+1)");
+	Boundary b{};
+	b.kind = BDY_CELL; b.definition = depth_definition; b.discharge_def = discharge_definition; b.count = count;
+	b.entries = entries; b.interval = interval; b.length = length;
+	if ((rc = upload_or_fail(&b.cells, cells, count * sizeof(uint64_t), "hp_boundary_add_cell: cannot upload the cells: ")) != HP_OK) return rc;
+	if ((rc = upload_or_fail(&b.data, series, (size_t)entries * 4 * d->esize, "hp_boundary_add_cell: cannot upload the series: ")) != HP_OK) { hipFree(b.cells); return rc; }
+	d->bdy.push_back(b);
+	d->bdy_on_ring = d->bdy_on_ring || on_ring;
+	return refresh_fusable(d);
+}
+
+int hp_boundary_clear(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	d->facts.boundaries_or_bed_changed();
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	for (auto& b : d->bdy) { hipFree(b.data); hipFree(b.cells); }
+	d->bdy.clear();
+	d->bdy_on_ring = false;
+	if ((rc = links_clear(d)) != HP_OK) return rc;
+	return refresh_fusable(d);
+}
+
+// ---- link groups (hp_links.hpp) ----
+int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count)
+{
+	// argument checks first: none of them touches the device (hp_links.hpp: validate_links)
+	const std::string who = "hp_boundary_add_links";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	LinkStore& L = d->links;
+	const uint64_t cols = (uint64_t)d->desc.cols, reach = (uint64_t)stencil_reach(d->desc);
+	std::vector<uint64_t> taken;
+	std::string why;
+	if (!validate_links(links, count, L.links, cols, (uint64_t)d->desc.global_rows, reach, L.taken, taken, why)) return fail(HP_ERR_INVALID, why);
+	// this strip's share: both ends of a link, or neither (links_strip_verdict)
+	const int64_t lo = d->desc.row_offset, hi = d->desc.row_offset + d->desc.rows;
+	const int64_t stale = d->ghost_rows > (int64_t)reach ? d->ghost_rows - (int64_t)reach : 0;      // (two reaches stored: the outer one)
+	const int64_t stale_lo = lo > 0 ? stale : 0, stale_hi = hi < d->desc.global_rows ? stale : 0;
+	std::vector<LinkDev> dev((size_t)count);
+	for (uint64_t k = 0; k < count; ++k) {
+		const hp_link_t& l = links[k];
+		const int64_t ya = (int64_t)(l.cell_a / cols), yb = (int64_t)(l.cell_b / cols);
+		const int verdict = links_strip_verdict(ya, yb, lo, hi, stale_lo, stale_hi);
+		if (verdict == LINK_ONE)
+			return fail(HP_ERR_UNSUPPORTED, who + ": link " + std::to_string(k) + " (cells " + std::to_string(l.cell_a) + " and " + std::to_string(l.cell_b) +
+			            "): this strip stores rows " + std::to_string(lo) + " to " + std::to_string(hi - 1) + " and would hold exactly one of its ends on every iteration");
+		LinkDev& o = dev[(size_t)k];
+		o.a = verdict == LINK_BOTH ? l.cell_a - (uint64_t)lo * cols : LINK_ABSENT;
+		o.b = verdict == LINK_BOTH ? l.cell_b - (uint64_t)lo * cols : LINK_ABSENT;
+		o.kind = l.kind; o.one_way = l.one_way; o.level = l.level; o.size = l.size; o.coeff = l.coeff; o.limit = l.limit;
+	}
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	if (!L.records) {
+		if ((rc = alloc_or_fail((void**)&L.records, (size_t)LINK_MAX * sizeof(hp_link_record_t), who + ": cannot allocate the records: ")) != HP_OK) return rc;
+		HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)LINK_MAX * sizeof(hp_link_record_t), d->stream));
+	}
+	Boundary b{};
+	b.kind = BDY_LINKS; b.count = count; b.entries = L.links;
+	if ((rc = alloc_or_fail(&b.cells, (size_t)count * sizeof(LinkDev), who + ": cannot allocate the links: ")) != HP_OK) return rc;
+	hipError_t e = hipMemcpyAsync(b.cells, dev.data(), (size_t)count * sizeof(LinkDev), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (`dev` goes with this call)
+	if (e != hipSuccess) { hipFree(b.cells); return fail(HP_ERR_HIP, who + ": writing the links: " + hipGetErrorString(e)); }
+	d->facts.boundaries_or_bed_changed();
+	d->bdy.push_back(b);
+	L.links += count;
+	L.groups += 1;
+	L.taken.swap(taken);
+	++L.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_links_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_link_record_t* out)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (first > d->links.links || count > d->links.links - first) return fail(HP_ERR_INVALID, "hp_links_read: first + count beyond the domain's links");
+	if (count == 0) return HP_OK;
+	if (!out) return fail(HP_ERR_INVALID, "hp_links_read: out == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_links_read between hp_step_begin and hp_step_end");
+	HIP_TRY(hipMemcpyAsync(out, d->links.records + first, (size_t)count * sizeof(hp_link_record_t), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (links) *links = d->links.links;
+	if (groups) *groups = d->links.groups;
+	return HP_OK;
+}
+
+int hp_boundaries_fused(hp_domain_t* d, int* fused)
+{
+	if (!d || !fused) return fail(HP_ERR_INVALID, "null argument");
+	*fused = d->fusable ? 1 : 0;
+	return HP_OK;
+}
+
+} // extern "C"

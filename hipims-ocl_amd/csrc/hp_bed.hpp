@@ -6,8 +6,11 @@
 // The arithmetic of the fraction and of the new bed is ONE definition in plain C++ (bed_fraction, bed_level, bed_round below): the
 // kernel uses it, tests/bed_probe.cpp includes this file with a host compiler, and frontend.BedShapes restates it in NumPy.  All
 // of it is fp64 and uses correctly rounded multiply, add, divide and compare only; nothing is fused: hp_engine.hip's translation
-// unit is built with -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.
+// unit is built with -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.  Behind the arithmetic, HIP-free as well and
+// in the probe's reach: what hp_bed_shape_add (hp_actors.hpp) does before it touches the device -- its argument checks
+// (validate_bed_shape), the layout of the lists' device block (bed_layout) and the block's bytes (bed_image).
 #pragma once
+#include "../../include/hipims_mi.h"
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -57,6 +60,99 @@ HP_BED_FN double bed_level(const double base, const double target, const double 
 
 // ... and rounded once: b1
 template <typename T> HP_BED_FN T bed_round(const double base, const double target, const double f) { return (T)bed_level(base, target, f); }
+
+} // namespace hp
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace hp {
+
+// The host's copies of a domain's lists (BedShapes, hp_domain.hpp)
+struct BedHost {
+	std::vector<uint64_t> listed;                     // GLOBAL ids of every cell of every shape, sorted: the repeated-cell check
+	std::vector<uint64_t> cells;                      // LOCAL ids, shape after shape
+	std::vector<double>   target;
+	std::vector<unsigned char> shape_of;
+	std::vector<double>   series;
+	std::vector<unsigned> series_off = {0u};          // [shapes + 1]
+};
+
+// -------------------------------------------------------------------------------------------------
+// validate_bed_shape : every argument error of hp_bed_shape_add behind the descriptor's own (NULL, ABI size) that needs no device,
+//     in the order the entry point has always raised them.  `have`: the domain's lists so far, NULL for a NULL domain -- then only
+//     the checks in front of "null domain" run.  On success `listed_after` holds have->listed merged with the new cells.  Returns
+//     false with `why` set.
+// -------------------------------------------------------------------------------------------------
+inline bool validate_bed_shape(const hp_bed_shape_desc_t* desc, const BedHost* have, const uint64_t cols, const uint64_t global_rows,
+                               std::vector<uint64_t>& listed_after, std::string& why)
+{
+	const std::string who = "hp_bed_shape_add";
+	if (!desc->cells || !desc->target || !desc->series) { why = who + ": cells / target / series == NULL"; return false; }
+	if (desc->series_entries < 1 || desc->series_entries > BED_MAX_SERIES) { why = who + ": series_entries outside 1..4096"; return false; }
+	if (desc->cell_count < 1 || desc->cell_count > BED_MAX_CELLS) { why = who + ": cell_count outside 1..1048576"; return false; }
+	const uint64_t n = desc->cell_count;
+	for (uint64_t k = 0; k < n; ++k)
+		if (!std::isfinite(desc->target[k]) || std::fabs(desc->target[k]) > BED_MAX_LEVEL) { why = who + ": target " + std::to_string(k) + " is not a finite elevation of at most 9999"; return false; }
+	for (unsigned k = 0; k < desc->series_entries; ++k) {
+		const double t = desc->series[2 * k], f = desc->series[2 * k + 1];
+		if (!std::isfinite(t) || (k > 0 && !(t > desc->series[2 * k - 2]))) { why = who + ": series entry " + std::to_string(k) + ": times must be finite and strictly increasing"; return false; }
+		if (!(f >= 0.0 && f <= 1.0)) { why = who + ": series entry " + std::to_string(k) + ": fraction outside [0, 1]"; return false; }
+	}
+	std::vector<uint64_t> sorted(desc->cells, desc->cells + n);
+	std::sort(sorted.begin(), sorted.end());
+	auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+	if (twice != sorted.end()) { why = who + ": cell " + std::to_string(*twice) + " is listed twice"; return false; }
+	if (!have) return true;
+	if (sorted.back() >= cols * global_rows) { why = who + ": cell " + std::to_string(sorted.back()) + " lies outside the grid"; return false; }
+	if (have->series_off.size() > BED_MAX_SHAPES) { why = who + ": more than 64 shapes"; return false; }
+	if (have->listed.size() + n > BED_MAX_CELLS) { why = who + ": more than 1048576 cells over all shapes"; return false; }
+	listed_after.resize(have->listed.size() + (size_t)n);
+	std::merge(have->listed.begin(), have->listed.end(), sorted.begin(), sorted.end(), listed_after.begin());
+	twice = std::adjacent_find(listed_after.begin(), listed_after.end());
+	if (twice != listed_after.end()) { why = who + ": cell " + std::to_string(*twice) + " is listed twice (another shape has it)"; return false; }
+	return true;
+}
+
+// The device block of the lists of n cells, `pairs` series entries and `shapes` shapes (BedLists points into it), in bytes:
+// [cells: n x 8 | target: n x 8 | series: pairs x 16 | base: n elements, to 8 | series_off: (shapes + 1) x 4, to 8 | shape_of: n]
+struct BedLayout { size_t cells, target, series, base, series_off, shape_of, bytes; };
+inline BedLayout bed_layout(const size_t n, const size_t pairs, const size_t shapes, const size_t esize)
+{
+	BedLayout l;
+	l.cells = 0;
+	l.target = l.cells + n * 8;
+	l.series = l.target + n * 8;
+	l.base = l.series + pairs * 16;
+	l.series_off = l.base + (n * esize + 7) / 8 * 8;
+	l.shape_of = l.series_off + ((shapes + 1) * 4 + 7) / 8 * 8;
+	l.bytes = l.shape_of + std::max<size_t>(n, 1);
+	return l;
+}
+
+// The block's bytes for the shapes of `old` plus one more, of the m series entries `series`: `cells` and `target` are old's with
+// this strip's share of the new shape behind them, `l` the layout of the lot.  (base is the device's to fill: bed_gather)
+inline std::vector<unsigned char> bed_image(const BedLayout& l, const BedHost& old, const std::vector<uint64_t>& cells, const std::vector<double>& target,
+                                            const double* series, const unsigned m)
+{
+	const size_t n_old = old.cells.size(), n_all = cells.size(), pairs_old = old.series.size() / 2, shapes = old.series_off.size();
+	std::vector<unsigned char> image(l.bytes, 0);
+	if (n_all) {
+		std::memcpy(image.data() + l.cells, cells.data(), n_all * 8);
+		std::memcpy(image.data() + l.target, target.data(), n_all * 8);
+		if (n_old) std::memcpy(image.data() + l.shape_of, old.shape_of.data(), n_old);
+		std::memset(image.data() + l.shape_of + n_old, (int)(shapes - 1), n_all - n_old);
+	}
+	if (pairs_old) std::memcpy(image.data() + l.series, old.series.data(), pairs_old * 16);
+	std::memcpy(image.data() + l.series + pairs_old * 16, series, (size_t)m * 16);
+	std::memcpy(image.data() + l.series_off, old.series_off.data(), shapes * 4);
+	const unsigned end = (unsigned)(pairs_old + m);
+	std::memcpy(image.data() + l.series_off + shapes * 4, &end, 4);
+	return image;
+}
 
 } // namespace hp
 

@@ -1,6 +1,8 @@
-// hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain
-// and the map of its pinned host block.  Internal to the library's one translation unit: hp_engine.hip includes it, then
-// hp_observers.hpp (the code of the four observers whose state is declared here, and of the RecordLog two of them share).
+// hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain,
+// the map of its pinned host block and the helpers more than one part uses (with_real, alloc_or_fail, upload_or_fail, stream_blocks,
+// stencil_reach, state_replaced).  Internal to the library's one translation unit: hp_engine.hip includes it, then hp_observers.hpp
+// (the code of the four observers whose state is declared here, and of the RecordLog two of them share) and hp_actors.hpp (the code
+// of the boundaries, the link groups among them, and the moving bed: Boundary, LinkStore and BedShapes below).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_facts.hpp"
@@ -14,6 +16,7 @@
 #include "hp_links.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -48,8 +51,40 @@ void log_line(int level, const std::string& msg)
 			return fail(HP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
 	} while (0)
 
+// Device (or pinned host) memory, or the call fails with `what` + the runtime's reason.  The sticky last error is cleared: the
+// launches of later steps ask for it, and this one is dealt with here.
+int alloc_or_fail(void** p, const size_t bytes, const std::string& what, const bool pinned = false)
+{
+	const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+	if (e == hipSuccess) return HP_OK;
+	*p = nullptr;
+	(void)hipGetLastError();
+	return fail(HP_ERR_HIP, what + hipGetErrorString(e));
+}
+// ... filled from `host` by a blocking copy (`host` is free on return); a failed copy frees it again
+int upload_or_fail(void** dev, const void* host, const size_t bytes, const std::string& what)
+{
+	const int rc = alloc_or_fail(dev, bytes, what);
+	if (rc != HP_OK) return rc;
+	const hipError_t e = hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
+	if (e == hipSuccess) return HP_OK;
+	hipFree(*dev);
+	*dev = nullptr;
+	(void)hipGetLastError();
+	return fail(HP_ERR_HIP, what + hipGetErrorString(e));
+}
+
+// a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
+inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
+
+// stencil reach of the scheme = ghost rows one iteration consumes, and the width of the never-written edge ring
+inline long stencil_reach(const hp_domain_desc_t& desc) { return desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? 2 : 1; }
+
+// ---- the actors' state (their code: hp_actors.hpp) ----
+// a boundary, in the order added.  The first two are the AREA boundaries (AreaBdy, hp_kernels.hpp): consecutive ones share a launch
+enum BoundaryKind { BDY_UNIFORM, BDY_GRIDDED, BDY_CELL, BDY_LINKS };          // BDY_LINKS: cells is its LinkDev array, entries its first record
 struct Boundary {
-	int      kind;         // 0 uniform, 1 gridded, 2 cell, 3 link group (cells: its LinkDev array, entries: its first record)
+	BoundaryKind kind;
 	int      definition;
 	int      discharge_def;
 	void*    cells;        // device: global cell ids (cell boundaries)
@@ -58,6 +93,7 @@ struct Boundary {
 	uint64_t entries, grows, gcols;
 	double   interval, length, resolution, off_x, off_y;
 };
+inline bool is_area(const Boundary& b) { return b.kind == BDY_UNIFORM || b.kind == BDY_GRIDDED; }
 
 // ---- the observers' state (their code: hp_observers.hpp) ----
 // the output stage (hp_output.hpp, hp_overview.hpp, hp_sparse.hpp; hp_domain_derive / hp_domain_overview / hp_domain_sparse / hp_domain_stats):
@@ -106,6 +142,7 @@ struct ZoneRecorder {
 	double           flood_depth = 0.0;
 };
 
+// ---- the other actors' state ----
 // the moving bed (hp_bed.hpp; hp_bed_*): nothing of it exists while the domain has no shape.  Not an observer: an apply writes the
 // bed and the state -- by contract exactly what the two uploads of the host round trip it replaces write
 struct BedShapes {
@@ -115,13 +152,7 @@ struct BedShapes {
 	BedBlock*        info = nullptr;                  // device: what the applies leave for hp_bed_info
 	uint64_t         applies = 0;                     // applies queued since the first shape was added (its parity picks the counter word)
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's beds belong to one epoch
-	// host copies of the lists: a new shape rewrites the device block as a whole
-	std::vector<uint64_t> listed;                     // GLOBAL ids of every cell of every shape, sorted: the repeated-cell check
-	std::vector<uint64_t> cells;                      // LOCAL ids, shape after shape
-	std::vector<double>   target;
-	std::vector<unsigned char> shape_of;
-	std::vector<double>   series;
-	std::vector<unsigned> series_off = {0u};
+	BedHost          host;                            // host copies of the lists: a new shape rewrites the device block as a whole
 	// hp_state_save's copy of the bed at the listed cells
 	void*            saved = nullptr;
 	size_t           saved_room = 0;                  // cells it holds
@@ -129,7 +160,7 @@ struct BedShapes {
 	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
-// link groups (hp_links.hpp; hp_boundary_add_links): the groups themselves are Boundary entries of kind 3, in the order added; this
+// link groups (hp_links.hpp; hp_boundary_add_links): the groups themselves are Boundary entries of kind BDY_LINKS, in the order added; this
 // is what they share.  Nothing of it exists while the domain has never had a link
 struct LinkStore {
 	uint64_t         links = 0;                       // links of all groups
@@ -277,6 +308,25 @@ static_assert(HOST_HANDSHAKE + 128 + 8 * sizeof(double) <= HOST_TAIL_ERR && HOST
 static_assert(HOST_SPEC_FLAG + 8 <= HOST_READBACK && HOST_READBACK + 16 <= HOST_RINGS && HOST_RINGS + 8 <= HOST_BLOCK_BYTES, "pinned block: flag / read-backs / rings");
 
 int check_domain(hp_domain* d);           // (hp_engine.hip: every entry point that touches the device comes through it)
+template <typename T> Params<T> make_params(const hp_domain* d);             // (hp_engine.hip)
+template <typename T> int apply_boundaries(hp_domain* d, void* target);      // (hp_actors.hpp: the boundaries, in the order added, onto `target`)
+
+// f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
+template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }
+
+// SLOT_BDY (the fused boundaries' contribution to the next maximum) holds nothing of an iteration to come
+inline int zero_bdy_slot(hp_domain* d)
+{
+	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
+	return HP_OK;
+}
+// Both state buffers have just been queued the same new state (hp_domain_upload(HP_ARRAY_STATE), hp_bed_apply): what goes with it
+inline int state_replaced(hp_domain* d)
+{
+	d->tune_phase = 0;                                                    // (a sample still in flight measured the state that has just been replaced)
+	d->facts.full_state_uploaded(d->ghost_rows);                          // (use_alt = 0: CSchemeGodunov.cpp:1075)
+	return zero_bdy_slot(d);
+}
 
 inline int check_rows(const hp_domain* d, const int64_t row0, const int64_t nrows)
 {

@@ -1,10 +1,14 @@
-// hp_engine.hip -- host side of libhipims_mi.so: the C ABI of include/hipims_mi.h over the HIP kernels.
+// hp_engine.hip -- host side of libhipims_mi.so: the C ABI of include/hipims_mi.h over the HIP kernels.  Here: the domain's life,
+// uploads and downloads, checkpoints, and stepping -- tile launches, iteration pairs and their tuner, speculative batches, strips over
+// RCCL and the peer mailboxes.  What reads the state (the observers) and what changes it from outside the flux kernels (the actors:
+// boundaries, link groups, bed shapes) live in hp_observers.hpp and hp_actors.hpp.
 //
 // Mirrors what the reference's CSchemeGodunov / CSchemeMUSCLHancock do against COCLDevice/COCLBuffer/COCLKernel
 // (buffers: CSchemeGodunov.cpp:789-892; iteration graph: :1617-1666) -- one HIP stream per domain stands in for
 // the reference's per-device command queue, stream order for its explicit queueBarrier() calls.
 #include "hp_domain.hpp"        // fail / HIP_TRY, struct hp_domain, the map of its pinned block
 #include "hp_observers.hpp"     // output stage, peak tracker, probe recorder: their entry points and what a checkpoint does for them
+#include "hp_actors.hpp"        // boundaries, link groups, bed shapes: their entry points, the boundary pass, what a checkpoint does for them
 #include <hip/hip_ext.h>
 #include <dlfcn.h>
 
@@ -48,9 +52,6 @@ static unsigned tail_limit()
 	return v < TAIL_MAX_BLOCKS ? v : TAIL_MAX_BLOCKS;
 }
 
-// stencil reach of the scheme = ghost rows one iteration consumes
-inline long strip_ghosts(const hp_domain* d) { return d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? 2 : 1; }
-
 template <typename T> Params<T> make_params(const hp_domain* d)
 {
 	Params<T> p;
@@ -84,54 +85,6 @@ inline dim3 grid2d(long cols, long rows, dim3 block)
 	return dim3((unsigned)((cols + block.x - 1) / block.x), (unsigned)((rows + block.y - 1) / block.y));
 }
 
-template <typename T> int apply_boundaries(hp_domain* d, void* target)
-{
-	const Params<T> p = make_params<T>(d);
-	const bool truncated = (d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0;
-	size_t want = ((size_t)p.cols * p.rows + 255) / 256;
-	const dim3 block(256), grid((unsigned)(want < 1024 ? want : 1024));
-	// consecutive uniform / gridded boundaries go out as ONE launch (bdy_area); cell boundaries keep their place in
-	// the order added (the reference's order is unspecified, quirk Q7; ours is the order of the hp_boundary_add_* calls)
-	AreaBdyList<T> list;
-	list.count = 0;
-	auto flush = [&]() {
-		if (list.count == 0) return;
-		hipLaunchKernelGGL(bdy_area<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, list, (State4<T>*)target,
-		                   (const T*)d->bed, truncated, d->fusable ? (const T*)d->cfl_slot + SLOT_BDY : (const T*)nullptr);
-		list.count = 0;
-	};
-	for (const Boundary& b : d->bdy) {
-		if (b.kind == 3) {
-			flush();
-			hipLaunchKernelGGL(bdy_links<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
-			                   (const LinkDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->links.records + b.entries);
-			continue;
-		}
-		if (b.kind == 2) {
-			flush();
-			CellBdy<T> c{(const unsigned long long*)b.cells, b.count, (const T*)b.data, b.entries, b.definition,
-			             b.discharge_def, (T)b.interval, (T)b.length};
-			hipLaunchKernelGGL(bdy_cell<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p,
-			                   (const Scalars<T>*)d->scalars, c, (State4<T>*)target, (const T*)d->bed);
-			continue;
-		}
-		if (list.count == AREA_BDY_MAX) flush();
-		AreaBdy<T>& a = list.b[list.count++];
-		a = AreaBdy<T>{};
-		if (b.kind == 0) {
-			a.kind = 0;
-			a.u = UniformBdy<T>{(const T*)b.data, (uint32_t)b.entries, b.definition, (T)b.interval, (T)b.length};
-		} else {
-			a.kind = 1;
-			a.g = GriddedBdy<T>{(const T*)b.data, b.entries, b.grows, b.gcols, b.definition,
-			                    (T)b.resolution, (T)b.off_x, (T)b.off_y, (T)b.interval};
-		}
-	}
-	flush();
-	HIP_TRY(hipGetLastError());
-	return HP_OK;
-}
-
 template <typename T> int launch_reduce(hp_domain* d, const void* state, long row_lo, long row_hi)
 {
 	const Params<T> p = make_params<T>(d);
@@ -154,7 +107,7 @@ template <typename T> int price_edge_ring(hp_domain* d)
 {
 	const Params<T> p = make_params<T>(d);
 	HIP_TRY(hipMemsetAsync((T*)d->cfl_slot + SLOT_EDGE, 0, 2 * sizeof(T), d->stream));
-	const int w = (d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK) ? 2 : 1;
+	const int w = (int)stencil_reach(d->desc);
 	const bool at_south = d->desc.row_offset == 0;
 	const bool at_north = d->desc.row_offset + d->desc.rows == d->desc.global_rows;
 	const long south = at_south ? 0 : -1;
@@ -713,7 +666,7 @@ static bool pair_exact(const hp_domain* d)
 	static const int forced = std::getenv("HP_PAIR_EXACT") ? (std::atoi(std::getenv("HP_PAIR_EXACT")) != 0 ? 1 : 0) : -1;
 	if (forced >= 0) return forced != 0;
 	for (const Boundary& b : d->bdy)
-		if ((b.kind == 0 && b.definition == HP_UNIFORM_LOSS_RATE) || (b.kind == 1 && b.definition == HP_GRIDDED_MASS_FLUX)) return true;
+		if ((b.kind == BDY_UNIFORM && b.definition == HP_UNIFORM_LOSS_RATE) || (b.kind == BDY_GRIDDED && b.definition == HP_GRIDDED_MASS_FLUX)) return true;
 	return false;
 }
 static int pair_stamps_alloc(hp_domain* d)
@@ -946,53 +899,6 @@ template <typename T> int set_scalar_field(hp_domain* d, size_t offset, double v
 	return HP_OK;
 }
 
-
-// Which area boundaries the flux kernel carries itself (K1 FUSED, hp_kernels.hpp): Godunov scheme, tuned kernel, nothing but
-// uniform / gridded boundaries (a cell boundary or a link group in between has its place in the order added), at most FUSED_BDY_MAX of
-// them, and rain grids coarse enough for a tile to meet at most two grid rows and a wavefront two grid columns.  Everything
-// else keeps the stand-alone pass.  HP_FUSE_BDY=0 switches the fusion off (A/B runs).
-template <typename T> int refresh_fusable_t(hp_domain* d)
-{
-	static const bool enabled = !(std::getenv("HP_FUSE_BDY") && std::atoi(std::getenv("HP_FUSE_BDY")) == 0);
-	d->fusable = false;
-	if (!enabled || d->desc.scheme != HP_SCHEME_GODUNOV || d->desc.kernel == HP_KERNEL_BASIC) return HP_OK;
-	if (d->bdy.empty() || d->bdy.size() > (size_t)FUSED_BDY_MAX) return HP_OK;
-	AreaBdyList<T> list;
-	list.count = 0;
-	for (const Boundary& b : d->bdy) {
-		if (b.kind >= 2) return HP_OK;                                        // a cell boundary or a link group: its place in the order
-		AreaBdy<T>& a = list.b[list.count++];
-		a = AreaBdy<T>{};
-		if (b.kind == 0) {
-			a.kind = 0;
-			a.u = UniformBdy<T>{(const T*)b.data, (uint32_t)b.entries, b.definition, (T)b.interval, (T)b.length};
-		} else {
-			if (b.resolution < 64.0 * d->desc.dx) return HP_OK;
-			a.kind = 1;
-			a.g = GriddedBdy<T>{(const T*)b.data, b.entries, b.grows, b.gcols, b.definition,
-			                    (T)b.resolution, (T)b.off_x, (T)b.off_y, (T)b.interval};
-		}
-	}
-	if (!d->fused_list) HIP_TRY(hipMalloc(&d->fused_list, sizeof(AreaBdyList<double>)));
-	// the flux launches of a batch still in flight read this list: wait for them before it changes (hp_step_batch returns
-	// without waiting, and a blocking copy is not ordered behind a non-blocking stream -- a boundary added right after a
-	// batch call used to rain on that batch's remaining iterations; found by the fuzz's boundary-added-mid-run cases)
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	if (d->stream_halo) HIP_TRY(hipStreamSynchronize(d->stream_halo));
-	HIP_TRY(hipMemcpy(d->fused_list, &list, sizeof list, hipMemcpyHostToDevice));
-	d->fusable = true;
-	return HP_OK;
-}
-
-int refresh_fusable(hp_domain* d)
-{
-	int rc = d->desc.precision == 8 ? refresh_fusable_t<double>(d) : refresh_fusable_t<float>(d);
-	if (rc != HP_OK) return rc;
-	// nothing of a next iteration is in any buffer at this point (a batch's last iteration never fuses)
-	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
-	return HP_OK;
-}
-
 int spec_resolve(hp_domain* d);
 int tail_failed_error()
 {
@@ -1009,121 +915,6 @@ int check_domain(hp_domain* d)
 	// a speculative STRICT batch is still to be looked at: whoever enters the library next does that first, so that nothing is
 	// ever queued behind -- or read from -- a batch that has to be re-run
 	if (d->spec_pending) return spec_resolve(d);
-	return HP_OK;
-}
-
-// ---- the moving bed (hp_bed.hpp): the device block of the shapes' lists, and what a checkpoint does for the listed cells ----
-static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, "hp_bed_*_t layout");
-// [cells: n x 8 | target: n x 8 | series: pairs x 16 | base: n elements, to 8 | series_off: (shapes + 1) x 4, to 8 | shape_of: n]
-struct BedLayout { size_t cells, target, series, base, series_off, shape_of, bytes; };
-BedLayout bed_layout(const size_t n, const size_t pairs, const size_t shapes, const size_t esize)
-{
-	BedLayout l;
-	l.cells = 0;
-	l.target = l.cells + n * 8;
-	l.series = l.target + n * 8;
-	l.base = l.series + pairs * 16;
-	l.series_off = l.base + (n * esize + 7) / 8 * 8;
-	l.shape_of = l.series_off + ((shapes + 1) * 4 + 7) / 8 * 8;
-	l.bytes = l.shape_of + std::max<size_t>(n, 1);
-	return l;
-}
-BedLists bed_lists(void* block, const BedLayout& l, const size_t n, const unsigned shapes)
-{
-	char* b = (char*)block;
-	BedLists L = {};
-	L.cells = (const unsigned long long*)(b + l.cells);
-	L.target = (const double*)(b + l.target);
-	L.series = (const double*)(b + l.series);
-	L.base = b + l.base;
-	L.series_off = (const unsigned*)(b + l.series_off);
-	L.shape_of = (const unsigned char*)(b + l.shape_of);
-	L.count = n;
-	L.shapes = shapes;
-	return L;
-}
-void bed_destroy(hp_domain* d) { hipFree(d->beds.block); hipFree(d->beds.info); hipFree(d->beds.saved); }
-
-// hp_state_save, before it touches anything: room for the bed at the listed cells (peaks_save_reserve's rule: a failure leaves the
-// checkpoint before it untouched)
-int bed_save_reserve(hp_domain* d)
-{
-	BedShapes& B = d->beds;
-	if (!B.shapes || B.lists.count <= B.saved_room) return HP_OK;
-	void* grown = nullptr;
-	int rc = alloc_or_fail(&grown, (size_t)B.lists.count * d->esize, "hp_state_save: cannot allocate the copy of the listed cells' bed: ");
-	if (rc != HP_OK) return rc;
-	if (B.saved) {
-		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
-		hipFree(B.saved);
-	}
-	B.saved = grown;
-	B.saved_room = (size_t)B.lists.count;
-	return HP_OK;
-}
-// ... and behind the state's copies: hp_state_restore brings back neither the bed nor the boundary list, and levels of one bed over
-// another are no state
-int bed_save(hp_domain* d)
-{
-	BedShapes& B = d->beds;
-	B.saved_taken = true;
-	B.saved_epoch = B.epoch;
-	if (!B.shapes || !B.lists.count) return HP_OK;
-	with_real(d, [&](auto zero) { using T = decltype(zero);
-		hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (const T*)d->bed, B.lists.cells, 0ull, B.lists.count, (T*)B.saved);
-	});
-	HIP_TRY(hipGetLastError());
-	return HP_OK;
-}
-// hp_state_restore, behind the state's copies
-int bed_restore(hp_domain* d)
-{
-	BedShapes& B = d->beds;
-	if (!B.saved_taken) return HP_OK;
-	if (B.saved_epoch != B.epoch) {                                           // (the probe recorder's rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: bed shapes were added or cleared after the state was saved: the bed is left as it is");
-		return HP_OK;
-	}
-	if (!B.shapes) return HP_OK;
-	d->facts.boundaries_or_bed_changed();
-	if (B.lists.count) {
-		with_real(d, [&](auto zero) { using T = decltype(zero);
-			hipLaunchKernelGGL((bed_scatter<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (T*)d->bed, B.lists.cells, B.lists.count, (const T*)B.saved);
-		});
-		HIP_TRY(hipGetLastError());
-	}
-	d->facts.bed_uploaded();
-	return HP_OK;
-}
-
-// ---- link groups (hp_links.hpp): what a checkpoint does for the links' records ----
-static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
-void links_destroy(hp_domain* d) { hipFree(d->links.records); hipFree(d->links.saved); }
-// hp_state_save, before it touches anything (peaks_save_reserve's rule)
-int links_save_reserve(hp_domain* d)
-{
-	LinkStore& L = d->links;
-	if (!L.links || L.saved) return HP_OK;
-	return alloc_or_fail((void**)&L.saved, (size_t)LINK_MAX * sizeof(hp_link_record_t), "hp_state_save: cannot allocate the copy of the links' records: ");
-}
-int links_save(hp_domain* d)
-{
-	LinkStore& L = d->links;
-	L.saved_taken = true;
-	L.saved_epoch = L.epoch;
-	if (L.links) HIP_TRY(hipMemcpyAsync(L.saved, L.records, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
-}
-int links_restore(hp_domain* d)
-{
-	LinkStore& L = d->links;
-	if (!L.saved_taken) return HP_OK;
-	if (L.saved_epoch != L.epoch) {                                           // (the probe recorder's rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: link groups were added or cleared after the state was saved: the links' records start from zero");
-		if (L.links) HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
-		return HP_OK;
-	}
-	if (L.links) HIP_TRY(hipMemcpyAsync(L.records, L.saved, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
 	return HP_OK;
 }
 
@@ -1220,7 +1011,7 @@ int hp_domain_create(const hp_domain_desc_t* desc, hp_domain_t** out)
 		delete d;
 		return fail(HP_ERR_INVALID, "strip does not fit the global grid");
 	}
-	const long g = (desc->scheme == HP_SCHEME_MUSCL_HANCOCK) ? 2 : 1;     // stencil reach = ghost rows per exchange
+	const long g = stencil_reach(*desc);                                  // = ghost rows per exchange
 	d->ghost_rows = desc->ghost_rows > 0 ? desc->ghost_rows : g;
 	if (d->ghost_rows != g && d->ghost_rows != 2 * g) {
 		delete d;
@@ -1309,7 +1100,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); bed_destroy(d); links_destroy(d);
+	observers_destroy(d); actors_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1337,10 +1128,7 @@ int hp_domain_upload(hp_domain_t* d, int which, const void* host, size_t bytes)
 		// both ping-pong buffers get the same host array (CSchemeGodunov.cpp:1064-1065)
 		HIP_TRY(hipMemcpyAsync(d->state[0], host, bytes, hipMemcpyHostToDevice, d->stream));
 		HIP_TRY(hipMemcpyAsync(d->state[1], host, bytes, hipMemcpyHostToDevice, d->stream));
-		d->tune_phase = 0;                                                // (a sample still in flight measured the state that has just been replaced)
-		d->facts.full_state_uploaded(d->ghost_rows);                      // (use_alt = 0: :1075)
-		HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
-		return HP_OK;
+		return state_replaced(d);
 	case HP_ARRAY_BED:
 		if (bytes != d->cells * d->esize) return fail(HP_ERR_INVALID, "bed size mismatch");
 		HIP_TRY(hipMemcpyAsync(d->bed, host, bytes, hipMemcpyHostToDevice, d->stream));
@@ -1376,9 +1164,8 @@ int hp_state_save(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_save between hp_step_begin and hp_step_end");
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
-	if ((rc = peaks_save_reserve(d)) != HP_OK) return rc;            // (first: a failure leaves the checkpoint before it untouched)
-	if ((rc = bed_save_reserve(d)) != HP_OK) return rc;
-	if ((rc = links_save_reserve(d)) != HP_OK) return rc;
+	if ((rc = observers_save_reserve(d)) != HP_OK) return rc;        // (first: a failure leaves the checkpoint before it untouched)
+	if ((rc = actors_save_reserve(d)) != HP_OK) return rc;
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1389,11 +1176,8 @@ int hp_state_save(hp_domain_t* d)
 	if ((rc = snapshot_take(d, d->saved_state, d->saved_scalars, d->facts->use_alt)) != HP_OK) return rc;
 	d->facts.checkpoint_taken();
 	d->saved_valid = true;
-	if ((rc = peaks_save(d)) != HP_OK) return rc;
-	log_save(d, PROBES);
-	log_save(d, ZONES);
-	if ((rc = bed_save(d)) != HP_OK) return rc;
-	return links_save(d);
+	if ((rc = observers_save(d)) != HP_OK) return rc;
+	return actors_save(d);
 }
 
 int hp_state_restore(hp_domain_t* d)
@@ -1425,189 +1209,8 @@ int hp_state_restore(hp_domain_t* d)
 	                                                                      // iterations bench.py's restore found one in flight nearly every time and the timed
 	                                                                      // region ran on a choice made for the pre-warmed flood)
 	d->fork_is_advance = false;
-	if ((rc = peaks_restore(d)) != HP_OK) return rc;
-	log_restore(d, PROBES);
-	log_restore(d, ZONES);
-	if ((rc = bed_restore(d)) != HP_OK) return rc;
-	return links_restore(d);
-}
-
-// ---- the moving bed (hp_bed.hpp) ----
-int hp_bed_shape_add(hp_domain_t* d, const hp_bed_shape_desc_t* desc)
-{
-	// argument checks first: none of them touches the device, and those that do not need the domain come before it
-	const std::string who = "hp_bed_shape_add";
-	if (!desc) return fail(HP_ERR_INVALID, who + ": desc == NULL");
-	if (desc->struct_size != sizeof(hp_bed_shape_desc_t)) return fail(HP_ERR_INVALID, "hp_bed_shape_desc_t size mismatch (ABI)");
-	if (!desc->cells || !desc->target || !desc->series) return fail(HP_ERR_INVALID, who + ": cells / target / series == NULL");
-	if (desc->series_entries < 1 || desc->series_entries > BED_MAX_SERIES) return fail(HP_ERR_INVALID, who + ": series_entries outside 1..4096");
-	if (desc->cell_count < 1 || desc->cell_count > BED_MAX_CELLS) return fail(HP_ERR_INVALID, who + ": cell_count outside 1..1048576");
-	const uint64_t n = desc->cell_count;
-	const unsigned m = desc->series_entries;
-	for (uint64_t k = 0; k < n; ++k)
-		if (!std::isfinite(desc->target[k]) || std::fabs(desc->target[k]) > BED_MAX_LEVEL)
-			return fail(HP_ERR_INVALID, who + ": target " + std::to_string(k) + " is not a finite elevation of at most 9999");
-	for (unsigned k = 0; k < m; ++k) {
-		const double t = desc->series[2 * k], f = desc->series[2 * k + 1];
-		if (!std::isfinite(t) || (k > 0 && !(t > desc->series[2 * k - 2])))
-			return fail(HP_ERR_INVALID, who + ": series entry " + std::to_string(k) + ": times must be finite and strictly increasing");
-		if (!(f >= 0.0 && f <= 1.0)) return fail(HP_ERR_INVALID, who + ": series entry " + std::to_string(k) + ": fraction outside [0, 1]");
-	}
-	std::vector<uint64_t> sorted(desc->cells, desc->cells + n);
-	std::sort(sorted.begin(), sorted.end());
-	{
-		const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
-		if (twice != sorted.end()) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(*twice) + " is listed twice");
-	}
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	BedShapes& B = d->beds;
-	const uint64_t cols = (uint64_t)d->desc.cols;
-	if (sorted.back() >= cols * (uint64_t)d->desc.global_rows) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(sorted.back()) + " lies outside the grid");
-	if (B.shapes >= BED_MAX_SHAPES) return fail(HP_ERR_INVALID, who + ": more than 64 shapes");
-	if (B.listed.size() + n > BED_MAX_CELLS) return fail(HP_ERR_INVALID, who + ": more than 1048576 cells over all shapes");
-	std::vector<uint64_t> listed(B.listed.size() + (size_t)n);
-	std::merge(B.listed.begin(), B.listed.end(), sorted.begin(), sorted.end(), listed.begin());
-	{
-		const auto twice = std::adjacent_find(listed.begin(), listed.end());
-		if (twice != listed.end()) return fail(HP_ERR_INVALID, who + ": cell " + std::to_string(*twice) + " is listed twice (another shape has it)");
-	}
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
-	// this strip's share: the cells whose row lies in its local array, ghost rows included
-	std::vector<uint64_t> cells(B.cells);
-	std::vector<double> target(B.target);
-	for (uint64_t k = 0; k < n; ++k) {
-		const uint64_t gy = desc->cells[k] / cols, x = desc->cells[k] - gy * cols;
-		if (gy < (uint64_t)d->desc.row_offset || gy >= (uint64_t)(d->desc.row_offset + d->desc.rows)) continue;
-		cells.push_back((gy - (uint64_t)d->desc.row_offset) * cols + x);
-		target.push_back(desc->target[k]);
-	}
-	const size_t n_old = B.cells.size(), n_all = cells.size(), pairs_old = B.series.size() / 2, pairs_all = pairs_old + m;
-	const unsigned shapes = B.shapes + 1;
-	// the new block first: if it cannot be had, the domain keeps the shapes it has
-	const BedLayout l = bed_layout(n_all, pairs_all, shapes, d->esize);
-	void* fresh = nullptr;
-	if ((rc = alloc_or_fail(&fresh, l.bytes, who + ": cannot allocate the lists: ")) != HP_OK) return rc;
-	BedBlock* info = B.info;
-	if (!info) {
-		if ((rc = alloc_or_fail((void**)&info, sizeof(BedBlock), who + ": cannot allocate the counters: ")) != HP_OK) { hipFree(fresh); return rc; }
-	}
-	std::vector<unsigned char> image(l.bytes, 0);
-	if (n_all) {
-		std::memcpy(image.data() + l.cells, cells.data(), n_all * 8);
-		std::memcpy(image.data() + l.target, target.data(), n_all * 8);
-		if (n_old) std::memcpy(image.data() + l.shape_of, B.shape_of.data(), n_old);
-		std::memset(image.data() + l.shape_of + n_old, (int)B.shapes, n_all - n_old);
-	}
-	if (pairs_old) std::memcpy(image.data() + l.series, B.series.data(), pairs_old * 16);
-	std::memcpy(image.data() + l.series + pairs_old * 16, desc->series, (size_t)m * 16);
-	std::memcpy(image.data() + l.series_off, B.series_off.data(), (size_t)shapes * 4);
-	const unsigned end = (unsigned)pairs_all;
-	std::memcpy(image.data() + l.series_off + (size_t)shapes * 4, &end, 4);
-	const BedLists L = bed_lists(fresh, l, n_all, shapes);
-	hipError_t e = hipMemcpyAsync(fresh, image.data(), l.bytes, hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess && !B.info) e = hipMemsetAsync(info, 0, sizeof(BedBlock), d->stream);
-	// the base of the shapes that are there moves over; the new shape's is the bed as it is now, gathered on the domain's stream
-	if (e == hipSuccess && n_old) e = hipMemcpyAsync((char*)fresh + l.base, B.lists.base, n_old * d->esize, hipMemcpyDeviceToDevice, d->stream);
-	if (e == hipSuccess && n_all > n_old) {
-		with_real(d, [&](auto zero) { using T = decltype(zero);
-			hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks(n_all - n_old)), dim3(256), 0, d->stream, (const T*)d->bed, L.cells, (unsigned long long)n_old,
-			                   (unsigned long long)(n_all - n_old), (T*)((char*)fresh + l.base));
-		});
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (queued applies still read the old block; the caller's arrays are free on return)
-	if (e != hipSuccess) {
-		(void)hipStreamSynchronize(d->stream);
-		hipFree(fresh);
-		if (!B.info) hipFree(info);
-		(void)hipGetLastError();
-		return fail(HP_ERR_HIP, who + ": writing the lists: " + hipGetErrorString(e));
-	}
-	hipFree(B.block);
-	B.block = fresh;
-	B.info = info;
-	B.lists = L;
-	B.shape_of.resize(n_all, (unsigned char)B.shapes);
-	B.shapes = shapes;
-	B.listed.swap(listed);
-	B.cells.swap(cells);
-	B.target.swap(target);
-	B.series.insert(B.series.end(), desc->series, desc->series + 2 * (size_t)m);
-	B.series_off.push_back(end);
-	++B.epoch;
-	return HP_OK;
-}
-
-int hp_bed_shapes_clear(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	BedShapes& B = d->beds;
-	if (!B.shapes) return HP_OK;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_shapes_clear between hp_step_begin and hp_step_end");
-	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (queued applies still use the lists)
-	bed_destroy(d);
-	BedShapes none;
-	none.epoch = B.epoch + 1;
-	none.saved_taken = B.saved_taken;
-	none.saved_epoch = B.saved_epoch;
-	B = none;
-	return HP_OK;
-}
-
-// By contract exactly the host round trip it replaces -- download state and bed, move the bed and shift the levels, hp_domain_upload
-// of the bed, hp_domain_upload of the state --: the kernel patches the buffer hp_domain_download(HP_ARRAY_STATE) reads, and what
-// follows it is what the two uploads do, in their order (hp_domain_upload above).
-int hp_bed_apply(hp_domain_t* d)
-{
-	int rc = check_domain(d);            // (resolves a pending speculative STRICT batch: an apply never patches a state that is re-run)
-	if (rc != HP_OK) return rc;
-	BedShapes& B = d->beds;
-	if (!B.shapes) return HP_OK;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_bed_apply between hp_step_begin and hp_step_end");
-	if (d->facts->ghost_valid != d->ghost_rows)
-		return fail(HP_ERR_STATE, "hp_bed_apply: the strip's ghost rows are not all valid (two reaches after an odd number of iterations): apply after an even batch");
-	const int cur = d->facts->use_alt;
-	const unsigned slot = (unsigned)(B.applies & 1u);
-	with_real(d, [&](auto zero) { using T = decltype(zero);
-		hipLaunchKernelGGL((bed_apply<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (State4<T>*)d->state[cur], (T*)d->bed,
-		                   (const Scalars<T>*)d->scalars, B.lists, B.info, slot);
-	});
-	HIP_TRY(hipGetLastError());
-	++B.applies;
-	d->facts.boundaries_or_bed_changed();
-	d->facts.buffers_written_outside();
-	d->facts.bed_uploaded();
-	// both ping-pong buffers hold the patched state, as after hp_domain_upload(HP_ARRAY_STATE)
-	HIP_TRY(hipMemcpyAsync(d->state[cur ^ 1], d->state[cur], d->cells * 4 * d->esize, hipMemcpyDeviceToDevice, d->stream));
-	d->tune_phase = 0;
-	d->facts.full_state_uploaded(d->ghost_rows);
-	HIP_TRY(hipMemsetAsync((char*)d->cfl_slot + (size_t)SLOT_BDY * d->esize, 0, d->esize, d->stream));
-	return HP_OK;
-}
-
-int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out)
-{
-	if (!out) return fail(HP_ERR_INVALID, "hp_bed_info: out == NULL");
-	if (out->struct_size != sizeof(hp_bed_info_t)) return fail(HP_ERR_INVALID, "hp_bed_info_t size mismatch (ABI)");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	const BedShapes& B = d->beds;
-	out->shapes = B.shapes;
-	out->cells_local = B.lists.count;
-	out->applies = B.applies;
-	out->changed_last = out->changed_total = 0;
-	out->t_last = 0.0;
-	if (!B.shapes) return HP_OK;
-	BedBlock host;
-	HIP_TRY(hipMemcpyAsync(&host, B.info, sizeof host, hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	if (B.applies) out->changed_last = host.changed[(B.applies - 1) & 1u];
-	out->changed_total = host.changed_total;
-	out->t_last = host.t_last;
-	return HP_OK;
+	if ((rc = observers_restore(d)) != HP_OK) return rc;
+	return actors_restore(d);
 }
 
 int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int64_t nrows)
@@ -1644,185 +1247,6 @@ int hp_domain_upload_rows(hp_domain_t* d, const void* host, int64_t row0, int64_
 	HIP_TRY(hipMemcpyAsync((char*)d->state[d->facts->use_alt] + (size_t)row0 * per_row, host, (size_t)nrows * per_row,
 	                       hipMemcpyHostToDevice, d->stream));
 	d->facts.rows_uploaded();
-	return HP_OK;
-}
-
-int hp_boundary_add_uniform(hp_domain_t* d, int definition, const void* series, uint32_t entries,
-                            double interval, double length)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	d->facts.boundaries_or_bed_changed();
-	if (!series || entries == 0 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad uniform boundary");
-	if (definition != HP_UNIFORM_RAIN_INTENSITY && definition != HP_UNIFORM_LOSS_RATE)
-		return fail(HP_ERR_INVALID, "unknown uniform boundary definition");
-	Boundary b{};
-	b.kind = 0; b.definition = definition; b.entries = entries; b.interval = interval; b.length = length;
-	const size_t bytes = (size_t)entries * 2 * d->esize;
-	HIP_TRY(hipMalloc(&b.data, bytes));
-	HIP_TRY(hipMemcpy(b.data, series, bytes, hipMemcpyHostToDevice));
-	d->bdy.push_back(b);
-	return refresh_fusable(d);
-}
-
-int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, uint64_t entries,
-                            uint64_t grid_rows, uint64_t grid_cols, double resolution,
-                            double offset_x, double offset_y, double interval)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	d->facts.boundaries_or_bed_changed();
-	if (!grids || entries == 0 || grid_rows == 0 || grid_cols == 0 || !(resolution > 0) || !(interval > 0))
-		return fail(HP_ERR_INVALID, "bad gridded boundary");
-	{
-		// bdy_Gridded indexes floor((x dx - off) / res) without a range check (CLBoundaries.clc:231-236): a grid that
-		// does not cover the interior cells reads outside the buffer.  Rejected here instead.
-		const double dx = d->desc.dx;
-		const double x_lo = 1.0 * dx - offset_x, x_hi = (double)(d->desc.cols - 2) * dx - offset_x;
-		const double y_lo = 1.0 * dx - offset_y, y_hi = (double)(d->desc.global_rows - 2) * dx - offset_y;
-		if (x_lo < 0.0 || y_lo < 0.0 || std::floor(x_hi / resolution) >= (double)grid_cols ||
-		    std::floor(y_hi / resolution) >= (double)grid_rows)
-			return fail(HP_ERR_INVALID, "gridded boundary does not cover the domain's interior cells");
-	}
-	Boundary b{};
-	b.kind = 1; b.definition = definition; b.entries = entries; b.grows = grid_rows; b.gcols = grid_cols;
-	b.resolution = resolution; b.off_x = offset_x; b.off_y = offset_y; b.interval = interval;
-	const size_t bytes = (size_t)entries * grid_rows * grid_cols * d->esize;
-	HIP_TRY(hipMalloc(&b.data, bytes));
-	HIP_TRY(hipMemcpy(b.data, grids, bytes, hipMemcpyHostToDevice));
-	d->bdy.push_back(b);
-	return refresh_fusable(d);
-}
-
-int hp_boundary_add_cell(hp_domain_t* d, int depth_definition, int discharge_definition, const uint64_t* cells,
-                         uint64_t count, const void* series, uint64_t entries, double interval, double length)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	d->facts.boundaries_or_bed_changed();
-	if (!cells || count == 0 || !series || entries < 2 || !(interval > 0)) return fail(HP_ERR_INVALID, "bad cell boundary");
-	if (depth_definition < 0 || depth_definition > 3 || discharge_definition < 0 || discharge_definition > 3)
-		return fail(HP_ERR_INVALID, "unknown cell boundary definition");
-	const uint64_t global_cells = (uint64_t)d->desc.cols * (uint64_t)d->desc.global_rows;
-	bool on_ring = false;
-	{
-		const uint64_t w = (d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK) ? 2 : 1, cols = (uint64_t)d->desc.cols,
-		               grows = (uint64_t)d->desc.global_rows;
-		for (uint64_t i = 0; i < count; ++i) {
-			if (cells[i] >= global_cells) return fail(HP_ERR_INVALID, "cell boundary id outside the grid");
-			const uint64_t gy = cells[i] / cols, x = cells[i] - gy * cols;
-			on_ring = on_ring || x < w || x + w >= cols || gy < w || gy + w >= grows;
-		}
-	}
-	if (length > (double)(entries - 1) * interval + 1e-9)
-		return fail(HP_ERR_INVALID, "cell boundary series shorter than its length (interpolation reads entry n+1)");
-	Boundary b{};
-	b.kind = 2; b.definition = depth_definition; b.discharge_def = discharge_definition; b.count = count;
-	b.entries = entries; b.interval = interval; b.length = length;
-	HIP_TRY(hipMalloc(&b.cells, count * sizeof(uint64_t)));
-	HIP_TRY(hipMemcpy(b.cells, cells, count * sizeof(uint64_t), hipMemcpyHostToDevice));
-	const size_t bytes = (size_t)entries * 4 * d->esize;
-	HIP_TRY(hipMalloc(&b.data, bytes));
-	HIP_TRY(hipMemcpy(b.data, series, bytes, hipMemcpyHostToDevice));
-	d->bdy.push_back(b);
-	d->bdy_on_ring = d->bdy_on_ring || on_ring;
-	return refresh_fusable(d);
-}
-
-int hp_boundary_clear(hp_domain_t* d)
-{
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	d->facts.boundaries_or_bed_changed();
-	HIP_TRY(hipStreamSynchronize(d->stream));
-	for (auto& b : d->bdy) { hipFree(b.data); hipFree(b.cells); }
-	d->bdy.clear();
-	d->bdy_on_ring = false;
-	if (d->links.groups) {                                                    // the link groups go with the list, and their records with them
-		LinkStore& L = d->links;
-		HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
-		L.links = 0;
-		L.groups = 0;
-		L.taken.clear();
-		++L.epoch;
-	}
-	return refresh_fusable(d);
-}
-
-int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count)
-{
-	// argument checks first: none of them touches the device (hp_links.hpp: validate_links)
-	const std::string who = "hp_boundary_add_links";
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	LinkStore& L = d->links;
-	const uint64_t cols = (uint64_t)d->desc.cols, reach = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK ? 2 : 1;
-	std::vector<uint64_t> taken;
-	std::string why;
-	if (!validate_links(links, count, L.links, cols, (uint64_t)d->desc.global_rows, reach, L.taken, taken, why)) return fail(HP_ERR_INVALID, why);
-	// this strip's share: both ends of a link, or neither (links_strip_verdict)
-	const int64_t lo = d->desc.row_offset, hi = d->desc.row_offset + d->desc.rows;
-	const int64_t stale = d->ghost_rows > (int64_t)reach ? d->ghost_rows - (int64_t)reach : 0;      // (two reaches stored: the outer one)
-	const int64_t stale_lo = lo > 0 ? stale : 0, stale_hi = hi < d->desc.global_rows ? stale : 0;
-	std::vector<LinkDev> dev((size_t)count);
-	for (uint64_t k = 0; k < count; ++k) {
-		const hp_link_t& l = links[k];
-		const int64_t ya = (int64_t)(l.cell_a / cols), yb = (int64_t)(l.cell_b / cols);
-		const int verdict = links_strip_verdict(ya, yb, lo, hi, stale_lo, stale_hi);
-		if (verdict == LINK_ONE)
-			return fail(HP_ERR_UNSUPPORTED, who + ": link " + std::to_string(k) + " (cells " + std::to_string(l.cell_a) + " and " + std::to_string(l.cell_b) +
-			            "): this strip stores rows " + std::to_string(lo) + " to " + std::to_string(hi - 1) + " and would hold exactly one of its ends on every iteration");
-		LinkDev& o = dev[(size_t)k];
-		o.a = verdict == LINK_BOTH ? l.cell_a - (uint64_t)lo * cols : LINK_ABSENT;
-		o.b = verdict == LINK_BOTH ? l.cell_b - (uint64_t)lo * cols : LINK_ABSENT;
-		o.kind = l.kind; o.one_way = l.one_way; o.level = l.level; o.size = l.size; o.coeff = l.coeff; o.limit = l.limit;
-	}
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
-	if (!L.records) {
-		if ((rc = alloc_or_fail((void**)&L.records, (size_t)LINK_MAX * sizeof(hp_link_record_t), who + ": cannot allocate the records: ")) != HP_OK) return rc;
-		HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)LINK_MAX * sizeof(hp_link_record_t), d->stream));
-	}
-	Boundary b{};
-	b.kind = 3; b.count = count; b.entries = L.links;
-	if ((rc = alloc_or_fail(&b.cells, (size_t)count * sizeof(LinkDev), who + ": cannot allocate the links: ")) != HP_OK) return rc;
-	hipError_t e = hipMemcpyAsync(b.cells, dev.data(), (size_t)count * sizeof(LinkDev), hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (`dev` goes with this call)
-	if (e != hipSuccess) { hipFree(b.cells); return fail(HP_ERR_HIP, who + ": writing the links: " + hipGetErrorString(e)); }
-	d->facts.boundaries_or_bed_changed();
-	d->bdy.push_back(b);
-	L.links += count;
-	L.groups += 1;
-	L.taken.swap(taken);
-	++L.epoch;
-	return refresh_fusable(d);
-}
-
-int hp_links_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_link_record_t* out)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (first > d->links.links || count > d->links.links - first) return fail(HP_ERR_INVALID, "hp_links_read: first + count beyond the domain's links");
-	if (count == 0) return HP_OK;
-	if (!out) return fail(HP_ERR_INVALID, "hp_links_read: out == NULL");
-	int rc = check_domain(d);
-	if (rc != HP_OK) return rc;
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_links_read between hp_step_begin and hp_step_end");
-	HIP_TRY(hipMemcpyAsync(out, d->links.records + first, (size_t)count * sizeof(hp_link_record_t), hipMemcpyDeviceToHost, d->stream));
-	return HP_OK;
-}
-
-int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups)
-{
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (links) *links = d->links.links;
-	if (groups) *groups = d->links.groups;
-	return HP_OK;
-}
-
-int hp_boundaries_fused(hp_domain_t* d, int* fused)
-{
-	if (!d || !fused) return fail(HP_ERR_INVALID, "null argument");
-	*fused = d->fusable ? 1 : 0;
 	return HP_OK;
 }
 
@@ -1895,7 +1319,7 @@ int hp_step_begin(hp_domain_t* d)
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_step_begin called twice");
-	if (d->ghost_rows != strip_ghosts(d))
+	if (d->ghost_rows != stencil_reach(d->desc))
 		return fail(HP_ERR_UNSUPPORTED, "the split step exchanges after every iteration: it needs ghost_rows = the stencil reach "
 		                                "(two reaches of ghost rows are hp_strip_step_batch's)");
 	d->split_now = true;
@@ -2730,7 +2154,7 @@ int hp_strip_step_batch(hp_domain_t* d, uint32_t n_iterations)
 	if (!d->comm) return fail(HP_ERR_STATE, "hp_strip_step_batch without hp_strip_comm_init");
 	if (d->in_step) return fail(HP_ERR_STATE, "inside a split step");
 	if (n_iterations == 0) return HP_OK;
-	const long g = strip_ghosts(d);
+	const long g = stencil_reach(d->desc);
 	if ((rc = strip_handshake(d)) != HP_OK) return rc;
 	d->fork_is_advance = fork_ready && d->comm_world <= 1;            // (the handshake queued work behind the last advance_time)
 	// (a maximum that some rank has yet to price anew -- an upload since the last batch -- keeps the ranks on single iterations

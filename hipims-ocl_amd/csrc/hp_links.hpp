@@ -4,7 +4,8 @@
 // The arithmetic of one link and one iteration is ONE definition in plain C++ (link_flow, link_record below): the kernel uses
 // it, tests/links_probe.cpp includes this file with a host compiler, and frontend.Links restates it in NumPy.  All of it is fp64
 // and uses correctly rounded add, multiply, divide, square root and compare only; nothing is fused: hp_engine.hip's translation
-// unit is built with -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.  The contract is in include/hipims_mi.h.
+// unit is built with -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.  The contract is in include/hipims_mi.h;
+// the host side (hp_boundary_add_links, the pass that launches bdy_links, the records' part of a checkpoint) is in hp_actors.hpp.
 #pragma once
 #include "../../include/hipims_mi.h"
 #include <cstdint>

@@ -1,7 +1,7 @@
 // hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp, hp_overview.hpp, hp_sparse.hpp), the peak tracker
 // (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
-// (*_save, *_restore, *_destroy).  The two recorders share one record log (log_*): their own entry points keep the argument
+// (*_save, *_restore, *_destroy; observers_* calls them in order).  The two recorders share one record log (log_*): their own entry points keep the argument
 // checks, what they upload and the launch.  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, RecordLog, ProbeRecorder, ZoneRecorder).  Included
 // once by hp_engine.hip, after hp_domain.hpp: the library stays one translation unit.
 #pragma once
@@ -22,20 +22,6 @@ static_assert(sizeof(hp_zones_desc_t) == 32, "hp_zones_desc_t layout");
 static_assert(ZONE_WORDS == HP_ZONE_WORDS, "hp_zones.hpp and hipims_mi.h disagree");
 static_assert(AGG_MAX == HP_AGG_MAX && AGG_MIN == HP_AGG_MIN && AGG_COUNT == HP_AGG_COUNT && AGG_KINDS == HP_AGG_KINDS && OVERVIEW_PAIRS == 27, "hp_overview.hpp and hipims_mi.h disagree");
 
-// f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
-template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }
-
-// Device (or pinned host) memory, or the call fails with `what` + the runtime's reason.  The sticky last error is cleared: the
-// launches of later steps ask for it, and this one is dealt with here.
-int alloc_or_fail(void** p, const size_t bytes, const std::string& what, const bool pinned = false)
-{
-	const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-	if (e == hipSuccess) return HP_OK;
-	*p = nullptr;
-	(void)hipGetLastError();
-	return fail(HP_ERR_HIP, what + hipGetErrorString(e));
-}
-
 // The value list of hp_domain_derive / hp_peaks_read (`limit` values exist, spelt `limit_name`): none of these checks touches the
 // device or needs the domain.  `seen`: the mask of the values listed.
 int check_value_list(const std::string& who, const int* values, int count, int limit, const char* limit_name, int element_bytes, void* const* rasters, unsigned& seen)
@@ -52,9 +38,6 @@ int check_value_list(const std::string& who, const int* values, int count, int l
 	}
 	return HP_OK;
 }
-
-// a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
-inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
 
 // Cap of the raster scratch.  A request that needs more is worked through in blocks of rows; the kernel of a block runs in
 // well under a hundredth of the time its rasters take to cross the host link, so blocks are queued one after the other on the
@@ -319,6 +302,12 @@ int log_info(hp_domain* d, const Recorder& r, uint64_t* samples, uint64_t* capac
 	if (stride) *stride = r.log(d).stride;
 	return HP_OK;
 }
+
+// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the four ----
+int observers_save_reserve(hp_domain* d) { return peaks_save_reserve(d); }
+int observers_save(hp_domain* d) { const int rc = peaks_save(d); if (rc == HP_OK) { log_save(d, PROBES); log_save(d, ZONES); } return rc; }
+int observers_restore(hp_domain* d) { const int rc = peaks_restore(d); if (rc == HP_OK) { log_restore(d, PROBES); log_restore(d, ZONES); } return rc; }
+void observers_destroy(hp_domain* d) { out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); }
 
 } // namespace
 

@@ -227,8 +227,69 @@ def test_argument_errors_are_invalid_before_any_device_call():
     assert lib.hp_bed_info(None, C.byref(info)) == -1 and b"size mismatch" in lib.hp_last_error()
 
 
+def block_image(shapes, cols, row_lo, row_hi, esize):
+    """The device block of the shapes' lists, restated from the layout comment of csrc/hp_bed.hpp:
+    [cells: n x 8 | target: n x 8 | series: pairs x 16 | base: n elements, padded to 8 | series_off: (shapes + 1) x 4, padded to 8 |
+    shape_of: n, at least one byte].  `shapes`: (global ids, targets, series) each; the strip keeps the ids of its rows, as local ids.
+    Returns the seven figures of the layout, the bytes (base zero: the device fills it) and the regions' sizes before padding."""
+    cells, target, shape_of, series, series_off = [], [], [], [], [0]
+    for s, (ids, tg, sr) in enumerate(shapes):
+        for c, t in zip(ids, tg):
+            if row_lo <= c // cols < row_hi:
+                cells.append(c - row_lo * cols)
+                target.append(t)
+                shape_of.append(s)
+        series += [v for pair in sr for v in pair]
+        series_off.append(len(series) // 2)
+    n, pad8 = len(cells), lambda b: b + b"\0" * (-len(b) % 8)
+    regions = [np.array(cells, "<u8").tobytes(), np.array(target, "<f8").tobytes(), np.array(series, "<f8").tobytes(), bytes(n * esize),
+               np.array(series_off, "<u4").tobytes(), np.array(shape_of, "u1").tobytes() if n else b"\0"]
+    padded = regions[:3] + [pad8(regions[3]), pad8(regions[4]), regions[5]]
+    offsets = [sum(len(r) for r in padded[:k]) for k in range(7)]
+    return offsets, b"".join(padded), [len(r) for r in regions]
+
+
+@pytest.mark.parametrize("esize", [4, 8])
+def test_layout_and_image_of_the_device_block_equal_the_restatement(probe, esize):
+    """validate_bed_shape, bed_layout and bed_image through the probe: a first shape, a second on top of it, cell counts that are no
+    multiple of 8 (5 and 5 + 6: both paddings are met, base's with 4-byte elements, series_off's with two shapes), and strips that
+    hold none of a shape's cells."""
+    cols, grows = 10, 12
+    first = ([53, 54, 55, 64, 97], [0.5, -1.25, 3.0, 1.0 / 3.0, 9999.0], [(2.0, 0.0), (12.0, 1.0)])
+    second = ([61, 62, 63, 71, 72, 108], [0.1, 0.2, 0.3, 0.4, 0.5, 0.6], [(0.0, 0.0), (1.5, 0.75), (4.0, 0.25)])
+    flat = lambda s: f"{len(s[0])} {len(s[2])} " + " ".join(str(c) for c in s[0]) + " " + " ".join(bits(t) for t in s[1]) + " " + \
+        " ".join(bits(v) for pair in s[2] for v in pair)
+    strips = [(0, 12), (5, 8), (0, 3), (7, 9), (9, 12)]              # whole grid; part of both; none of either (n == 0); none of the first; one cell of each
+    cases = [(shapes, lo, hi) for lo, hi in strips for shapes in ([first], [first, second])]
+    got = probe([f"B {esize} {cols} {grows} {lo} {hi} {len(shapes)} " + " ".join(flat(s) for s in shapes) for shapes, lo, hi in cases])
+    images = {}
+    for (shapes, lo, hi), line in zip(cases, got):
+        *figures, image = line.split()
+        offsets, want, sizes = block_image(shapes, cols, lo, hi, esize)
+        assert [int(v) for v in figures] == offsets, (lo, hi, len(shapes))
+        assert bytes.fromhex(image) == want and len(want) == offsets[6], (lo, hi, len(shapes))
+        for k in range(6):                                                          # disjoint, in order, 8-aligned
+            assert offsets[k] % 8 == 0 and offsets[k] + sizes[k] <= offsets[k + 1] < offsets[k] + sizes[k] + 8
+        images[(len(shapes), lo, hi)] = (offsets, bytes.fromhex(image), sizes)
+    n_of = lambda key: images[key][2][0] // 8
+    assert n_of((1, 0, 12)) == 5 and n_of((2, 0, 12)) == 11 and n_of((2, 0, 3)) == 0 and n_of((1, 7, 9)) == 0 and n_of((2, 7, 9)) == 2
+    assert n_of((1, 9, 12)) == 1 and n_of((2, 9, 12)) == 2
+    assert images[(2, 0, 3)][0][6] == images[(2, 0, 3)][0][5] + 1                   # n == 0: one shape_of byte all the same
+    for lo, hi in strips:                                                           # the first shape's entries, carried over unchanged
+        (o1, b1, s1), (o2, b2, _) = images[(1, lo, hi)], images[(2, lo, hi)]
+        for k, size in ((0, s1[0]), (1, s1[1]), (2, s1[2]), (4, s1[4]), (5, s1[0] // 8)):
+            assert b2[o2[k]:o2[k] + size] == b1[o1[k]:o1[k] + size], (lo, hi, k)
+        assert b2[o2[4] + 8:o2[4] + 12] == struct.pack("<I", 5)                     # ... and the second's series behind the first's
+    # the checks in front of it, in the entry point's order: a cell of the new shape that an earlier one has
+    again = ([10, 97], [0.0, 0.0], [(0.0, 1.0)])
+    beyond = ([cols * grows], [0.0], [(0.0, 1.0)])
+    refused = probe([f"B {esize} {cols} {grows} 0 12 2 {flat(first)} {flat(again)}", f"B {esize} {cols} {grows} 0 12 1 {flat(beyond)}"])
+    assert refused[0] == "! hp_bed_shape_add: cell 97 is listed twice (another shape has it)"
+    assert refused[1] == "! hp_bed_shape_add: cell 120 lies outside the grid"
+
+
 # 4 ---------------------------------------------------------------------------------------------------------------------
-XML = """<?xml version="1.0"?>
+XML ="""<?xml version="1.0"?>
 <configuration>
   <metadata><name>reservoir behind a wall</name></metadata>
   <simulation>
