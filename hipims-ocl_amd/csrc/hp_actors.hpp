@@ -7,6 +7,7 @@
 // stays one translation unit.
 #pragma once
 #include "hp_domain.hpp"
+#include "hp_gridded.hpp"
 #include <cmath>
 #include <cstdlib>
 
@@ -395,13 +396,13 @@ int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, u
 		return fail(HP_ERR_INVALID, "bad gridded boundary");
 	{
 		// bdy_Gridded indexes floor((x dx - off) / res) without a range check (CLBoundaries.clc:231-236): a grid that
-		// does not cover the interior cells reads outside the buffer.  Rejected here instead.
-		const double dx = d->desc.dx;
-		const double x_lo = 1.0 * dx - offset_x, x_hi = (double)(d->desc.cols - 2) * dx - offset_x;
-		const double y_lo = 1.0 * dx - offset_y, y_hi = (double)(d->desc.global_rows - 2) * dx - offset_y;
-		if (x_lo < 0.0 || y_lo < 0.0 || std::floor(x_hi / resolution) >= (double)grid_cols ||
-		    std::floor(y_hi / resolution) >= (double)grid_rows)
-			return fail(HP_ERR_INVALID, "gridded boundary does not cover the domain's interior cells");
+		// does not cover the interior cells reads outside the buffer.  Rejected here instead, by the kernels' own
+		// expression in the domain's precision (hp_gridded.hpp).
+		const hp_domain_desc_t& k = d->desc;
+		const bool covers = k.precision == 8
+			? hp::gridded_covers<double>(k.dx, resolution, offset_x, offset_y, (long)k.cols, (long)k.global_rows, grid_cols, grid_rows)
+			: hp::gridded_covers<float>(k.dx, resolution, offset_x, offset_y, (long)k.cols, (long)k.global_rows, grid_cols, grid_rows);
+		if (!covers) return fail(HP_ERR_INVALID, "gridded boundary does not cover the domain's interior cells");
 	}
 	Boundary b{};
 	b.kind = BDY_GRIDDED; b.definition = definition; b.entries = entries; b.grows = grid_rows; b.gcols = grid_cols;

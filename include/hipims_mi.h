@@ -521,7 +521,13 @@ enum { HP_GRIDDED_RAIN_INTENSITY = 0, HP_GRIDDED_RAIN_ACCUMUL = 1, HP_GRIDDED_MA
 /* series: `entries` x {time, value} pairs (value in mm/h), element type = domain precision */
 int hp_boundary_add_uniform(hp_domain_t* d, int definition, const void* series, uint32_t entries,
                             double interval, double length);
-/* grids: [entries][grid_rows][grid_cols] rates (mm/h), element type = domain precision */
+/* grids: [entries][grid_rows][grid_cols] rates (mm/h), element type = domain precision.  A cell (x, gy) reads column
+ * floor((x dx - offset_x) / resolution) and row floor((gy dx - offset_y) / resolution) of the grid, evaluated in the domain's
+ * precision.  A grid that does not cover every interior cell (0 <= column < grid_cols, 0 <= row < grid_rows at columns
+ * 1 .. cols - 2 and global rows 1 .. global_rows - 2) is HP_ERR_INVALID, "gridded boundary does not cover the domain's
+ * interior cells": the cover check is made in the domain's precision, with the kernels' own expression, so an fp32 domain
+ * can refuse a grid that an fp64 domain of the same shape takes (the float quotient can reach grid_cols where the double
+ * one stays just below).  The offsets are therefore at most dx. */
 int hp_boundary_add_gridded(hp_domain_t* d, int definition, const void* grids, uint64_t entries,
                             uint64_t grid_rows, uint64_t grid_cols, double resolution,
                             double offset_x, double offset_y, double interval);

@@ -273,6 +273,10 @@ class OracleSim(_SimBase):
     def force_dt(self, dt):
         self.lib.orc_sim_force_dt(self.h, self.creal(dt))
 
+    def set_time(self, t):
+        """The engine's hp_set_time: the clock alone (the timestep and the hydrological time stay)."""
+        self.lib.orc_sim_set_time(self.h, self.creal(t))
+
     def reset_counters(self):
         self.lib.orc_sim_reset_counters(self.h)
 

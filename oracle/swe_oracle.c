@@ -1070,6 +1070,7 @@ int orc_sim_add_cell(orc_sim* s, int depth_def, int discharge_def, const unsigne
 
 void orc_sim_set_target(orc_sim* s, real t_sync) { s->sc.t_sync = t_sync; }       /* CSchemeGodunov.cpp:1166-1176 */
 void orc_sim_force_dt(orc_sim* s, real dt)       { s->sc.dt = dt; }               /* :1213-1232 */
+void orc_sim_set_time(orc_sim* s, real t)        { s->sc.t = t; }                 /* rollbackSimulation rewrites the "Time" buffer, :1480-1494 */
 void orc_sim_reset_counters(orc_sim* s)                                           /* tst_ResetCounters, CLDynamicTimestep.clc:151-161 */
 { s->sc.batch_dt = RC(0.0); s->sc.batch_ok = 0; s->sc.batch_skipped = 0; }
 

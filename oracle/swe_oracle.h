@@ -135,6 +135,7 @@ int      orc_sim_add_cell(orc_sim* s, int depth_def, int discharge_def, const un
                           unsigned long count, const real* series, unsigned long entries, real interval, real length);
 void     orc_sim_set_target(orc_sim* s, real t_sync);
 void     orc_sim_force_dt(orc_sim* s, real dt);
+void     orc_sim_set_time(orc_sim* s, real t);
 void     orc_sim_reset_counters(orc_sim* s);
 /* tst_Reduce (primary buffer) + tst_UpdateTimestep, as Threaded_runBatch queues them after a new target time
  * (CSchemeGodunov.cpp:1189-1195) */
