@@ -1,9 +1,10 @@
 // hp_actors.hpp -- the actors of a domain, host side: what changes the state from outside the flux kernels.  Three kinds: the
-// boundaries (uniform, gridded and cell: hp_kernels.hpp), the link groups among them (hp_links.hpp) and the bed shapes (hp_bed.hpp).
+// boundaries (uniform, gridded and cell: hp_kernels.hpp), the link groups (hp_links.hpp) and the infiltration (hp_soil.hpp) among them,
+// and the bed shapes (hp_bed.hpp).
 // Here: their entry points of include/hipims_mi.h, the boundary pass the engine queues in front of an iteration (apply_boundaries)
 // and the choice of what the flux kernel carries of it instead (refresh_fusable), and what hp_state_save / hp_state_restore /
-// hp_domain_destroy do for the bed and the links (*_save, *_restore, *_destroy; actors_* calls them in order).  Their state is
-// declared in hp_domain.hpp (Boundary, BedShapes, LinkStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
+// hp_domain_destroy do for the bed, the links and the infiltration (*_save, *_restore, *_destroy; actors_* calls them in order).  Their
+// state is declared in hp_domain.hpp (Boundary, BedShapes, LinkStore, SoilStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
 // stays one translation unit.
 #pragma once
 #include "hp_domain.hpp"
@@ -15,6 +16,7 @@ namespace {
 
 static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, "hp_bed_*_t layout");
 static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
+static_assert(sizeof(hp_soil_class_t) == 32 && sizeof(hp_infiltration_desc_t) == 32, "hp_soil_class_t / hp_infiltration_desc_t layout");
 
 // ---- the boundaries ----
 // an area boundary as the kernels read it: the stand-alone pass and the fused one are handed the same descriptor
@@ -53,6 +55,12 @@ template <typename T> int apply_boundaries(hp_domain* d, void* target)
 			flush();
 			hipLaunchKernelGGL(bdy_links<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
 			                   (const LinkDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->links.records + b.entries);
+			continue;
+		}
+		if (b.kind == BDY_INFILTRATION) {
+			flush();
+			hipLaunchKernelGGL(bdy_infiltration<T>, soil_grid(p.cols, p.rows), dim3(SOIL_BLOCK), 0, d->stream, p, (const Scalars<T>*)d->scalars,
+			                   (const SoilTable*)d->soil.table, (const unsigned char*)d->soil.ids, d->soil.F, (State4<T>*)target, (const T*)d->bed);
 			continue;
 		}
 		if (b.kind == BDY_CELL) {
@@ -217,11 +225,72 @@ int links_restore(hp_domain* d)
 	return HP_OK;
 }
 
-// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the two ----
-int actors_save_reserve(hp_domain* d) { const int rc = bed_save_reserve(d); return rc != HP_OK ? rc : links_save_reserve(d); }
-int actors_save(hp_domain* d) { const int rc = bed_save(d); return rc != HP_OK ? rc : links_save(d); }
-int actors_restore(hp_domain* d) { const int rc = bed_restore(d); return rc != HP_OK ? rc : links_restore(d); }
-void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); }
+// ---- the infiltration (hp_soil.hpp): what a checkpoint and hp_boundary_clear do for F ----
+void soil_destroy(hp_domain* d)
+{
+	SoilStore& S = d->soil;
+	hipFree(S.ids); hipFree(S.F); hipFree(S.table); hipFree(S.saved);
+	S.ids = nullptr; S.F = nullptr; S.table = nullptr; S.saved = nullptr;
+}
+// hp_boundary_clear (the stream is idle): the infiltration goes with the list, and F with it
+int soil_clear(hp_domain* d)
+{
+	SoilStore& S = d->soil;
+	if (!S.on) return HP_OK;
+	soil_destroy(d);
+	S.on = false;
+	S.classes = 0;
+	S.pervious = 0;
+	++S.epoch;
+	return HP_OK;
+}
+// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+int soil_save_reserve(hp_domain* d)
+{
+	SoilStore& S = d->soil;
+	if (!S.on || S.saved) return HP_OK;
+	return alloc_or_fail((void**)&S.saved, d->cells * sizeof(double), "hp_state_save: cannot allocate the copy of the cumulative infiltration: ");
+}
+int soil_save(hp_domain* d)
+{
+	SoilStore& S = d->soil;
+	S.saved_taken = true;
+	S.saved_epoch = S.epoch;
+	if (S.on) HIP_TRY(hipMemcpyAsync(S.saved, S.F, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+int soil_restore(hp_domain* d)
+{
+	SoilStore& S = d->soil;
+	if (!S.saved_taken) return HP_OK;
+	if (S.saved_epoch != S.epoch) {                                           // (the bed shapes' rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: the infiltration was added or cleared after the state was saved: the cumulative infiltration is left as it is");
+		return HP_OK;
+	}
+	if (S.on) HIP_TRY(hipMemcpyAsync(S.F, S.saved, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+
+// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the three ----
+int actors_save_reserve(hp_domain* d)
+{
+	int rc = bed_save_reserve(d);
+	if (rc == HP_OK) rc = links_save_reserve(d);
+	return rc != HP_OK ? rc : soil_save_reserve(d);
+}
+int actors_save(hp_domain* d)
+{
+	int rc = bed_save(d);
+	if (rc == HP_OK) rc = links_save(d);
+	return rc != HP_OK ? rc : soil_save(d);
+}
+int actors_restore(hp_domain* d)
+{
+	int rc = bed_restore(d);
+	if (rc == HP_OK) rc = links_restore(d);
+	return rc != HP_OK ? rc : soil_restore(d);
+}
+void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); }
 
 } // namespace
 
@@ -453,6 +522,7 @@ int hp_boundary_clear(hp_domain_t* d)
 	d->bdy.clear();
 	d->bdy_on_ring = false;
 	if ((rc = links_clear(d)) != HP_OK) return rc;
+	if ((rc = soil_clear(d)) != HP_OK) return rc;
 	return refresh_fusable(d);
 }
 
@@ -524,6 +594,79 @@ int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups)
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	if (links) *links = d->links.links;
 	if (groups) *groups = d->links.groups;
+	return HP_OK;
+}
+
+// ---- the infiltration (hp_soil.hpp) ----
+int hp_boundary_add_infiltration(hp_domain_t* d, const hp_infiltration_desc_t* desc)
+{
+	// argument checks first: none of them touches the device (hp_soil.hpp: validate_infiltration)
+	const std::string who = "hp_boundary_add_infiltration";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	uint64_t pervious = 0;
+	std::string why;
+	if (!validate_infiltration(desc, (uint64_t)d->cells, pervious, why)) return fail(HP_ERR_INVALID, why);
+	// a strip with two reaches of ghost rows holds the outer one on every second iteration only: F there would drift from its owner's
+	if (d->ghost_rows > stencil_reach(d->desc) && (d->desc.row_offset > 0 || d->desc.row_offset + d->desc.rows < d->desc.global_rows))
+		return fail(HP_ERR_UNSUPPORTED, who + ": this strip stores two reaches of ghost rows, the outer one valid on every second iteration only: "
+		            "the cumulative infiltration there would drift from its owner's (exchange after every iteration instead)");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	SoilStore& S = d->soil;
+	if (S.on) return fail(HP_ERR_STATE, who + ": the domain has an infiltration already (hp_boundary_clear removes it)");
+	// everything it needs first: if any of it cannot be had, the domain stays as it is
+	SoilTable host;
+	soil_table(desc, host);
+	unsigned char* ids = nullptr;
+	double* F = nullptr;
+	SoilTable* table = nullptr;
+	if ((rc = alloc_or_fail((void**)&ids, d->cells, who + ": cannot allocate the class ids: ")) != HP_OK) return rc;
+	if ((rc = alloc_or_fail((void**)&F, d->cells * sizeof(double), who + ": cannot allocate the cumulative infiltration: ")) != HP_OK) { hipFree(ids); return rc; }
+	if ((rc = alloc_or_fail((void**)&table, sizeof(SoilTable), who + ": cannot allocate the class table: ")) != HP_OK) { hipFree(ids); hipFree(F); return rc; }
+	hipError_t e = hipMemcpyAsync(ids, desc->soil_of_cell, d->cells, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(table, &host, sizeof host, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = desc->initial ? hipMemcpyAsync(F, desc->initial, d->cells * sizeof(double), hipMemcpyHostToDevice, d->stream)
+	                                        : hipMemsetAsync(F, 0, d->cells * sizeof(double), d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (`host` goes with this call; the caller's arrays are free on return)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(ids); hipFree(F); hipFree(table);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the rasters: " + hipGetErrorString(e));
+	}
+	Boundary b{};
+	b.kind = BDY_INFILTRATION;
+	d->facts.boundaries_or_bed_changed();
+	d->bdy.push_back(b);
+	S.on = true;
+	S.ids = ids; S.F = F; S.table = table;
+	S.classes = desc->class_count;
+	S.pervious = pervious;
+	++S.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_infiltration_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!raster) return fail(HP_ERR_INVALID, "hp_infiltration_read: raster == NULL");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	if (!d->soil.on) return fail(HP_ERR_STATE, "hp_infiltration_read: the domain has no infiltration");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_infiltration_read between hp_step_begin and hp_step_end");
+	if (nrows == 0) return HP_OK;
+	const size_t cols = (size_t)d->desc.cols;
+	HIP_TRY(hipMemcpyAsync(raster, d->soil.F + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_infiltration_info(hp_domain_t* d, uint32_t* classes, uint64_t* pervious_cells)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (classes) *classes = d->soil.classes;
+	if (pervious_cells) *pervious_cells = d->soil.pervious;
 	return HP_OK;
 }
 

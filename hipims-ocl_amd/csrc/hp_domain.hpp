@@ -2,7 +2,7 @@
 // the map of its pinned host block and the helpers more than one part uses (with_real, alloc_or_fail, upload_or_fail, stream_blocks,
 // stencil_reach, state_replaced).  Internal to the library's one translation unit: hp_engine.hip includes it, then hp_observers.hpp
 // (the code of the four observers whose state is declared here, and of the RecordLog two of them share) and hp_actors.hpp (the code
-// of the boundaries, the link groups among them, and the moving bed: Boundary, LinkStore and BedShapes below).
+// of the boundaries, the link groups and the infiltration among them, and the moving bed: Boundary, LinkStore, SoilStore and BedShapes below).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_facts.hpp"
@@ -14,6 +14,7 @@
 #include "hp_sparse.hpp"
 #include "hp_bed.hpp"
 #include "hp_links.hpp"
+#include "hp_soil.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <algorithm>
@@ -82,7 +83,8 @@ inline long stencil_reach(const hp_domain_desc_t& desc) { return desc.scheme == 
 
 // ---- the actors' state (their code: hp_actors.hpp) ----
 // a boundary, in the order added.  The first two are the AREA boundaries (AreaBdy, hp_kernels.hpp): consecutive ones share a launch
-enum BoundaryKind { BDY_UNIFORM, BDY_GRIDDED, BDY_CELL, BDY_LINKS };          // BDY_LINKS: cells is its LinkDev array, entries its first record
+enum BoundaryKind { BDY_UNIFORM, BDY_GRIDDED, BDY_CELL, BDY_LINKS,           // BDY_LINKS: cells is its LinkDev array, entries its first record
+                    BDY_INFILTRATION };                                       // BDY_INFILTRATION: everything of it is the domain's SoilStore
 struct Boundary {
 	BoundaryKind kind;
 	int      definition;
@@ -170,6 +172,21 @@ struct LinkStore {
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's records belong to one epoch
 	hp_link_record_t* saved = nullptr;                // hp_state_save's copy (LINK_MAX records)
 	bool             saved_taken = false;             // a checkpoint exists (with or without links) ...
+	uint64_t         saved_epoch = 0;                 // ... of this epoch
+};
+
+// the infiltration (hp_soil.hpp; hp_boundary_add_infiltration): the boundary itself is a Boundary entry of kind BDY_INFILTRATION, at
+// most one a domain; this is its state.  Nothing of it exists while the domain has none
+struct SoilStore {
+	bool             on = false;
+	unsigned char*   ids = nullptr;                   // device: the class id of every cell of the local array
+	double*          F = nullptr;                     // device: cumulative infiltrated depth, fp64 whatever the domain's precision
+	SoilTable*       table = nullptr;                 // device: the classes, indexed by id
+	uint32_t         classes = 0;
+	uint64_t         pervious = 0;                    // cells of a class other than 0
+	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's F belongs to one epoch
+	double*          saved = nullptr;                 // hp_state_save's copy of F
+	bool             saved_taken = false;             // a checkpoint exists (with or without infiltration) ...
 	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
@@ -290,6 +307,7 @@ struct hp_domain {
 	ZoneRecorder     zones;
 	BedShapes        beds;
 	LinkStore        links;
+	SoilStore        soil;
 };
 
 namespace {

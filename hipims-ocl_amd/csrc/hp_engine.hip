@@ -1378,8 +1378,9 @@ bool spec_wanted(const hp_domain* d, uint32_t n)
 #else
 	const bool fusable_ok = !d->fusable;
 #endif
-	// Never with link groups: the batch that is queued again after a raised word would count their records twice.
-	return enabled && n >= SPEC_MIN && d->desc.math_mode == HP_MATH_STRICT && d->desc.precision == 8 && !d->comm && fusable_ok && !d->links.groups &&
+	// Never with link groups: the batch that is queued again after a raised word would count their records twice.  Nor with an
+	// infiltration: it would add to F twice.
+	return enabled && n >= SPEC_MIN && d->desc.math_mode == HP_MATH_STRICT && d->desc.precision == 8 && !d->comm && fusable_ok && !d->links.groups && !d->soil.on &&
 	       d->desc.kernel != HP_KERNEL_BASIC && (d->desc.scheme == HP_SCHEME_GODUNOV || d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK);
 }
 int spec_begin(hp_domain* d)

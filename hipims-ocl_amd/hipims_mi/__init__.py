@@ -50,7 +50,8 @@ EXPORTS = [
     "hp_probes_enable", "hp_probes_disable", "hp_probes_reset", "hp_probes_sample", "hp_probes_read", "hp_probes_info",
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
     "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
-    "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
+    "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info",
+    "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
     "hp_stream_halo", "hp_comm_load", "hp_comm_unique_id", "hp_strip_comm_init", "hp_strip_step_batch", "hp_strip_update_timestep",
@@ -173,6 +174,39 @@ def pack_links(links, cols):
     return out
 
 
+# hp_soil_class_t as a NumPy record, and hp_infiltration_desc_t
+SOIL_CLASS_DTYPE = np.dtype([("ks", np.float64), ("suction", np.float64), ("deficit", np.float64), ("capacity", np.float64)])
+
+
+class InfiltrationDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("class_count", C.c_uint32), ("classes", C.c_void_p), ("soil_of_cell", C.c_void_p),
+                ("initial", C.c_void_p)]
+
+
+def pack_soil_classes(classes):
+    """Soil classes as an array of SOIL_CLASS_DTYPE.  `classes`: such an array, or a sequence of dicts / tuples (ks, suction,
+    deficit, capacity); capacity defaults to +inf.  Class k of the id raster is entry k - 1."""
+    if isinstance(classes, np.ndarray) and classes.dtype == SOIL_CLASS_DTYPE:
+        return np.ascontiguousarray(classes).reshape(-1)
+    names = ("ks", "suction", "deficit", "capacity")
+    out = np.zeros(len(classes), SOIL_CLASS_DTYPE)
+    for k, c in enumerate(classes):
+        c = dict(c) if isinstance(c, dict) else dict(zip(names, c))
+        out[k] = (float(c["ks"]), float(c["suction"]), float(c["deficit"]), float(c.get("capacity", np.inf)))
+    return out
+
+
+def soil_ids(values, what="the soil raster"):
+    """A raster of soil class ids as uint8: every value an integer in 0..255 (0 = impervious), else ValueError."""
+    v = np.asarray(values)
+    if v.dtype.kind not in "iu":
+        if not np.isfinite(v).all() or (v != np.floor(v)).any():
+            raise ValueError(f"{what}: soil class ids must be integers")
+    if v.size and (v.min() < 0 or v.max() > 255):
+        raise ValueError(f"{what}: soil class ids must lie in 0..255")
+    return np.ascontiguousarray(v.astype(np.uint8))
+
+
 _lib = None
 
 
@@ -245,6 +279,10 @@ def load_library(path: str | None = None):
         lib.hp_boundary_add_links.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         lib.hp_links_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.hp_links_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_boundary_add_infiltration"):    # (absent from older builds, as above)
+        lib.hp_boundary_add_infiltration.argtypes = [C.c_void_p, C.POINTER(InfiltrationDesc)]
+        lib.hp_infiltration_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_infiltration_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -954,6 +992,38 @@ class Domain:
         count = self.links_info()["links"] - first if count is None else count
         out = np.zeros(count, LINK_RECORD_DTYPE)
         _check(self.lib, self.lib.hp_links_read(self.h, first, count, out.ctypes.data_as(C.c_void_p)), "hp_links_read")
+        self.sync()
+        return out
+
+    def add_infiltration(self, soil, classes, initial=None):
+        """The infiltration (hp_boundary_add_infiltration): Green-Ampt by soil class, applied per iteration at its place in the order
+        the boundaries were added.  `soil`: [rows, cols] class ids of the LOCAL array (row 0 = south; 0 = impervious), `classes`: see
+        pack_soil_classes (class k is entry k - 1), `initial`: [rows, cols] cumulative infiltration in m for a hot start, or None for
+        zeros.  frontend.Infiltration is the same arithmetic on the host, bit for bit."""
+        ids = soil_ids(soil)
+        if ids.shape != (self.rows, self.cols):
+            raise ValueError(f"the soil raster must be [{self.rows}, {self.cols}]")
+        cls = pack_soil_classes(classes)
+        f0 = None
+        if initial is not None:
+            f0 = np.ascontiguousarray(initial, dtype=np.float64)
+            if f0.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial infiltration must be [{self.rows}, {self.cols}]")
+        desc = InfiltrationDesc(C.sizeof(InfiltrationDesc), len(cls), cls.ctypes.data if len(cls) else None, ids.ctypes.data,
+                                None if f0 is None else f0.ctypes.data)
+        _check(self.lib, self.lib.hp_boundary_add_infiltration(self.h, C.byref(desc)), "hp_boundary_add_infiltration")
+
+    def infiltration_info(self):
+        """dict(classes, pervious_cells): host counters (both 0 without an infiltration)."""
+        n, c = C.c_uint32(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_infiltration_info(self.h, C.byref(n), C.byref(c)), "hp_infiltration_info")
+        return dict(classes=n.value, pervious_cells=c.value)
+
+    def infiltration_read(self, row0=0, nrows=None):
+        """The cumulative infiltrated depth F in m, fp64 [nrows, cols] (default: every row of the local array); blocks."""
+        nrows = self.rows - row0 if nrows is None else nrows
+        out = np.zeros((max(0, nrows), self.cols), np.float64)
+        _check(self.lib, self.lib.hp_infiltration_read(self.h, out.ctypes.data, row0, nrows), "hp_infiltration_read")
         self.sync()
         return out
 

@@ -120,6 +120,7 @@ class Configuration:
     sparse: dict = None                            # select, above, values, target pattern: the <sparseTarget> element (the last one wins)
     bed_shapes: list = field(default_factory=list)  # dict(name, cells [(x, y)], target [n], series [m, 2]): <bedShape> elements
     links: list = field(default_factory=list)      # dict(a (x, y), b (x, y), kind, one_way, level, size, coeff, limit): rows of the <links> elements' mapFiles
+    soil_classes: list = field(default_factory=list)  # dict(ks, suction, deficit, capacity): rows of the <soilClasses> element's source; the id raster is the "soil" data source
 
 
 def _params(elem):
@@ -182,6 +183,11 @@ def parse_configuration(xml_path):
         series = _read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2)
         cfg.bed_shapes.append(dict(name=e.get("name") or f"bedShape{k}", cells=[(int(r[0]), int(r[1])) for r in cells],
                                    target=cells[:, 2].copy(), series=series))
+    # the infiltration's classes (no reference counterpart): <soilClasses source="soil.csv"/>, rows ks, suction, deficit, capacity ("inf" is
+    # a number to float()); class k of the raster <dataSource type="raster" value="soil" source="..."/> is row k
+    for e in data.findall("soilClasses"):
+        cfg.soil_classes = [dict(ks=float(r[0]), suction=float(r[1]), deficit=float(r[2]), capacity=float(r[3]))
+                            for r in _read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 4)]
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -882,6 +888,124 @@ class Links:
         self.active = self.active + move.astype(np.uint64)
         self.applies += 1
         return int(move.sum())
+
+
+class Infiltration:
+    """The infiltration on the host (hp_boundary_add_infiltration restated in NumPy, in exactly the operation order of
+    csrc/hp_soil.hpp: soil_step): Green-Ampt by soil class.  `apply` acts in place on state[rows, cols, 4], the iteration's source
+    buffer, where the engine launches bdy_infiltration; the arrays' dtype decides the single rounding of a stored level.  All
+    arithmetic is fp64 -- separate, correctly rounded adds, multiplies and square roots -- so the state and F equal the device's bit
+    for bit.  The GPU tests' reference; it also counts which branch each cell took."""
+
+    BRANCHES = ("ring", "impervious", "not_counted", "dry", "potential", "depth_limited", "capacity_cap", "capacity_full")
+
+    def __init__(self, rows, cols, classes, soil, initial=None, row_offset=0, global_rows=None):
+        """`row_offset`, `global_rows`: where the rows of a strip's local array lie in the whole grid (default: the whole grid)."""
+        from . import pack_soil_classes, soil_ids
+        self.rows, self.cols = int(rows), int(cols)
+        # the grid's edge ring (csrc/hp_soil.hpp: soil_on_ring): the outermost cells of the GLOBAL grid are left alone
+        gy = np.arange(self.rows) + int(row_offset)
+        x = np.arange(self.cols)
+        top = (self.rows if global_rows is None else int(global_rows)) - 1
+        self.ring = ((gy <= 0) | (gy >= top))[:, None] | ((x <= 0) | (x >= self.cols - 1))[None, :]
+        self.classes = c = pack_soil_classes(classes)
+        n = len(c)
+        if not 1 <= n <= 255:
+            raise ValueError("class_count outside 1..255")
+        if not (np.isfinite(c["ks"]) & np.isfinite(c["suction"])).all() or (c["ks"] < 0).any() or (c["suction"] < 0).any():
+            raise ValueError("ks and suction must be finite and not negative")
+        with np.errstate(invalid="ignore", over="ignore"):
+            if not ((c["deficit"] >= 0) & (c["deficit"] <= 1)).all():
+                raise ValueError("the moisture deficit lies in [0, 1]")
+            if not (c["capacity"] >= 0).all():
+                raise ValueError("the capacity is >= 0 (+inf for none)")
+            if not np.isfinite(c["ks"] * 1e6).all() or not np.isfinite(c["suction"] * c["deficit"]).all():
+                raise ValueError("ks * 1e6 and suction * deficit must be finite")
+        self.soil = soil_ids(soil)
+        if self.soil.shape != (self.rows, self.cols):
+            raise ValueError(f"the soil raster must be [{self.rows}, {self.cols}]")
+        if int(self.soil.max(initial=0)) > n:
+            bad = int(np.flatnonzero(self.soil.reshape(-1) > n)[0])
+            raise ValueError(f"cell {bad} has a class id above class_count")
+        if initial is None:
+            self.F = np.zeros((self.rows, self.cols))
+        else:
+            self.F = np.array(initial, dtype=np.float64)
+            if self.F.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial infiltration must be [{self.rows}, {self.cols}]")
+            if not np.isfinite(self.F).all() or (self.F < 0).any():
+                bad = int(np.flatnonzero(~(np.isfinite(self.F) & (self.F >= 0)).reshape(-1))[0])
+                raise ValueError(f"cell {bad}: initial must be finite and >= 0")
+        # the class table indexed by the id itself (entry 0 is never used), S formed once
+        self.ks, self.S, self.capacity = (np.zeros(n + 1) for _ in range(3))
+        self.ks[1:], self.S[1:], self.capacity[1:] = c["ks"], c["suction"] * c["deficit"], c["capacity"]
+        self.applies = 0
+        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES}   # per cell: iterations in which it took the branch
+
+    def branch_totals(self):
+        return {k: int(v.sum()) for k, v in self.branches.items()}
+
+    @staticmethod
+    def step(ks, S, capacity, F, z, zmax, bed, dt):
+        """soil_step on fp64 arrays, one element per cell of a class other than 0 -> (dF, z1, masks): the level before it is rounded,
+        and which branch each element took."""
+        dt = np.float64(dt)
+        with np.errstate(invalid="ignore", over="ignore"):
+            counted = (zmax > -9999.0) & (bed <= 9999.0)
+            depth = z - bed
+            wet = depth > 0.0
+            kd = ks * dt
+            b = kd - 2.0 * F
+            disc = b * b + (8.0 * kd) * (S + F)
+            root = np.sqrt(np.where(disc >= 0.0, disc, 0.0))                 # (disc is a sum of two non-negative terms, or a NaN)
+            root = np.where(disc >= 0.0, root, np.nan)
+            pot = 0.5 * (b + root)
+            pot = np.where(pot > 0.0, pot, 0.0)
+            room = capacity - F
+            full = ~(room > 0.0)
+            capped = ~full & (room < pot)
+            pot = np.where(full, 0.0, np.where(capped, room, pot))
+            limited = depth < pot
+            dF = np.where(limited, depth, pot)
+            live = counted & wet & (dt > 0.0)
+            dF = np.where(live & (dF > 0.0), dF, 0.0)
+            z1 = np.where(dF > 0.0, z - dF, z)
+        masks = dict(not_counted=~counted, dry=counted & ~wet, capacity_full=live & full, depth_limited=live & ~full & limited,
+                     capacity_cap=live & capped & ~limited, potential=live & ~full & ~capped & ~limited)
+        return dF, z1, masks
+
+    def apply(self, state, bed, dt):
+        """One iteration's infiltration, in place on `state` (the iteration's source buffer) and on F; `dt`: the timestep scalar of
+        that iteration.  Returns the number of cells changed."""
+        if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or not state.flags.c_contiguous:
+            raise ValueError("state must be a contiguous [rows, cols, 4] and bed [rows, cols]")
+        real = state.dtype.type
+        dt = np.float64(real(dt))
+        self.applies += 1
+        if not dt > 0.0:
+            return 0
+        st, zb, F, ids = state.reshape(-1, 4), np.asarray(bed).reshape(-1), self.F.reshape(-1), self.soil.reshape(-1)
+        at = np.flatnonzero((ids != 0) & ~self.ring.reshape(-1))
+        k = ids[at]
+        dF, z1, masks = self.step(self.ks[k], self.S[k], self.capacity[k], F[at], st[at, 0].astype(np.float64), st[at, 1].astype(np.float64),
+                                  zb[at].astype(np.float64), dt)
+        move = dF > 0.0
+        st[at[move], 0] = z1[move].astype(real)
+        F[at[move]] = F[at[move]] + dF[move]
+        self.branches["ring"] += self.ring
+        self.branches["impervious"] += (self.soil == 0) & ~self.ring
+        for name, mask in masks.items():
+            self.branches[name].reshape(-1)[at] += mask
+        return int(move.sum())
+
+
+def write_soil_csv(path, classes):
+    """The source of a <soilClasses> element: what parse_configuration reads back (repr round-trips every double)."""
+    from . import pack_soil_classes
+    with open(path, "w") as f:
+        f.write("ks,suction,deficit,capacity\n")
+        for c in pack_soil_classes(classes):
+            f.write(",".join(repr(float(c[k])) for k in ("ks", "suction", "deficit", "capacity")) + "\n")
 
 
 def derive_output(what, state, bed, resolution=1.0):

@@ -182,7 +182,7 @@ class Model:
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
                  probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None,
-                 links=None):
+                 links=None, infiltration=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -208,6 +208,33 @@ class Model:
             if cfg.scheme == frontend.SCHEME_MUSCL_HANCOCK and log:
                 log("Warning: link groups are inert under MUSCL-Hancock, like every boundary condition (quirk Q8)")
             sim.add_links(self.link_list)
+        # The infiltration (no reference counterpart): the raster of a <dataSource type="raster" value="soil" source="..."/> with the
+        # classes of <soilClasses source="soil.csv"/> (columns ks, suction, deficit, capacity), or `infiltration`: dict(soil=, classes=,
+        # initial=) with soil an array [rows, cols] (row 0 = south; 0 = impervious) or a raster file.  Behind the file's boundaries and
+        # the links, so the rain of an iteration is on the ground before the soil takes its share.  It acts inside every iteration, so
+        # only an engine that has it on the device will do.  A <dataTarget value="infiltration" .../> writes F at every output time.
+        spec = dict(infiltration) if infiltration else None
+        source = next((src for src in cfg.sources if "soil" in src[1]), None)
+        if spec is None and source is not None:
+            if source[0] != "raster":
+                raise ValueError("the soil data source must be a raster")
+            if not cfg.soil_classes:
+                raise ValueError("the soil data source needs a <soilClasses source=.../> element")
+            spec = dict(soil=os.path.join(cfg.source_dir, source[2]), classes=cfg.soil_classes)
+        self.infiltration = None
+        if spec is not None:
+            soil = spec["soil"]
+            soil = frontend.read_raster(soil)[0] if isinstance(soil, (str, os.PathLike)) else np.asarray(soil)
+            if soil.shape != (self.rows, self.cols):
+                raise ValueError(f"the soil raster is {soil.shape[1]} x {soil.shape[0]} cells, the domain {self.cols} x {self.rows}")
+            if not hasattr(sim, "add_infiltration"):
+                raise NotImplementedError("the infiltration acts inside every iteration: it needs an engine with add_infiltration (the HIP engine)")
+            if cfg.scheme == frontend.SCHEME_MUSCL_HANCOCK and log:
+                log("Warning: the infiltration is inert under MUSCL-Hancock, like every boundary condition (quirk Q8)")
+            self.infiltration = dict(soil=soil, classes=list(spec["classes"]), initial=spec.get("initial"))
+            sim.add_infiltration(soil, self.infiltration["classes"], self.infiltration["initial"])
+        elif any(what == "infiltration" for what, _ in cfg.targets):
+            raise ValueError("an infiltration data target needs a soil data source")
         self.scheme = SchemeDriver(sim, cfg, self.cols * self.rows)
         self.output_format, self.log, self.clock = output_format, log, clock
         self.progress_interval = progress_interval
@@ -439,7 +466,8 @@ class Model:
         if not due:
             return False
         is_peak = [frontend.peak_value_code(what) is not None for what, _ in self.cfg.targets]
-        plain = [what for (what, _), pk in zip(self.cfg.targets, is_peak) if not pk]
+        is_soil = [what == "infiltration" for what, _ in self.cfg.targets]     # the cumulative infiltration F: the engine's own raster
+        plain = [what for (what, _), pk, so in zip(self.cfg.targets, is_peak, is_soil) if not pk and not so]
         if self.device_outputs:                                    # every target in ONE call, rasters only over the host link
             derived = self.sim.derive(plain) if plain else {}
         elif plain or not self.cfg.targets:
@@ -468,6 +496,8 @@ class Model:
         for k, (what, pattern) in enumerate(self.cfg.targets):
             if is_peak[k]:
                 arr = peaks[frontend.peak_value_code(what)]
+            elif is_soil[k]:
+                arr = self.sim.infiltration_read()
             else:
                 arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
             out[what] = arr

@@ -246,6 +246,13 @@ class HipEngine:
     def links_read(self, first=0, count=None):
         return self.domain.links_read(first, count)
 
+    # the infiltration (Domain.add_infiltration)
+    def add_infiltration(self, soil, classes, initial=None):
+        self.domain.add_infiltration(soil, classes, initial)
+
+    def infiltration_read(self, row0=0, nrows=None):
+        return self.domain.infiltration_read(row0, nrows)
+
     # the peak tracker (Domain.peaks_*)
     def peaks_enable(self, values, arrival_depth=0.01):
         self.domain.peaks_enable(values, arrival_depth=arrival_depth)
@@ -663,6 +670,39 @@ class StripRunner:
         for idx, rec in parts:
             out[idx] = rec
         return out
+
+    # ---- the infiltration: every rank adds the rows of the global rasters that it stores, ghost rows included, and recomputes F on its
+    #      ghost rows: F is a function of the cell's own history of (Z, dt), which with an exchange after every iteration is its owner's
+    #      bit for bit.  Nothing of F is exchanged; with two reaches of ghost rows the outer one is stale every other iteration ----
+    def add_infiltration(self, soil_global, classes, initial_global=None):
+        """`soil_global`, `initial_global`: the [rows, cols] rasters of the WHOLE grid (row 0 = south); every rank calls it with the
+        same arguments.  Refused BEFORE any rank adds anything where the strips exchange after every second iteration only."""
+        from . import soil_ids
+        if not hasattr(self.engine, "add_infiltration"):
+            raise RuntimeError("add_infiltration: this engine has no infiltration (the HIP engine's hp_boundary_add_infiltration)")
+        if self.exchange_period > 1 and self.world > 1:
+            raise ValueError("add_infiltration: the strips store two reaches of ghost rows and exchange after every second iteration "
+                             "(exchange_period = 2): the cumulative infiltration on the outer reach would drift from its owner's; use exchange_period = 1")
+        ids = soil_ids(soil_global)
+        if ids.shape != (self.rows, self.cols):
+            raise ValueError(f"the soil raster must be [{self.rows}, {self.cols}]")
+        f0 = None
+        if initial_global is not None:
+            f0 = np.asarray(initial_global, dtype=np.float64)
+            if f0.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial infiltration must be [{self.rows}, {self.cols}]")
+            f0 = np.ascontiguousarray(f0[self.local_slice()])
+        self.engine.add_infiltration(np.ascontiguousarray(ids[self.local_slice()]), classes, f0)
+        self._infiltration = True
+
+    def gather_infiltration(self):
+        """The cumulative infiltration F of the whole grid on rank 0 (fp64 [rows, cols], equal to the single domain's
+        Domain.infiltration_read() in every bit), None on the other ranks: every rank's OWNED rows.  Collective."""
+        if not getattr(self, "_infiltration", False):
+            raise RuntimeError("gather_infiltration: no infiltration was added")
+        mine = self.engine.infiltration_read(self.own_lo - self.local_lo, self.own_hi - self.own_lo)
+        parts = self._gather_parts(mine)
+        return np.concatenate(parts, axis=0) if self.rank == 0 else None
 
     def gather_outputs(self, values, dtype=np.float64):
         """Output rasters of the whole grid: every rank derives its OWNED rows on its device (Domain.derive), rank 0 gets

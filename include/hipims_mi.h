@@ -509,7 +509,10 @@ int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out);   /* BLOCKS */
  * While the domain has link groups (hp_boundary_add_links), hp_state_save also keeps the links' records and hp_state_restore puts
  * them back: the iterations that are repeated count again what they counted.  If link groups were added or cleared since the
  * snapshot, hp_state_restore sets the records of the links the domain has now to zero and sends one HP_LOG_WARNING to the log
- * sink: the probe recorder's rule. */
+ * sink: the probe recorder's rule.
+ * While the domain has an infiltration (hp_boundary_add_infiltration), hp_state_save also copies F and hp_state_restore puts it
+ * back.  If the infiltration was added or cleared since the snapshot, hp_state_restore leaves F as it is and sends one
+ * HP_LOG_WARNING to the log sink. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
@@ -605,7 +608,65 @@ int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count
  * memory must stay alive until then).  first + count beyond the domain's links is HP_ERR_INVALID; count == 0 is HP_OK. */
 int hp_links_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_link_record_t* out);
 int hp_links_info(hp_domain_t* d, uint64_t* links, uint64_t* groups);   /* host counters; either pointer may be NULL */
-int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups too (and their records) */
+/* ---- infiltration: water leaves the surface into the soil -- Green-Ampt by soil class (no reference counterpart: the reference
+ *      takes water out through the uniform loss rate only, one number for the whole domain and no memory).  Every cell carries a
+ *      soil class id (0 = impervious) and its cumulative infiltrated depth F; the infiltration is the fifth boundary kind, next to
+ *      uniform, gridded, cell and link groups: applied once per iteration on the iteration's source buffer, at its place in the
+ *      order added.  The kernel is one lane per cell (csrc/hp_soil.hpp: bdy_infiltration): a streaming pass over the class bytes
+ *      that touches the state and F only where the class is not 0.
+ *      STATE.  One fp64 raster F in device memory (8 bytes per cell) and one byte per cell for the class id; nothing of either
+ *      exists on a domain that never adds infiltration, and such a domain queues exactly what it queued without this call.
+ *      At most one infiltration per domain: a second hp_boundary_add_infiltration is HP_ERR_STATE.  A domain with it is not
+ *      fusable (hp_boundaries_fused is false, as with a cell boundary or a link group), so it runs single iterations, never
+ *      iteration pairs; and it never runs a speculative STRICT batch (a batch that is queued again would add to F twice).  Under
+ *      MUSCL-Hancock it is inert, like every boundary (quirk Q8): F does not move.
+ *      THE CONTRACT.  All arithmetic in fp64 whatever the domain's precision, the stored values widened first; correctly rounded
+ *      add, multiply, divide, square root and compare only, never fused.  dt is the "Timestep" scalar; S = suction * deficit is
+ *      formed once on the host.  Per cell and iteration:
+ *        1. The cell is untouched, F included, if dt <= 0, if its class is 0, if it is not counted in the sense of
+ *      hp_domain_stats (a cell is counted when Zmax > -9999 and bed <= 9999), or if it lies on the edge ring of the GLOBAL grid
+ *      (column 0 or cols - 1, global row 0 or global_rows - 1): the area boundaries' rule.  The flux kernels never write the ring
+ *      and the engine prices the ring's part of the timestep once per upload, so nothing drains it.
+ *        2. depth = Z - bed.  If !(depth > 0), nothing happens.
+ *        3. The potential: the closed-form Green-Ampt step of CASC2D / GSSHA, finite at F == 0.  kd = ks * dt;
+ *      b = kd - 2.0 * F; disc = b * b + (8.0 * kd) * (S + F); pot = 0.5 * (b + sqrt(disc)).  If !(pot > 0), pot = 0.
+ *        4. room = capacity - F.  If !(room > 0), pot = 0; else if room < pot, pot = room.
+ *        5. dF = depth < pot ? depth : pot.
+ *        6. If dF > 0: Z = (T)(Z - dF), rounded once, and F = F + dF.  Zmax, Qx and Qy stay as they are: the loss rate's and the
+ *      links' rule.  A cell with dF == 0 is not stored at all.
+ *      frontend.Infiltration restates all of it in NumPy; tests/soil_probe.cpp holds the two to each other bit for bit.
+ *      STRIPS.  The id raster and `initial` are of the LOCAL array, ghost rows included, as the zone raster is.  Every strip
+ *      recomputes F on its ghost rows: F is a function of the cell's own history of (Z, dt), and with an exchange after every
+ *      iteration that history is its owner's bit for bit, so nothing of F is exchanged.  A strip with two reaches of ghost rows
+ *      holds its outermost reach on every second iteration only, and F there would drift from its owner's: on such a strip
+ *      hp_boundary_add_infiltration returns HP_ERR_UNSUPPORTED. ---- */
+typedef struct {
+	double ks;                         /* saturated hydraulic conductivity, m/s; finite, >= 0 */
+	double suction;                    /* wetting-front suction head psi, m; finite, >= 0 */
+	double deficit;                    /* moisture deficit dtheta, -; in [0, 1] */
+	double capacity;                   /* largest cumulative infiltration, m; >= 0, +inf for none */
+} hp_soil_class_t;
+typedef struct {
+	uint32_t struct_size;
+	uint32_t class_count;              /* 1..255 */
+	const hp_soil_class_t* classes;    /* class k is classes[k-1] */
+	const uint8_t* soil_of_cell;       /* cols*rows ids of the LOCAL array, row 0 = south; 0 = impervious, 1..class_count */
+	const double*  initial;            /* cols*rows cumulative infiltration F0 in m (finite, >= 0), or NULL for zeros: a hot start */
+} hp_infiltration_desc_t;
+/* Argument errors -- a bad struct_size, a NULL pointer, class_count outside 1..255, an id above class_count, a non-finite or
+ * negative ks or suction, a deficit outside [0, 1], a NaN or negative capacity, a non-finite ks * 1e6 or suction * deficit, a
+ * negative or non-finite initial -- are HP_ERR_INVALID before any device call; where a cell is at fault the message names the
+ * first offending cell.  Between hp_step_begin and hp_step_end the call returns HP_ERR_STATE.  If an allocation fails the call
+ * returns HP_ERR_HIP and the domain stays usable without infiltration.  The arrays are free on return. */
+int hp_boundary_add_infiltration(hp_domain_t* d, const hp_infiltration_desc_t* desc);
+/* Rows row0 .. row0 + nrows - 1 of F (fp64, cols values a row).  Enqueued; valid after hp_sync (the host memory must stay alive
+ * until then).  A row range outside the array is HP_ERR_INVALID; a domain without infiltration, or a call between hp_step_begin
+ * and hp_step_end, HP_ERR_STATE. */
+int hp_infiltration_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows);
+/* Host counters, does not block: the classes of the domain's infiltration and its cells of a class other than 0 (both 0 without
+ * one); either pointer may be NULL. */
+int hp_infiltration_info(hp_domain_t* d, uint32_t* classes, uint64_t* pervious_cells);
+int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups too (and their records), and the infiltration with its F */
 /* Are the domain's area boundaries carried by the flux kernel itself (rain / loss of iteration n+1 added to the state
  * iteration n stores, no separate pass over the grid)?  True for the Godunov scheme with up to three uniform / gridded
  * boundaries, no cell boundary among them, and rain grids of at least 64 model cells per grid cell; everything else runs
