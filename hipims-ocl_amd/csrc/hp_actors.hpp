@@ -85,9 +85,8 @@ template <typename T> int apply_boundaries(hp_domain* d, void* target)
 // else keeps the stand-alone pass.  HP_FUSE_BDY=0 switches the fusion off (A/B runs).
 template <typename T> int refresh_fusable_t(hp_domain* d)
 {
-	static const bool enabled = !(std::getenv("HP_FUSE_BDY") && std::atoi(std::getenv("HP_FUSE_BDY")) == 0);
 	d->fusable = false;
-	if (!enabled || d->desc.scheme != HP_SCHEME_GODUNOV || d->desc.kernel == HP_KERNEL_BASIC) return HP_OK;
+	if (!plan_knobs().fuse_bdy || d->desc.scheme != HP_SCHEME_GODUNOV || d->desc.kernel == HP_KERNEL_BASIC) return HP_OK;
 	if (d->bdy.empty() || d->bdy.size() > (size_t)FUSED_BDY_MAX) return HP_OK;
 	AreaBdyList<T> list;
 	list.count = 0;

@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_facts.hpp"
+#include "hp_plan.hpp"
 #include "hp_kernels.hpp"
 #include "hp_peaks.hpp"
 #include "hp_probes.hpp"
@@ -327,6 +328,7 @@ static_assert(HOST_SPEC_FLAG + 8 <= HOST_READBACK && HOST_READBACK + 16 <= HOST_
 
 int check_domain(hp_domain* d);           // (hp_engine.hip: every entry point that touches the device comes through it)
 template <typename T> Params<T> make_params(const hp_domain* d);             // (hp_engine.hip)
+const PlanKnobs& plan_knobs();                                               // (hp_engine.hip: the rules' switches, read from the environment once)
 template <typename T> int apply_boundaries(hp_domain* d, void* target);      // (hp_actors.hpp: the boundaries, in the order added, onto `target`)
 
 // f(T{}) with T = the domain's precision: a launch that differs only in that type is written once

@@ -45,11 +45,50 @@ struct Rccl {
 void peer_release(hp_domain* d);      // (mailboxes of the peer-written maximum, further down)
 PeerBox peer_box(hp_domain* d, bool use, long timeout_ms = 0);
 PeerPush make_push(const hp_domain* d);
-constexpr unsigned TAIL_MAX_BLOCKS = 65536;    // words allocated per domain
-static unsigned tail_limit()
+
+// The rules' switches (hp_plan.hpp) from the environment: the only place that names these variables, read once per process, at the
+// first call.  (HP_MARCH2_RSEG's value is a tiling knob, below; here only whether it is set at all.)
+const PlanKnobs& plan_knobs()
 {
-	static const unsigned v = std::getenv("HP_TAIL_MAX_BLOCKS") ? (unsigned)std::atoi(std::getenv("HP_TAIL_MAX_BLOCKS")) : TAIL_MAX_BLOCKS;   // (a knob for A/B runs; 768 = one round of blocks)
-	return v < TAIL_MAX_BLOCKS ? v : TAIL_MAX_BLOCKS;
+	static const PlanKnobs knobs = [] {
+		auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? std::atoi(e) : unset; };
+		auto off = [&](const char* name) { return num(name, 1) == 0; };          // NAME=0 switches off
+		auto on = [&](const char* name) { return num(name, 0) != 0; };           // NAME=1 (any non-zero) switches on
+		auto force = [&](const char* name) { return std::getenv(name) ? (num(name, 0) != 0 ? 1 : 0) : -1; };
+		PlanKnobs k;
+		k.two_step = num("HP_TWO_STEP", -1);
+		k.launch_tail = !off("HP_LAUNCH_TAIL"); k.strip_reduce_always = on("HP_STRIP_REDUCE_ALWAYS");
+		k.pair_bdy = !off("HP_PAIR_BDY"); k.pair_strict = !off("HP_PAIR_STRICT"); k.pair_exact = force("HP_PAIR_EXACT");
+		k.pair_skip = !off("HP_PAIR_SKIP"); k.fill_after_pairs = !off("HP_FILL_AFTER_PAIRS");
+		k.strict_speculate = on("HP_STRICT_SPECULATE"); k.pair_tune = !off("HP_PAIR_TUNE"); k.sweep_alternate = force("HP_SWEEP_ALTERNATE");
+		k.tail_max_blocks = (unsigned)num("HP_TAIL_MAX_BLOCKS", (int)TAIL_MAX_BLOCKS);
+		k.tail_max_blocks_k2k6 = (unsigned)num("HP_TAIL_MAX_BLOCKS_K2K6", (int)TAIL_MAX_BLOCKS);
+		k.march2_rseg_forced = std::getenv("HP_MARCH2_RSEG") != nullptr;
+		k.fuse_bdy = !off("HP_FUSE_BDY");
+		return k;
+	}();
+	return knobs;
+}
+// What the rules read from the domain, as it is now: scalar copies and one walk over the boundary list.  Taken where a rule is
+// evaluated -- nothing is kept, so nothing can go stale.
+PlanDomain plan_domain(const hp_domain* d)
+{
+	PlanDomain p;
+	p.scheme = d->desc.scheme; p.kernel = d->desc.kernel; p.math_mode = d->desc.math_mode; p.precision = d->desc.precision; p.dynamic_dt = d->desc.dynamic_dt;
+	p.quirks = d->desc.quirks; p.rows = d->desc.rows; p.cols = d->desc.cols; p.cells = d->cells;
+	p.row_offset = d->desc.row_offset; p.global_rows = d->desc.global_rows; p.ghost_rows = d->ghost_rows;
+	p.has_bdy = !d->bdy.empty(); p.fusable = d->fusable; p.bdy_on_ring = d->bdy_on_ring;
+	for (const Boundary& b : d->bdy)
+		if ((b.kind == BDY_UNIFORM && b.definition == HP_UNIFORM_LOSS_RATE) || (b.kind == BDY_GRIDDED && b.definition == HP_GRIDDED_MASS_FLUX)) p.bdy_removes_water = true;
+	p.has_comm = d->comm != nullptr; p.comm_world = d->comm_world; p.peer_direct = d->peer_direct; p.peer_mine = d->peer_mine != nullptr;
+	p.has_tail_words = d->tail_words != nullptr; p.tail_allowed = d->tail_allowed; p.halo_overlap = d->halo_overlap; p.split_now = d->split_now;
+	p.strip_any_bdy = d->strip_any_bdy; p.strip_first = d->strip_first; p.strip_any_full = d->strip_any_full;
+	p.spec_now = d->spec_now; p.has_stamps = d->z_state != nullptr; p.march2_pays = d->tiling.march2_pays;
+	p.has_links = d->links.groups != 0; p.soil_on = d->soil.on;
+#ifdef HP_KEEP_SPEC_FUSED
+	p.spec_fused_kept = true;                                             // (launch_march: the instantiation kept buildable for study)
+#endif
+	return p;
 }
 
 template <typename T> Params<T> make_params(const hp_domain* d)
@@ -127,10 +166,10 @@ template <typename T> int price_edge_ring(hp_domain* d)
 	return HP_OK;
 }
 
-// The tiling knobs (hp_tiling.hpp) from the environment: these three readers are the only place that names the variables.  Each is
+// The tiling knobs (hp_tiling.hpp) from the environment: these two readers are the only place that names the variables.  Each is
 // read when it always was: at hp_domain_create HP_RSEG_REFINE and the pair kernel's look at HP_TILING_SEARCH once per process,
 // the others per domain (tools/strong_probe_pair.py creates domains with the K1 / K6 search on and off); once per process, at the
-// first launch, what make_tile_map takes; once per process, at the first pair launch, whether HP_MARCH2_RSEG is set at all.
+// first launch, what make_tile_map takes.
 TilingKnobs tiling_knobs()
 {
 	auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? std::atoi(e) : unset; };
@@ -151,11 +190,6 @@ const LaunchKnobs& launch_knobs()
 	static const LaunchKnobs k = {std::getenv("HP_HALO_ROWS") ? std::atol(std::getenv("HP_HALO_ROWS")) : 0,
 	                              std::getenv("HP_NBANDS") ? std::atoi(std::getenv("HP_NBANDS")) : 0};
 	return k;
-}
-bool march2_rseg_forced()               // (run_pair_t: no STRICT 12-row cap then)
-{
-	static const bool forced = std::getenv("HP_MARCH2_RSEG") != nullptr;
-	return forced;
 }
 
 // Rows one flux launch updates: everything between the never-written edge ring / the outermost ghost rows.  A strip with
@@ -191,7 +225,8 @@ template <typename T> int make_tail(hp_domain* d, unsigned& blocks, int part, hi
 {
 	tail = LaunchTail<T>{};
 	if (part == PART_ALL) d->flux_launches++;
-	if (!(d->tail_want && part == PART_ALL && stream == d->stream && blocks <= limit)) return 0;
+	const int kind = tail_kind_for(d->tail_want, part == PART_ALL, stream == d->stream, blocks, limit, d->push_now);
+	if (kind == 0) return 0;
 	tail.done = d->tail_words;
 	tail.done1 = d->tail_words + TAIL_MAX_BLOCKS + 8;
 	tail.bdy_flag = 0;
@@ -204,8 +239,7 @@ template <typename T> int make_tail(hp_domain* d, unsigned& blocks, int part, hi
 	tail.box = peer_box(d, (d->tail_fresh & 4) != 0);
 	tail.edge_rows[0] = tail.edge_rows[1] = tail.edge_rows[2] = tail.edge_rows[3] = 0;
 	tail.peer_rows[0] = tail.peer_rows[1] = nullptr;
-	int kind = 1;
-	if (d->push_now) {
+	if (kind == 2) {
 		const long G = d->ghost_rows, rows = d->desc.rows, cols = d->desc.cols;
 		const int b = d->facts->use_alt ^ 1;
 		if (d->peer_state[0][b]) {
@@ -216,41 +250,17 @@ template <typename T> int make_tail(hp_domain* d, unsigned& blocks, int part, hi
 			tail.peer_rows[1] = (State4<T>*)d->peer_state[1][b] - (rows - 2 * G) * cols;                // my row rows - 2G -> its row 0
 			tail.edge_rows[2] = (int)(rows - 2 * G); tail.edge_rows[3] = (int)(rows - G);
 		}
-		kind = 2;
 	}
 	blocks += 1;
 	d->tail_done = true;
 	d->flux_launches_tailed++;
 	return kind;
 }
-// (K2 / K6 have their own knob for A/B runs.  A first probe had them lose 0.5 / 1.7 % at the 4608 blocks of 4096^2 and a limit of
-// two rounds of blocks was set; bench.py's interleaved repeats on one box then showed the opposite -- MUSCL-Hancock 4096^2
-// 0.311 -> 0.302 ms, fp32 0.215 -> 0.192, inertial 0.268 -> 0.249-0.263 -- so there is no limit of their own any more)
-static unsigned tail_limit_k2k6()
-{
-	static const unsigned v = std::getenv("HP_TAIL_MAX_BLOCKS_K2K6") ? (unsigned)std::atoi(std::getenv("HP_TAIL_MAX_BLOCKS_K2K6")) : TAIL_MAX_BLOCKS;
-	return std::min(tail_limit(), v);
-}
 
-// Alternating sweep direction.  A launch leaves the last ~250 MiB it loaded or stored in the Infinity Cache (256 MiB, stores
-// allocate: MI355X_MICROARCH.md), and what it stored last is the top of every row band -- exactly what the NEXT launch, which reads
-// the state this one wrote, would reach last.  Every other whole-domain launch therefore visits each band's tiles from the top down
-// (TileMap::flip: the same tiles mirrored within the band): it starts on rows whose new state and bed may still be on the die.  Pure
-// scheduling: which wavefront solves a face never changes its bits.  Measured (profiles/r04zv_sweep_alternate_again.txt,
-// r04zw_sweep_alternate_f64.txt; same box, interleaved): fp32, whose launch is 0.6 GB: S-DAM 4096^2 +5 %, S-RAIN +2.5 %, S-ROUGH
-// +3 %, MUSCL +2.3 %, 8192^2 +0.7 %; fp64 MUSCL +2.5 % on the dam break, +0.5 % on live water; fp64 Godunov and inertial: 0 to -3 %
-// (2048^2, 16384 x 1026, 16384 x 8192) and erratic at 4096^2 and 8192^2.  Box-dependent: a third box showed no difference at all
-// for fp32 (0.1290 / 0.1300 / 0.1291 ms).  So: on for fp32 and for fp64 MUSCL, where it was never behind; off for fp64 Godunov /
-// inertial; HP_SWEEP_ALTERNATE=0 / 1 forces it.
-inline bool sweep_alternates(const hp_domain* d)
-{
-	static const int forced = std::getenv("HP_SWEEP_ALTERNATE") ? (std::atoi(std::getenv("HP_SWEEP_ALTERNATE")) != 0 ? 1 : 0) : -1;
-	if (forced >= 0) return forced != 0;
-	return d->desc.precision == 4 || d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK;
-}
+// Alternating sweep direction (hp_plan.hpp: sweep_alternates): every other whole-domain launch visits each band's tiles from the top down.
 inline void sweep_direction(hp_domain* d, const int part, TileMap& tm)
 {
-	if (part != PART_ALL || !sweep_alternates(d)) return;
+	if (part != PART_ALL || !sweep_alternates(plan_domain(d), plan_knobs())) return;
 	tm.flip = d->sweep_flip;
 	d->sweep_flip ^= 1;
 }
@@ -269,7 +279,7 @@ int launch_muscl(hp_domain* d, const void* src, void* dst, int edge_buffer, int 
 		return HP_OK;
 	sweep_direction(d, part, tm);
 	LaunchTail<T> tail;
-	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit_k2k6(), tail);
+	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit_k2k6(plan_knobs()), tail);
 #define HP_LAUNCH_K2S(UNIFORM_, TAIL_, SPEC_)                                                                                        \
 	hipLaunchKernelGGL((muscl_march<STRICT, CFL_MODE, UNIFORM_, TAIL_, T, SPEC_>), dim3(blocks), dim3(256), 0, stream, p,            \
 	                   (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)src, (State4<T>*)dst,                     \
@@ -305,7 +315,7 @@ int launch_march(hp_domain* d, const void* src, void* dst, int edge_buffer, int 
 	const int truncated = ((d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0 ? 1 : 0) | (d->fill_now ? 2 : 0);   // the kernel's `flags`
 
 	LaunchTail<T> tail;
-	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit(), tail);
+	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit(plan_knobs()), tail);
 #define HP_LAUNCH_K1S(FUSED_, TAIL_, LIST_, NEXT_, SPEC_)                                                                                   \
 	hipLaunchKernelGGL((godunov_march<STRICT, CFL_MODE, FUSED_, TAIL_, T, SPEC_>), dim3(blocks), dim3(256), 0, stream, p,                   \
 	                   (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)src, (State4<T>*)dst,                     \
@@ -354,7 +364,7 @@ int launch_inertial(hp_domain* d, const void* src, void* dst, int edge_buffer, i
 		return HP_OK;
 	sweep_direction(d, part, tm);
 	LaunchTail<T> tail;
-	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit_k2k6(), tail);
+	const int tail_kind = make_tail<T>(d, blocks, part, stream, tail_limit_k2k6(plan_knobs()), tail);
 #define HP_LAUNCH_K6(TAIL_)                                                                                                         \
 	hipLaunchKernelGGL((inertial_march<STRICT, CFL_MODE, TAIL_, T>), dim3(blocks), dim3(256), 0, stream, p,                          \
 	                   (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)src, (State4<T>*)dst,                     \
@@ -366,20 +376,21 @@ int launch_inertial(hp_domain* d, const void* src, void* dst, int edge_buffer, i
 }
 
 template <typename T, bool STRICT>
-int launch_flux(hp_domain* d, const void* src, void* dst, int cfl_mode, int part, hipStream_t stream)
+int launch_flux(hp_domain* d, const void* src, void* dst, const SinglePlan& plan, int part, hipStream_t stream)
 {
 	const Params<T> p = make_params<T>(d);
+	const int cfl_mode = plan.cfl_mode, ring = plan.edge_buffer;          // (ring of the buffer that is priced: plan_single)
 	if (d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK) {
 		if (p.cols < 5 || p.rows < 5) return fail(HP_ERR_INVALID, "MUSCL-Hancock needs at least a 5x5 grid");
-		return cfl_mode ? launch_muscl<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream)
-		                : launch_muscl<T, STRICT, 0>(d, src, dst, 0, part, stream);
+		return cfl_mode ? launch_muscl<T, STRICT, 1>(d, src, dst, ring, part, stream)
+		                : launch_muscl<T, STRICT, 0>(d, src, dst, ring, part, stream);
 	}
 	if (d->desc.scheme == HP_SCHEME_INERTIAL) {
 		if (p.cols < 3 || p.rows < 3) return fail(HP_ERR_INVALID, "the inertial scheme needs at least a 3x3 grid");
 		switch (cfl_mode) {
-		case 1:  return launch_inertial<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream);
-		case 2:  return launch_inertial<T, STRICT, 2>(d, src, dst, d->facts->use_alt, part, stream);
-		default: return launch_inertial<T, STRICT, 0>(d, src, dst, 0, part, stream);
+		case 1:  return launch_inertial<T, STRICT, 1>(d, src, dst, ring, part, stream);
+		case 2:  return launch_inertial<T, STRICT, 2>(d, src, dst, ring, part, stream);
+		default: return launch_inertial<T, STRICT, 0>(d, src, dst, ring, part, stream);
 		}
 	}
 	if (d->desc.kernel == HP_KERNEL_BASIC) {
@@ -392,45 +403,27 @@ int launch_flux(hp_domain* d, const void* src, void* dst, int cfl_mode, int part
 		HIP_TRY(hipGetLastError());
 		return HP_OK;
 	}
-	// ring of the buffer that is priced: mode 1 -> dst, mode 2 -> src (= primary)
 	switch (cfl_mode) {
-	case 1:  return launch_march<T, STRICT, 1>(d, src, dst, d->facts->use_alt ^ 1, part, stream);
-	case 2:  return launch_march<T, STRICT, 2>(d, src, dst, d->facts->use_alt, part, stream);
-	default: return launch_march<T, STRICT, 0>(d, src, dst, 0, part, stream);
+	case 1:  return launch_march<T, STRICT, 1>(d, src, dst, ring, part, stream);
+	case 2:  return launch_march<T, STRICT, 2>(d, src, dst, ring, part, stream);
+	default: return launch_march<T, STRICT, 0>(d, src, dst, ring, part, stream);
 	}
 }
 
-static bool pairs_possible(const hp_domain* d);
 // boundaries -> flux -> local CFL maximum   (CSchemeGodunov.cpp:1637-1657)
 template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 {
 	void* src = d->state[d->facts->use_alt];
 	void* dst = d->state[d->facts->use_alt ^ 1];
 	int rc;
-	const bool has_bdy = !d->bdy.empty() && d->desc.scheme != HP_SCHEME_MUSCL_HANCOCK;   // MUSCL never applies them (Q8)
-	if (has_bdy) {
+	const PlanDomain pd = plan_domain(d);
+	if (boundaries_applied(pd)) {
 		d->fork_is_advance = false;
 		if ((rc = apply_boundaries<T>(d, src)) != HP_OK) return rc;
 	}
-
-	// Which buffer does the CFL reduction price?  Q1: always the primary one (CSchemeGodunov.cpp:1629/:1634);
-	// otherwise what this iteration writes.
-	const bool q1 = (d->desc.quirks & HP_QUIRK_CFL_READS_PRIMARY) != 0;
-	const bool muscl = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK;
-	const bool basic = d->desc.kernel == HP_KERNEL_BASIC && d->desc.scheme == HP_SCHEME_GODUNOV;
-	const bool dst_is_primary = d->facts->use_alt == 1;
-	int cfl_mode = 0;                                    // fused epilogue of the tuned kernel
-	if (d->desc.dynamic_dt && !basic) {
-		// MUSCL-Hancock has ONE state buffer in the reference (updated in place), so its reduction always sees
-		// the new state: here that is dst, whichever physical buffer it is
-		if (muscl || !q1 || dst_is_primary) cfl_mode = 1; // price what lands in dst
-		else if (has_bdy)          cfl_mode = 2;         // primary = source, changed in place by the boundaries
-		else                       cfl_mode = 0;         // primary untouched: last maximum still holds
-		// the ring maxima are cached from the last upload -- unless a cell boundary rewrites ring cells in place
-		// (bdy_cell accepts any cell; tst_Reduce re-reads every cell each iteration, CLDynamicTimestep.clc:166-249)
-		if (cfl_mode != 0 && (d->facts->edge_dirty || (has_bdy && d->bdy_on_ring)))
-			{ d->fork_is_advance = false; if ((rc = price_edge_ring<T>(d)) != HP_OK) return rc; }
-	}
+	// what the launch prices, whether it carries its own tail block, what follows it (hp_plan.hpp)
+	const SinglePlan plan = plan_single(pd, d->facts, plan_knobs());
+	if (plan.reprice_ring) { d->fork_is_advance = false; if ((rc = price_edge_ring<T>(d)) != HP_OK) return rc; }
 
 	// flux-kernel timing: every `stride`-th launch is bracketed by a pair of events taken from a pool created by
 	// hp_kernel_timing (nothing is created inside a timed region; once the pool is used up sampling stops)
@@ -439,7 +432,7 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 	// (... while pairs really run: a domain that COULD pair but does not -- batches of one iteration, a launch too big for the tail
 	// block, a maximum that stays stale -- is seen by its run of single iterations and samples them)
 	d->single_streak++;
-	const bool sample = d->timing_stride > 0 && d->timing_used < d->timing_events.size() && (!pairs_possible(d) || d->single_streak > 3) &&
+	const bool sample = d->timing_stride > 0 && d->timing_used < d->timing_events.size() && (!pairs_possible(pd, plan_knobs()) || d->single_streak > 3) &&
 	                    (d->timing_counter++ % (uint64_t)d->timing_stride) == 0;
 	hipEvent_t e0 = nullptr, e1 = nullptr;
 	if (sample) {
@@ -447,31 +440,9 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 		e1 = d->timing_events[d->timing_used].second;
 		HIP_TRY(hipEventRecord(e0, d->stream));
 	}
-	// The launch's own tail block instead of a separate advance launch (LaunchTail): inside a batch call, the tuned Godunov
-	// kernel, one launch over all rows, nothing between the flux launch and the advance (no stand-alone reduction), and
-	// either no reduction over strips at all or the strips' own transport in its plain shape (no rank with boundaries or a
-	// stale maximum: those iterations pass remembered maxima around, which stays with the advance launch).
-	{
-		static const bool enabled = !(std::getenv("HP_LAUNCH_TAIL") && std::atoi(std::getenv("HP_LAUNCH_TAIL")) == 0);
-		static const bool lonely_too = std::getenv("HP_STRIP_REDUCE_ALWAYS") && std::atoi(std::getenv("HP_STRIP_REDUCE_ALWAYS")) != 0;
-		const bool reduce_after = d->desc.dynamic_dt && cfl_mode == 0 && (basic || d->facts->need_full_reduce);
-		const int priced = (d->desc.dynamic_dt && cfl_mode != 0) ? 1 : 0;
-		// strips: the ranks reduce on the iterations strip_allreduce_max says (`everyone`); the tail block serves the two plain
-		// shapes -- this rank priced and everyone reduces, or nobody does -- and leaves the rest (a rank that passes its
-		// REMEMBERED maximum around: boundaries or a stale maximum somewhere else) to the advance launch
-		bool strips_ok = d->comm_world <= 1 ? !(d->comm && lonely_too) : d->peer_direct;
-		int fresh = priced;
-		if (d->comm_world > 1 && d->peer_direct) {
-			const bool everyone = d->desc.dynamic_dt && (muscl || !q1 || dst_is_primary || basic || d->strip_any_bdy ||
-			                                             (d->strip_first && d->strip_any_full));
-			strips_ok = (priced != 0) == everyone;
-			fresh = everyone ? 7 : 4;
-		}
-		d->tail_want = enabled && d->tail_allowed && !basic && !reduce_after && strips_ok &&
-		               !(d->halo_overlap && d->split_now) && d->tail_words != nullptr;
-		d->tail_fresh = fresh;
-		d->tail_done = false;
-	}
+	d->tail_want = plan.tail_want;
+	d->tail_fresh = plan.tail_fresh;
+	d->tail_done = false;
 	if (d->halo_overlap && d->split_now) {
 		// fork: everything queued so far (previous advance, boundaries, ring pricing) happens-before the halo
 		// segments; they run on their own stream, next to the interior segments on the domain's stream
@@ -480,12 +451,12 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 		if (!d->fork_is_advance) HIP_TRY(hipEventRecord(d->ev_fork, d->stream));
 		d->fork_is_advance = false;
 		HIP_TRY(hipStreamWaitEvent(d->stream_halo, d->ev_fork, 0));
-		if ((rc = launch_flux<T, STRICT>(d, src, dst, cfl_mode, PART_HALO, d->stream_halo)) != HP_OK) return rc;
+		if ((rc = launch_flux<T, STRICT>(d, src, dst, plan, PART_HALO, d->stream_halo)) != HP_OK) return rc;
 		HIP_TRY(hipEventRecord(d->ev_halo, d->stream_halo));
-		if ((rc = launch_flux<T, STRICT>(d, src, dst, cfl_mode, PART_INTERIOR, d->stream)) != HP_OK) return rc;
+		if ((rc = launch_flux<T, STRICT>(d, src, dst, plan, PART_INTERIOR, d->stream)) != HP_OK) return rc;
 		// join: the CFL maximum (and anything after it on the domain's stream) needs both launches
 		HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_halo, 0));
-	} else if ((rc = launch_flux<T, STRICT>(d, src, dst, cfl_mode, PART_ALL, d->stream)) != HP_OK) return rc;
+	} else if ((rc = launch_flux<T, STRICT>(d, src, dst, plan, PART_ALL, d->stream)) != HP_OK) return rc;
 	d->tail_want = false;
 	if (sample) {
 		HIP_TRY(hipEventRecord(e1, d->stream));
@@ -494,11 +465,11 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 
 	d->adv_fresh = 0;
 	if (d->desc.dynamic_dt) {
-		if (cfl_mode != 0) {
+		if (plan.cfl_mode != 0) {
 			d->adv_fresh = 1;
 			d->facts.maximum_priced();
-		} else if (basic || d->facts->need_full_reduce) {
-			const void* reduce_buf = q1 ? d->state[0] : dst;
+		} else if (plan.reduce_after) {
+			const void* reduce_buf = plan.reduce_buffer_is_primary ? d->state[0] : dst;
 			if ((rc = launch_reduce<T>(d, reduce_buf, d->own_lo, d->own_hi)) != HP_OK) return rc;
 			d->adv_fresh = 1;
 			d->facts.maximum_priced();
@@ -579,50 +550,7 @@ template <typename T> int step_end_impl(hp_domain* d)
 	return HP_OK;
 }
 
-// ---- two iterations per pass (hp_kernels.hpp: godunov_march2) -------------------------------------------------------------------
-// A pair is two consecutive iterations (k reads the primary buffer, k + 1 writes it) of a batch on a single domain run by ONE
-// launch.  Eligible: Godunov scheme, tuned kernel, FAST arithmetic, no boundary conditions (they act between the two iterations),
-// no strips, the reference's reduction quirk Q1 on (it is what makes the second timestep known in advance), the remembered maximum
-// valid, the launch's own tail block available (it advances the time twice), and the next iteration reads the primary buffer.
-// HP_TWO_STEP=0 switches it off, =1 forces it on wherever it is eligible; default: grids whose launch is at least two rounds of
-// blocks at 12-row tiles (choose_tiling: march2_pays -- below that the extra halo rows and the shorter tiles cost more than the
-// bytes save: 1024^2 and the 4096 x 514 strip lose 3-5 %, 2048^2 gains 13 %, 4096^2 22 %, profiles/r05n_two_step.txt).
-static int two_step_mode()
-{
-	static const int v = std::getenv("HP_TWO_STEP") ? std::atoi(std::getenv("HP_TWO_STEP")) : -1;
-	return v;
-}
-// (the part of the test that does not change from one iteration to the next: this domain's batches are made of pairs wherever two
-// iterations are to be had)
-static bool pairs_possible_common(const hp_domain* d)
-{
-	const int mode = two_step_mode();
-	if (mode == 0 || (mode < 0 && !d->tiling.march2_pays)) return false;
-	static const bool tail_enabled = !(std::getenv("HP_LAUNCH_TAIL") && std::atoi(std::getenv("HP_LAUNCH_TAIL")) == 0);
-	// boundary conditions: none, or area boundaries the flux kernel can carry itself (`fusable`: uniform / coarse gridded ones; round 6) --
-	// the pair kernel applies them between its two steps and prices the state it stores with and without the next iteration's
-	// (godunov_march2, BDY); single domains only.  HP_PAIR_BDY=0 keeps such domains on single iterations (A/B runs).
-	static const bool bdy_enabled = !(std::getenv("HP_PAIR_BDY") && std::atoi(std::getenv("HP_PAIR_BDY")) == 0);
-	// (fp32: from 30 M cells on -- S-RAIN 4096^2 fp32 LOSES 3 % in pairs, 0.1436 -> 0.1478 ms, where fp64 gains 7.5 % and 8192^2 gains 8-9 %
-	// in both precisions: profiles/r06w_srain_pairs_by_size.txt; with five waves per SIMD, the final binary: level at 16.8 M and 25 M cells,
-	// +5 % at 37.7 M, +13 % at 67 M: profiles/r06ah_f32_bdy_pairs_by_size.txt; HP_TWO_STEP=1 overrides)
-	const bool bdy_size_ok = d->desc.precision == 8 || d->cells >= 30000000 || mode > 0;
-	const bool bdy_ok = d->bdy.empty() || (bdy_enabled && bdy_size_ok && d->fusable && !d->comm && d->comm_world <= 1 && d->desc.dynamic_dt);
-	// STRICT (round 6): the same statements in the same order as K1's, so the pair is the same computation there too -- always with
-	// the stamps (the exact mode promises the reference's bits); no boundaries, single domains, dynamic timestep.  What it is for: rows
-	// of still water are a copy in STRICT (K1's skip), and a pair copies them at half the bytes.  HP_PAIR_STRICT=0 switches it off.
-	static const bool strict_enabled = !(std::getenv("HP_PAIR_STRICT") && std::atoi(std::getenv("HP_PAIR_STRICT")) == 0);
-	const bool math_ok = d->desc.math_mode == HP_MATH_FAST ||
-	                     (strict_enabled && d->bdy.empty() && !d->comm && d->comm_world <= 1 && d->desc.dynamic_dt && !d->spec_now);
-	return d->desc.scheme == HP_SCHEME_GODUNOV && d->desc.kernel != HP_KERNEL_BASIC && math_ok &&
-	       bdy_ok && (!d->desc.dynamic_dt || (d->desc.quirks & HP_QUIRK_CFL_READS_PRIMARY) != 0) &&
-	       tail_enabled && d->tail_words != nullptr && d->desc.rows >= 5 && d->desc.cols >= 5;
-}
-static bool pairs_possible(const hp_domain* d)          // a single domain
-{
-	return pairs_possible_common(d) && !d->comm && d->comm_world <= 1 && !d->peer_mine && d->desc.row_offset == 0 &&
-	       d->desc.global_rows == d->desc.rows;
-}
+// ---- two iterations per pass (hp_kernels.hpp: godunov_march2; which domains pair and when: hp_plan.hpp) ---------------------------------
 // After partial uploads (rings_differ: the two buffers' edge rings MAY differ) the rings are compared once, the first time pairs are
 // wanted: block-wise loads of a whole grid (hp_domain_upload_rows over all rows: how grids too big for one host array arrive) leave
 // them equal to the zero-filled other buffer's wherever the ring is the usual closed wall (state 0), and such domains pair.  Blocks.
@@ -645,33 +573,10 @@ static int rings_really_differ(hp_domain* d)
 	d->facts.rings_compared(*host == 0);
 	return HP_OK;
 }
-static bool pair_eligible(const hp_domain* d)
-{
-	return pairs_possible(d) && d->facts.pair_ready(d->desc.dynamic_dt != 0);
-}
-// A ROW STRIP runs pairs where it stores two reaches of ghost rows (one exchange per two iterations anyway) and the strips write
-// their rows into each other themselves (transport level 2: the pair's tail block holds the one mailbox round, which is the
-// hand-over).  What THIS rank can do goes into the batch's handshake (strip_handshake); the ranks pair up only if all of them can.
-static bool strip_pairs_possible_here(const hp_domain* d)
-{
-	return pairs_possible_common(d) && d->comm && d->comm_world > 1 && d->peer_direct && d->ghost_rows == 2 && !d->facts->rings_differ;
-}
 // The stamps' buffers (PairAux), allocated with a domain's first exact pair.
-// Which pairs keep quirk Q3 exact (godunov_march2's HZ instantiation: 4-9 % slower): HP_PAIR_EXACT=1 all of them, =0 none; default: the
-// domains whose area boundaries can REMOVE water -- a loss rate, a mass flux -- where whole regions dry at once and sit untouched, with
-// stale values in the reference's other buffer, for as long as they stay dry.
-static bool pair_exact(const hp_domain* d)
-{
-	if (d->desc.math_mode == HP_MATH_STRICT) return true;
-	static const int forced = std::getenv("HP_PAIR_EXACT") ? (std::atoi(std::getenv("HP_PAIR_EXACT")) != 0 ? 1 : 0) : -1;
-	if (forced >= 0) return forced != 0;
-	for (const Boundary& b : d->bdy)
-		if ((b.kind == BDY_UNIFORM && b.definition == HP_UNIFORM_LOSS_RATE) || (b.kind == BDY_GRIDDED && b.definition == HP_GRIDDED_MASS_FLUX)) return true;
-	return false;
-}
 static int pair_stamps_alloc(hp_domain* d)
 {
-	if (!pair_exact(d) || d->z_state) return HP_OK;
+	if (!pair_exact(plan_domain(d), plan_knobs()) || d->z_state) return HP_OK;
 	const size_t rec = (size_t)4 * d->esize + 16;                         // stamp_rec<T>(): the state, then the launch's number
 	HIP_TRY(hipMalloc(&d->z_state, d->cells * rec));
 	HIP_TRY(hipMalloc((void**)&d->haz_words, 64));
@@ -682,12 +587,7 @@ static int pair_stamps_alloc(hp_domain* d)
 // Still records (hp_kernels.hpp: StillRec): a tile of a FAST fp64 pair launch whose stencil the launch before recorded as one still state,
 // found as it was left, is skipped.  That holds only while nothing else writes either state buffer (or the bed) between the two launches:
 // every such writer says so (hp_facts.hpp: buffers_written_outside), and so does every pair launch that does not write records itself
-// (pair_launched).  HP_PAIR_SKIP=0: no records, nothing skipped (A/B runs).
-static bool pair_skip_enabled()
-{
-	static const bool v = !(std::getenv("HP_PAIR_SKIP") && std::atoi(std::getenv("HP_PAIR_SKIP")) == 0);
-	return v;
-}
+// (pair_launched).  HP_PAIR_SKIP=0: no records, nothing skipped (A/B runs; hp_plan.hpp: pair_records).
 static int still_rec_alloc(hp_domain* d, const int windows)
 {
 	const size_t slots = (size_t)windows * (size_t)d->desc.rows;
@@ -728,23 +628,23 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 		lo = south ? d->ghost_rows : 1;
 		hi = d->desc.rows - (north ? d->ghost_rows : 1);
 	} else launch_rows(d, 1, lo, hi);
-	// (STRICT: 12-row tiles -- its live tiles cost 1300 instructions per row and stage, and a 24-row one is what the launch waits for at its
-	// end: S-DAM 4096^2 0.275 ms per iteration at 24 rows, 0.2645 at 12, 0.281 at 8; profiles/r06i_strict_pair_tile_sweep.txt)
-	const int rseg2 = (d->desc.math_mode == HP_MATH_STRICT && !march2_rseg_forced()) ? std::min(d->tiling.march2_rseg, 12) : d->tiling.march2_rseg;
+	const PlanDomain pd = plan_domain(d);
+	const PlanKnobs& knobs = plan_knobs();
+	const int rseg2 = pair_tile_rows(pd, knobs, d->tiling.march2_rseg);    // (STRICT: 12-row tiles)
 	if (!make_tile_map(launch_knobs(), lo, hi, 1, PART_ALL, (int)((p.cols - 2 + MARCH2_COLS - 1) / MARCH2_COLS), rseg2, rseg2, 0, tm, blocks, rseg2,
 	                   0, d->own_lo, d->own_hi, d->tiling.march2_nbands))
 		return HP_ERR_STATE;
-	if (blocks > tail_limit()) return HP_ERR_STATE;                      // (the caller falls back to single iterations)
+	if (blocks > tail_limit(knobs)) return HP_ERR_STATE;                 // (the caller falls back to single iterations)
 	d->tail_want = true; d->tail_allowed = true; d->push_now = strip;    // (strip: the final rows of the edge ranges leave with the launch)
 	// single domain: the second iteration prices the primary buffer (1); a strip: ... and every rank reduces, through the mailboxes,
 	// whose round is also the hand-over of the rows (7; fixed timestep: the round alone, 4) -- step_begin_impl's `fresh`
 	d->tail_fresh = strip ? (d->desc.dynamic_dt ? 7 : 4) : (d->desc.dynamic_dt ? 1 : 0);
 	d->tail_done = false;
 	LaunchTail<T> tail;
-	const int kind = make_tail<T>(d, blocks, PART_ALL, d->stream, tail_limit(), tail);
+	const int kind = make_tail<T>(d, blocks, PART_ALL, d->stream, tail_limit(knobs), tail);
 	d->tail_want = false; d->tail_allowed = false; d->push_now = false;
 	if (kind != (strip ? 2 : 1)) return HP_ERR_STATE;
-	const bool bdy = !d->bdy.empty();
+	const bool bdy = pd.has_bdy;
 	int rc;
 	if ((rc = pair_stamps_alloc(d)) != HP_OK) return rc;
 	bool in_place = false;
@@ -755,16 +655,15 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	tail.pair = bdy ? 2 : 1;
 	tail.bdy_flag = bdy && followed ? 1 : 0;
 	PairAux<T> aux{};
-	const bool exact = pair_exact(d) && d->z_state != nullptr;
+	const bool exact = pair_exact(pd, knobs) && d->z_state != nullptr;    // (the stamps' buffers: allocated just above, or not)
 	if (exact) aux.stamps = StampBufs<T>{(char*)d->z_state, d->haz_words};
 	aux.prev_gen = d->facts->other_stale ? d->pair_gen : 0u;              // `src` was written by a pair launch: its stamps apply
 	aux.gen = ++d->pair_gen;
 	if (aux.gen == 0) aux.gen = ++d->pair_gen;                            // (0 means "no launch")
 	aux.list = (const AreaBdyList<T>*)d->fused_list; aux.fuse_next = bdy && followed ? 1 : 0; aux.in_place = in_place ? 1 : 0;
 	aux.truncated = (d->desc.quirks & HP_QUIRK_BDY_TRUNCATED) != 0 ? 1 : 0;
-	// still records: the instantiations that take still runs on a single domain (FAST fp64, no area boundaries, no stamps) -- this launch
-	// writes the half the launch before did not, and reads that one if nothing has written a state buffer since (still_rec_valid)
-	const bool recs = sizeof(T) == 8 && pair_skip_enabled() && !strip && !bdy && !exact && d->desc.math_mode != HP_MATH_STRICT && rseg2 <= 32;
+	// still records: this launch writes the half the launch before did not, and reads that one if nothing has written a state buffer since
+	const bool recs = pair_records(pd, knobs, strip, exact, rseg2);
 	if (recs) {
 		if ((rc = still_rec_alloc(d, tm.nstrips)) != HP_OK) return rc;
 		StillRec* const base = (StillRec*)d->still_rec;
@@ -858,11 +757,8 @@ static int snapshot_take(hp_domain* d, void* state, void* scalars, const int fir
 int dispatch_begin(hp_domain* d)
 {
 	d->facts.buffers_written_outside();                                   // (a single iteration writes the other buffer, its boundaries the current one)
-	// after iteration pairs the non-current buffer is out of date; K1 brings it up to date by itself (its FILL flag: every cell of the
-	// launch's rows is stored), any other kernel gets the device copy first
-	static const bool fill_enabled = !(std::getenv("HP_FILL_AFTER_PAIRS") && std::atoi(std::getenv("HP_FILL_AFTER_PAIRS")) == 0);
-	// (exact pairs: the device copy, then the stamps on top -- repair_other_buffer -- so that K1 needs no knowledge of them)
-	const bool fill = fill_enabled && d->facts->other_stale && d->desc.scheme == HP_SCHEME_GODUNOV && d->desc.kernel != HP_KERNEL_BASIC && !(pair_exact(d) && d->z_state);
+	// after iteration pairs the non-current buffer is out of date: K1's FILL flag, or the device copy first
+	const bool fill = fill_wanted(plan_domain(d), d->facts, plan_knobs());
 	if (!fill) { const int rc0 = repair_other_buffer(d); if (rc0 != HP_OK) return rc0; }
 	d->fill_now = fill;
 	const bool strict = d->desc.math_mode == HP_MATH_STRICT;
@@ -1357,32 +1253,8 @@ namespace {
 // shared-reciprocal kernels, the flag word copied to pinned memory behind the last launch.  The next entry into the library
 // (check_domain) waits for the batch, looks at the word and, if it is raised, puts the snapshot back and runs the same
 // iterations with the plain kernels.  Cost of the snapshot: two device copies of the state per batch (0.45 ms at 4096^2, i.e.
-// one iteration's worth per batch); HP_STRICT_SPECULATE=1 switches it on (see spec_wanted for why it is off by default),
+// one iteration's worth per batch); HP_STRICT_SPECULATE=1 switches it on (see hp_plan.hpp: spec_wanted for why it is off by default),
 // HP_STRICT_SPEC_FORCE=k pretends every k-th batch raised the word (tests).
-constexpr uint32_t SPEC_MIN = 8;
-bool spec_wanted(const hp_domain* d, uint32_t n)
-{
-	// OPT-IN (HP_STRICT_SPECULATE=1).  Measured with the rigorous flag (profiles/r04j_strict_lines_*): the Godunov kernel gains 2-3 %
-	// (S-DAM 4096^2 0.490 -> 0.479 ms, S-RAIN 0.716 -> 0.697), the MUSCL-Hancock kernel LOSES 9-13 % (0.580 -> 0.657, 1.069 -> 1.164):
-	// the denominator-side v_div_scale + compare that make the detection exact cost most of what the shared reciprocal saves
-	// (without any detection the same kernels run at 0.426 / 0.657 / 0.518 / 0.926 ms).  Not worth a snapshot per batch by default.
-	static const bool enabled = std::getenv("HP_STRICT_SPECULATE") && std::atoi(std::getenv("HP_STRICT_SPECULATE")) != 0;
-	// Not with FUSED area boundaries (round 5).  The speculative flavour of the fused kernel with its own tail block is the engine's
-	// largest instantiation -- 168 VGPRs with 58-66 of them spilled and 103-114 spilled SGPRs -- and what the compiler made of it
-	// stopped being the plain kernel's arithmetic when an unrelated flag was added to the kernel (deterministic, relative 1e-7 ...
-	// 1e-4, no word raised; the same source built for two waves per SIMD, without the vector spills, is exact again:
-	// profiles/r05fg_spec_fused_tail_miscompare.txt).  A 2-3 % experiment is not worth an instantiation that only holds while the
-	// register allocator is lucky: such domains run the plain STRICT kernels.
-#ifdef HP_KEEP_SPEC_FUSED
-	const bool fusable_ok = true;
-#else
-	const bool fusable_ok = !d->fusable;
-#endif
-	// Never with link groups: the batch that is queued again after a raised word would count their records twice.  Nor with an
-	// infiltration: it would add to F twice.
-	return enabled && n >= SPEC_MIN && d->desc.math_mode == HP_MATH_STRICT && d->desc.precision == 8 && !d->comm && fusable_ok && !d->links.groups && !d->soil.on &&
-	       d->desc.kernel != HP_KERNEL_BASIC && (d->desc.scheme == HP_SCHEME_GODUNOV || d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK);
-}
 int spec_begin(hp_domain* d)
 {
 	const size_t bytes = d->cells * 4 * d->esize, sc_bytes = sizeof(Scalars<double>);
@@ -1410,11 +1282,6 @@ int spec_begin(hp_domain* d)
 // lies near iteration 1000 and the engine ran pairs until the sample of iteration 1750, 9 % behind single iterations all the while;
 // now, in batches of 250, it switches in the batch that contains the crossover: tools/strict_tuner_probe.py, profiles/r06ak_*.  A sample costs one copy of the state and six iterations in the slower flavour: 0.1-0.2 % at this period.)
 // HP_PAIR_TUNE=0: always pairs where eligible; HP_PAIR_TUNE_PERIOD=n: iterations between samples.
-static bool tuner_on(const hp_domain* d)
-{
-	static const bool enabled = !(std::getenv("HP_PAIR_TUNE") && std::atoi(std::getenv("HP_PAIR_TUNE")) == 0);
-	return enabled && d->desc.math_mode == HP_MATH_STRICT && two_step_mode() != 1;
-}
 static int tuner_poll(hp_domain* d)
 {
 	if (d->tune_phase == 1 && hipEventQuery(d->tune_ev[3]) == hipSuccess) {
@@ -1448,15 +1315,15 @@ int run_single(hp_domain* d, const bool followed)
 int run_iterations(hp_domain* d, uint32_t n_iterations)
 {
 	int rc;
-	const bool tune = tuner_on(d);
+	const bool tune = tuner_on(plan_domain(d), plan_knobs());
 	if (tune && (rc = tuner_poll(d)) != HP_OK) return rc;
 	// (partial uploads since the last look: the rings are compared once, before the first pair_eligible -- blocks)
-	if (d->facts->rings_differ && !d->facts->rings_checked && n_iterations >= 2 && pairs_possible(d) && (rc = rings_really_differ(d)) != HP_OK) return rc;
+	if (d->facts->rings_differ && !d->facts->rings_checked && n_iterations >= 2 && pairs_possible(plan_domain(d), plan_knobs()) && (rc = rings_really_differ(d)) != HP_OK) return rc;
 	for (uint32_t i = 0; i < n_iterations; ++i) {
 		if (tune && d->tune_phase != 0 && (i & 15u) == 15u && (rc = tuner_poll(d)) != HP_OK) return rc;   // (two event queries: host time, behind the queue)
 		// (STRICT) a sample: three pairs, then six single iterations -- the first pair and the first two single iterations warm the
 		// kernel's code and are not timed, the rest are bracketed by events
-		if (tune && d->tune_phase == 0 && i + 12 <= n_iterations && !d->facts->rings_differ && pair_eligible(d)) {
+		if (tune && d->tune_phase == 0 && i + 12 <= n_iterations && !d->facts->rings_differ && pair_eligible(plan_domain(d), d->facts, plan_knobs())) {
 			for (hipEvent_t& e : d->tune_ev) if (!e) HIP_TRY(hipEventCreate(&e));
 			if ((rc = pair_stamps_alloc(d)) != HP_OK) return rc;           // (the first pair's allocation and its memset are not the pair's price)
 			rc = run_pair(d, false, true);
@@ -1476,7 +1343,7 @@ int run_iterations(hp_domain* d, uint32_t n_iterations)
 			}
 			if (rc != HP_ERR_STATE) return rc;
 		}
-		if (i + 2 <= n_iterations && (!tune || d->tune_prefer_pairs) && pair_eligible(d)) {
+		if (i + 2 <= n_iterations && (!tune || d->tune_prefer_pairs) && pair_eligible(plan_domain(d), d->facts, plan_knobs())) {
 			rc = run_pair(d, false, i + 2 < n_iterations);
 			if (rc == HP_OK) { ++i; continue; }
 			if (rc != HP_ERR_STATE) return rc;                 // (HP_ERR_STATE: not launchable as a pair -- single iterations)
@@ -1518,7 +1385,7 @@ int hp_step_batch(hp_domain_t* d, uint32_t n_iterations)
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "inside a split step");
-	const bool speculate = spec_wanted(d, n_iterations);
+	const bool speculate = spec_wanted(plan_domain(d), plan_knobs(), n_iterations);
 	if (speculate && (rc = spec_begin(d)) != HP_OK) return rc;
 	rc = run_iterations(d, n_iterations);
 	if (speculate) {
@@ -1733,17 +1600,12 @@ int strip_allreduce_max(hp_domain* d, bool first_of_batch)
 {
 	// (measurement knob, tools/strong_probe.py: a communicator of ONE rank normally skips the reduction; with the knob it goes
 	// through it -- the library's all-reduce or its own mailbox -- so that the cost of the step can be timed on one GPU)
-	static const bool lonely_too = std::getenv("HP_STRIP_REDUCE_ALWAYS") && std::atoi(std::getenv("HP_STRIP_REDUCE_ALWAYS")) != 0;
-	if (d->comm_world <= 1 && !lonely_too) return HP_OK;
+	if (d->comm_world <= 1 && !plan_knobs().strip_reduce_always) return HP_OK;
 	if (!d->desc.dynamic_dt) {
 		if (d->peer_direct) d->adv_fresh = 4;                          // fixed timestep: nothing to reduce, the round still hands the rows over
 		return HP_OK;
 	}
-	const bool q1 = (d->desc.quirks & HP_QUIRK_CFL_READS_PRIMARY) != 0, muscl = d->desc.scheme == HP_SCHEME_MUSCL_HANCOCK;
-	const bool basic = d->desc.kernel == HP_KERNEL_BASIC && d->desc.scheme == HP_SCHEME_GODUNOV;
-	const bool dst_is_primary = d->facts->use_alt == 1;
-	const bool everyone = muscl || !q1 || dst_is_primary || basic || d->strip_any_bdy || (first_of_batch && d->strip_any_full);
-	if (!everyone) {
+	if (!strips_reduce_everyone(plan_domain(d), d->facts, first_of_batch)) {
 		if (d->adv_fresh) return fail(HP_ERR_STATE, "a strip priced a new maximum on an iteration the other ranks do not reduce "
 		                                            "(boundaries or uploads changed inside a batch?)");
 		if (d->peer_direct) d->adv_fresh = 4;                          // a round all the same: it is what hands the ghost rows over (PeerPush)
@@ -1768,7 +1630,7 @@ int strip_allreduce_max(hp_domain* d, bool first_of_batch)
 // calls, which nothing forces to be the same on every rank; the ping-pong phase and the ghost-row state must be.
 int strip_handshake(hp_domain* d)
 {
-	d->strip_any_bdy = !d->bdy.empty() && d->desc.scheme != HP_SCHEME_MUSCL_HANCOCK;
+	d->strip_any_bdy = boundaries_applied(plan_domain(d));
 	d->strip_any_full = d->facts->need_full_reduce;
 	d->strip_pairs = false;
 	if (d->comm_world <= 1) return HP_OK;
@@ -1777,7 +1639,7 @@ int strip_handshake(hp_domain* d)
 	const bool broken = peer_error_check(d) != HP_OK;
 	// (element 0: 3 = this rank's exchange is broken, 1 = it has boundary conditions, 0.5 = it has none but cannot run iteration
 	// pairs, 0 = it can: the maximum over the ranks says what ALL of them may do)
-	const double mine[8] = {broken ? 3.0 : (d->strip_any_bdy ? 1.0 : (strip_pairs_possible_here(d) ? 0.0 : 0.5)), d->strip_any_full ? 1.0 : 0.0, (double)d->facts->use_alt, -(double)d->facts->use_alt,
+	const double mine[8] = {broken ? 3.0 : (d->strip_any_bdy ? 1.0 : (strip_pairs_possible_here(plan_domain(d), d->facts, plan_knobs()) ? 0.0 : 0.5)), d->strip_any_full ? 1.0 : 0.0, (double)d->facts->use_alt, -(double)d->facts->use_alt,
 	                        (double)d->facts->ghost_valid, -(double)d->facts->ghost_valid, (double)d->ghost_rows, -(double)d->ghost_rows};
 	double all[8];
 	char* slot = (char*)d->cfl_slot + (size_t)SLOT_HANDSHAKE * d->esize;
@@ -2318,7 +2180,7 @@ int hp_pair_stats(hp_domain_t* d, uint64_t out[12])
 	if (!out) return fail(HP_ERR_INVALID, "out == NULL");
 	out[0] = d->pairs; out[1] = d->pair_cold_starts; out[2] = out[3] = 0;
 	HIP_TRY(hipStreamSynchronize(d->stream));
-	if (tuner_on(d) && (rc = tuner_poll(d)) != HP_OK) return rc;
+	if (tuner_on(plan_domain(d), plan_knobs()) && (rc = tuner_poll(d)) != HP_OK) return rc;
 	out[4] = d->tune_samples; out[5] = d->tune_switches; out[6] = d->tune_prefer_pairs ? 1 : 0;
 	out[7] = d->tune_single_ms > 0.f ? (uint64_t)(1000.0 * d->tune_pair_ms / d->tune_single_ms) : 0;
 	out[8] = out[9] = out[10] = out[11] = 0;

@@ -27,7 +27,7 @@ BUDGET = os.path.join(CSRC, "resource_budget.json")
 @pytest.fixture(scope="module")
 def built():
     """The library and its usage file, newer than every source (a stale binary would be checked against the wrong table)."""
-    sources = [os.path.join(CSRC, f) for f in ("hp_engine.hip", "hp_domain.hpp", "hp_facts.hpp", "hp_observers.hpp", "hp_actors.hpp", "hp_kernels.hpp", "hp_tiling.hpp",
+    sources = [os.path.join(CSRC, f) for f in ("hp_engine.hip", "hp_domain.hpp", "hp_facts.hpp", "hp_plan.hpp", "hp_observers.hpp", "hp_actors.hpp", "hp_kernels.hpp", "hp_tiling.hpp",
                                               "hp_output.hpp", "hp_peaks.hpp", "hp_probes.hpp", "hp_zones.hpp", "hp_overview.hpp", "hp_sparse.hpp", "hp_bed.hpp",
                                               "hp_links.hpp", "hp_math.hpp", "hp_crmath.h", "../../include/hipims_mi.h", "Makefile")]     # the Makefile's prerequisites
     newest = max(os.path.getmtime(f) for f in sources)
