@@ -1,10 +1,10 @@
 // hp_actors.hpp -- the actors of a domain, host side: what changes the state from outside the flux kernels.  Three kinds: the
 // boundaries (uniform, gridded and cell: hp_kernels.hpp), the link groups (hp_links.hpp) and the infiltration (hp_soil.hpp) among them,
-// and the bed shapes (hp_bed.hpp).
+// the bed shapes (hp_bed.hpp), and the tracer that rides on the water they move (hp_tracer.hpp).
 // Here: their entry points of include/hipims_mi.h, the boundary pass the engine queues in front of an iteration (apply_boundaries)
 // and the choice of what the flux kernel carries of it instead (refresh_fusable), and what hp_state_save / hp_state_restore /
 // hp_domain_destroy do for the bed, the links and the infiltration (*_save, *_restore, *_destroy; actors_* calls them in order).  Their
-// state is declared in hp_domain.hpp (Boundary, BedShapes, LinkStore, SoilStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
+// state is declared in hp_domain.hpp (Boundary, BedShapes, LinkStore, SoilStore, TracerStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
 // stays one translation unit.
 #pragma once
 #include "hp_domain.hpp"
@@ -17,6 +17,7 @@ namespace {
 static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, "hp_bed_*_t layout");
 static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
 static_assert(sizeof(hp_soil_class_t) == 32 && sizeof(hp_infiltration_desc_t) == 32, "hp_soil_class_t / hp_infiltration_desc_t layout");
+static_assert(sizeof(hp_tracer_desc_t) == 16, "hp_tracer_desc_t layout");
 
 // ---- the boundaries ----
 // an area boundary as the kernels read it: the stand-alone pass and the fused one are handed the same descriptor
@@ -87,6 +88,7 @@ template <typename T> int refresh_fusable_t(hp_domain* d)
 {
 	d->fusable = false;
 	if (!plan_knobs().fuse_bdy || d->desc.scheme != HP_SCHEME_GODUNOV || d->desc.kernel == HP_KERNEL_BASIC) return HP_OK;
+	if (d->tracer.on) return HP_OK;                                           // its step stands behind EVERY boundary: none rides in the flux kernel
 	if (d->bdy.empty() || d->bdy.size() > (size_t)FUSED_BDY_MAX) return HP_OK;
 	AreaBdyList<T> list;
 	list.count = 0;
@@ -270,26 +272,84 @@ int soil_restore(hp_domain* d)
 	return HP_OK;
 }
 
-// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the three ----
+// ---- the tracer (hp_tracer.hpp): its launches in front of the flux kernel, and what a checkpoint does for M ----
+// One iteration's tracer: the sources onto the current M, then the step from it into the other buffer, which becomes the current one.
+// `source`: the state buffer the flux launch of this iteration reads (the boundaries have been applied to it)
+template <typename T> int apply_tracer(hp_domain* d, const void* source)
+{
+	TracerStore& R = d->tracer;
+	const Params<T> p = make_params<T>(d);
+	if (R.sources && R.lists.count)
+		hipLaunchKernelGGL(tracer_sources<T>, dim3(stream_blocks((size_t)R.lists.count)), dim3(256), 0, d->stream, p, (const Scalars<T>*)d->scalars, R.lists, R.M[R.phase]);
+	const dim3 block(64, 4), grid((unsigned)((p.cols + 63) / 64), (unsigned)((p.rows + 3) / 4));
+	hipLaunchKernelGGL(tracer_step<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
+	                   (const double*)R.M[R.phase], R.M[R.phase ^ 1]);
+	HIP_TRY(hipGetLastError());
+	R.phase ^= 1;
+	++R.iterations;
+	return HP_OK;
+}
+void tracer_destroy(hp_domain* d)
+{
+	TracerStore& R = d->tracer;
+	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.block); hipFree(R.saved);
+	R.M[0] = R.M[1] = nullptr; R.block = nullptr; R.saved = nullptr;
+}
+// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+int tracer_save_reserve(hp_domain* d)
+{
+	TracerStore& R = d->tracer;
+	if (!R.on || R.saved) return HP_OK;
+	return alloc_or_fail((void**)&R.saved, d->cells * sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
+}
+int tracer_save(hp_domain* d)
+{
+	TracerStore& R = d->tracer;
+	R.saved_taken = true;
+	R.saved_epoch = R.epoch;
+	R.saved_iterations = R.iterations;
+	if (R.on) HIP_TRY(hipMemcpyAsync(R.saved, R.M[R.phase], d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+// (the phase names a buffer, nothing more: the saved M goes into the buffer that is current now, and the counter comes back)
+int tracer_restore(hp_domain* d)
+{
+	TracerStore& R = d->tracer;
+	if (!R.saved_taken) return HP_OK;
+	if (R.saved_epoch != R.epoch) {                                           // (the infiltration's rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: the tracer was enabled or disabled after the state was saved: the tracer is left as it is");
+		return HP_OK;
+	}
+	if (R.on) {
+		HIP_TRY(hipMemcpyAsync(R.M[R.phase], R.saved, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
+		R.iterations = R.saved_iterations;
+	}
+	return HP_OK;
+}
+
+// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the four ----
 int actors_save_reserve(hp_domain* d)
 {
 	int rc = bed_save_reserve(d);
 	if (rc == HP_OK) rc = links_save_reserve(d);
-	return rc != HP_OK ? rc : soil_save_reserve(d);
+	if (rc == HP_OK) rc = soil_save_reserve(d);
+	return rc != HP_OK ? rc : tracer_save_reserve(d);
 }
 int actors_save(hp_domain* d)
 {
 	int rc = bed_save(d);
 	if (rc == HP_OK) rc = links_save(d);
-	return rc != HP_OK ? rc : soil_save(d);
+	if (rc == HP_OK) rc = soil_save(d);
+	return rc != HP_OK ? rc : tracer_save(d);
 }
 int actors_restore(hp_domain* d)
 {
 	int rc = bed_restore(d);
 	if (rc == HP_OK) rc = links_restore(d);
-	return rc != HP_OK ? rc : soil_restore(d);
+	if (rc == HP_OK) rc = soil_restore(d);
+	return rc != HP_OK ? rc : tracer_restore(d);
 }
-void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); }
+void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); tracer_destroy(d); }
 
 } // namespace
 
@@ -531,6 +591,7 @@ int hp_boundary_add_links(hp_domain_t* d, const hp_link_t* links, uint64_t count
 	// argument checks first: none of them touches the device (hp_links.hpp: validate_links)
 	const std::string who = "hp_boundary_add_links";
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (d->tracer.on) return fail(HP_ERR_UNSUPPORTED, who + ": the domain carries a tracer, and the water a link moves would have to carry its share of it");
 	LinkStore& L = d->links;
 	const uint64_t cols = (uint64_t)d->desc.cols, reach = (uint64_t)stencil_reach(d->desc);
 	std::vector<uint64_t> taken;
@@ -605,6 +666,7 @@ int hp_boundary_add_infiltration(hp_domain_t* d, const hp_infiltration_desc_t* d
 	uint64_t pervious = 0;
 	std::string why;
 	if (!validate_infiltration(desc, (uint64_t)d->cells, pervious, why)) return fail(HP_ERR_INVALID, why);
+	if (d->tracer.on) return fail(HP_ERR_UNSUPPORTED, who + ": the domain carries a tracer, and the water the soil takes would have to carry its share of it");
 	// a strip with two reaches of ghost rows holds the outer one on every second iteration only: F there would drift from its owner's
 	if (d->ghost_rows > stencil_reach(d->desc) && (d->desc.row_offset > 0 || d->desc.row_offset + d->desc.rows < d->desc.global_rows))
 		return fail(HP_ERR_UNSUPPORTED, who + ": this strip stores two reaches of ghost rows, the outer one valid on every second iteration only: "
@@ -666,6 +728,171 @@ int hp_infiltration_info(hp_domain_t* d, uint32_t* classes, uint64_t* pervious_c
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	if (classes) *classes = d->soil.classes;
 	if (pervious_cells) *pervious_cells = d->soil.pervious;
+	return HP_OK;
+}
+
+// ---- the tracer (hp_tracer.hpp) ----
+int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc)
+{
+	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_enable)
+	const std::string who = "hp_tracer_enable";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	std::string why;
+	if (!validate_tracer_enable(desc, (uint64_t)d->cells, why)) return fail(HP_ERR_INVALID, why);
+	if (d->desc.scheme != HP_SCHEME_GODUNOV)
+		return fail(HP_ERR_UNSUPPORTED, who + ": the tracer takes its face fluxes from the Godunov scheme's face solve; this domain runs another scheme");
+	if (d->desc.global_rows != d->desc.rows)
+		return fail(HP_ERR_UNSUPPORTED, who + ": this domain is a strip of a larger grid: the tracer's ghost rows would need an exchange of their own");
+	if (d->links.groups) return fail(HP_ERR_UNSUPPORTED, who + ": the domain has link groups, and the water a link moves would have to carry its share of the tracer");
+	if (d->soil.on) return fail(HP_ERR_UNSUPPORTED, who + ": the domain has an infiltration, and the water the soil takes would have to carry its share of the tracer");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	TracerStore& R = d->tracer;
+	if (R.on) return fail(HP_ERR_STATE, who + ": the domain has a tracer already (hp_tracer_disable removes it)");
+	// everything it needs first: if any of it cannot be had, the domain stays as it is
+	const size_t bytes = d->cells * sizeof(double);
+	double* m0 = nullptr;
+	double* m1 = nullptr;
+	if ((rc = alloc_or_fail((void**)&m0, bytes, who + ": cannot allocate the tracer: ")) != HP_OK) return rc;
+	if ((rc = alloc_or_fail((void**)&m1, bytes, who + ": cannot allocate the tracer's second buffer: ")) != HP_OK) { hipFree(m0); return rc; }
+	hipError_t e = desc->initial ? hipMemcpyAsync(m0, desc->initial, bytes, hipMemcpyHostToDevice, d->stream) : hipMemsetAsync(m0, 0, bytes, d->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(m1, 0, bytes, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (the caller's raster is free on return)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(m0); hipFree(m1);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the raster: " + hipGetErrorString(e));
+	}
+	d->facts.boundaries_or_bed_changed();
+	R.on = true;
+	R.M[0] = m0; R.M[1] = m1;
+	R.phase = 0;
+	R.iterations = 0;
+	++R.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_tracer_sources_clear(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	TracerStore& R = d->tracer;
+	if (!R.sources) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_sources_clear between hp_step_begin and hp_step_end");
+	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (queued iterations still use the lists)
+	hipFree(R.block);
+	R.block = nullptr;
+	R.lists = TracerLists{};
+	R.sources = 0;
+	R.host = TracerHost{};
+	return HP_OK;
+}
+
+int hp_tracer_disable(hp_domain_t* d)
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	TracerStore& R = d->tracer;
+	if (!R.on) return HP_OK;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_disable between hp_step_begin and hp_step_end");
+	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (queued iterations still use the buffers)
+	tracer_destroy(d);
+	d->facts.boundaries_or_bed_changed();
+	R.on = false;
+	R.lists = TracerLists{};
+	R.sources = 0;
+	R.host = TracerHost{};
+	R.iterations = 0;
+	++R.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries)
+{
+	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_source)
+	const std::string who = "hp_tracer_add_source";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	TracerStore& R = d->tracer;
+	std::vector<uint64_t> listed;
+	std::string why;
+	if (!validate_tracer_source(cells, count, series, entries, R.host, (uint64_t)d->desc.cols, (uint64_t)d->desc.rows, listed, why)) return fail(HP_ERR_INVALID, why);
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!R.on) return fail(HP_ERR_STATE, who + ": the domain has no tracer (hp_tracer_enable)");
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	TracerHost next = R.host;
+	next.cells.insert(next.cells.end(), cells, cells + count);
+	next.source_of.resize(next.cells.size(), (unsigned char)R.sources);
+	next.series.insert(next.series.end(), series, series + 2 * (size_t)entries);
+	next.series_off.push_back((unsigned)(next.series.size() / 2));
+	const unsigned sources = R.sources + 1;
+	// the new block first: if it cannot be had, the domain keeps the sources it has
+	const TracerLayout l = tracer_layout(next.cells.size(), next.series.size() / 2, sources);
+	void* fresh = nullptr;
+	if ((rc = alloc_or_fail(&fresh, l.bytes, who + ": cannot allocate the lists: ")) != HP_OK) return rc;
+	const std::vector<unsigned char> image = tracer_image(l, next);
+	hipError_t e = hipMemcpyAsync(fresh, image.data(), l.bytes, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (queued iterations still read the old block; `image` goes with this call)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(fresh);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the lists: " + hipGetErrorString(e));
+	}
+	hipFree(R.block);
+	R.block = fresh;
+	char* b = (char*)fresh;
+	R.lists.cells = (const unsigned long long*)(b + l.cells);
+	R.lists.source_of = (const unsigned char*)(b + l.source_of);
+	R.lists.series = (const double*)(b + l.series);
+	R.lists.series_off = (const unsigned*)(b + l.series_off);
+	R.lists.count = next.cells.size();
+	R.lists.sources = sources;
+	R.sources = sources;
+	next.listed.swap(listed);
+	R.host = std::move(next);
+	return HP_OK;
+}
+
+int hp_tracer_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!raster) return fail(HP_ERR_INVALID, "hp_tracer_read: raster == NULL");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	if (!d->tracer.on) return fail(HP_ERR_STATE, "hp_tracer_read: the domain has no tracer");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_read between hp_step_begin and hp_step_end");
+	if (nrows == 0) return HP_OK;
+	const size_t cols = (size_t)d->desc.cols;
+	HIP_TRY(hipMemcpyAsync(raster, d->tracer.M[d->tracer.phase] + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_tracer_write(hp_domain_t* d, const double* raster, int64_t row0, int64_t nrows)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (!raster) return fail(HP_ERR_INVALID, "hp_tracer_write: raster == NULL");
+	int rc = check_rows(d, row0, nrows);
+	if (rc != HP_OK) return rc;
+	if ((rc = check_domain(d)) != HP_OK) return rc;
+	if (!d->tracer.on) return fail(HP_ERR_STATE, "hp_tracer_write: the domain has no tracer");
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_write between hp_step_begin and hp_step_end");
+	if (nrows == 0) return HP_OK;
+	const size_t cols = (size_t)d->desc.cols;
+	HIP_TRY(hipMemcpyAsync(d->tracer.M[d->tracer.phase] + (size_t)row0 * cols, raster, (size_t)nrows * cols * sizeof(double), hipMemcpyHostToDevice, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (the caller's raster is free on return)
+	return HP_OK;
+}
+
+int hp_tracer_info(hp_domain_t* d, uint64_t* iterations, uint32_t* sources, uint64_t* source_cells)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (iterations) *iterations = d->tracer.on ? d->tracer.iterations : 0;
+	if (sources) *sources = d->tracer.sources;
+	if (source_cells) *source_cells = (uint64_t)d->tracer.host.cells.size();
 	return HP_OK;
 }
 

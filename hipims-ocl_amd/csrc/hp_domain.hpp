@@ -2,7 +2,8 @@
 // the map of its pinned host block and the helpers more than one part uses (with_real, alloc_or_fail, upload_or_fail, stream_blocks,
 // stencil_reach, state_replaced).  Internal to the library's one translation unit: hp_engine.hip includes it, then hp_observers.hpp
 // (the code of the four observers whose state is declared here, and of the RecordLog two of them share) and hp_actors.hpp (the code
-// of the boundaries, the link groups and the infiltration among them, and the moving bed: Boundary, LinkStore, SoilStore and BedShapes below).
+// of the boundaries, the link groups and the infiltration among them, the moving bed and the tracer: Boundary, LinkStore, SoilStore,
+// BedShapes and TracerStore below).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_facts.hpp"
@@ -16,6 +17,7 @@
 #include "hp_bed.hpp"
 #include "hp_links.hpp"
 #include "hp_soil.hpp"
+#include "hp_tracer.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
 #include <algorithm>
@@ -191,6 +193,24 @@ struct SoilStore {
 	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
+// the tracer (hp_tracer.hpp; hp_tracer_enable): the solute mass per unit area M, its two buffers and the sources' lists.  Nothing of it
+// exists while the domain has none
+struct TracerStore {
+	bool             on = false;
+	double*          M[2] = {nullptr, nullptr};       // device: M[phase] is the current M, the other one what the next step writes
+	int              phase = 0;                       // its own, independent of the state's ping-pong
+	uint64_t         iterations = 0;                  // steps since hp_tracer_enable (as restored)
+	void*            block = nullptr;                 // device: the sources' lists (TracerLayout), rewritten by every hp_tracer_add_source
+	TracerLists      lists = {};
+	unsigned         sources = 0;
+	TracerHost       host;
+	uint64_t         epoch = 0;                       // counts enable / disable: a checkpoint's M belongs to one epoch
+	double*          saved = nullptr;                 // hp_state_save's copy of the current M
+	uint64_t         saved_iterations = 0;
+	bool             saved_taken = false;             // a checkpoint exists (with or without a tracer) ...
+	uint64_t         saved_epoch = 0;                 // ... of this epoch
+};
+
 } // namespace
 
 struct hp_domain {
@@ -309,6 +329,7 @@ struct hp_domain {
 	BedShapes        beds;
 	LinkStore        links;
 	SoilStore        soil;
+	TracerStore      tracer;
 };
 
 namespace {
@@ -330,6 +351,7 @@ int check_domain(hp_domain* d);           // (hp_engine.hip: every entry point t
 template <typename T> Params<T> make_params(const hp_domain* d);             // (hp_engine.hip)
 const PlanKnobs& plan_knobs();                                               // (hp_engine.hip: the rules' switches, read from the environment once)
 template <typename T> int apply_boundaries(hp_domain* d, void* target);      // (hp_actors.hpp: the boundaries, in the order added, onto `target`)
+template <typename T> int apply_tracer(hp_domain* d, const void* source);    // (hp_actors.hpp: the tracer's sources and its step on the iteration's source buffer)
 
 // f(T{}) with T = the domain's precision: a launch that differs only in that type is written once
 template <typename F> auto with_real(const hp_domain* d, F&& f) { if (d->desc.precision == 8) return f(double{}); return f(float{}); }

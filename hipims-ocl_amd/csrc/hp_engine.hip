@@ -84,7 +84,7 @@ PlanDomain plan_domain(const hp_domain* d)
 	p.has_tail_words = d->tail_words != nullptr; p.tail_allowed = d->tail_allowed; p.halo_overlap = d->halo_overlap; p.split_now = d->split_now;
 	p.strip_any_bdy = d->strip_any_bdy; p.strip_first = d->strip_first; p.strip_any_full = d->strip_any_full;
 	p.spec_now = d->spec_now; p.has_stamps = d->z_state != nullptr; p.march2_pays = d->tiling.march2_pays;
-	p.has_links = d->links.groups != 0; p.soil_on = d->soil.on;
+	p.has_links = d->links.groups != 0; p.soil_on = d->soil.on; p.tracer_on = d->tracer.on;
 #ifdef HP_KEEP_SPEC_FUSED
 	p.spec_fused_kept = true;                                             // (launch_march: the instantiation kept buildable for study)
 #endif
@@ -420,6 +420,11 @@ template <typename T, bool STRICT> int step_begin_impl(hp_domain* d)
 	if (boundaries_applied(pd)) {
 		d->fork_is_advance = false;
 		if ((rc = apply_boundaries<T>(d, src)) != HP_OK) return rc;
+	}
+	// the tracer: behind every boundary, on the buffer the flux launch is about to read and the timestep its tail block is about to advance
+	if (pd.tracer_on) {
+		d->fork_is_advance = false;
+		if ((rc = apply_tracer<T>(d, src)) != HP_OK) return rc;
 	}
 	// what the launch prices, whether it carries its own tail block, what follows it (hp_plan.hpp)
 	const SinglePlan plan = plan_single(pd, d->facts, plan_knobs());

@@ -56,7 +56,7 @@ struct PlanDomain {
 	bool     spec_now = false;
 	bool     has_stamps = false;               // the stamps' buffers exist (z_state)
 	bool     march2_pays = false;              // hp_tiling.hpp: the pair launch is at least two rounds of blocks at 12-row tiles
-	bool     has_links = false, soil_on = false;
+	bool     has_links = false, soil_on = false, tracer_on = false;
 	bool     spec_fused_kept = false;          // the library was built with -DHP_KEEP_SPEC_FUSED
 };
 
@@ -123,7 +123,9 @@ inline bool pairs_possible_common(const PlanDomain& d, const PlanKnobs& k)
 	// of still water are a copy in STRICT (K1's skip), and a pair copies them at half the bytes.  HP_PAIR_STRICT=0 switches it off.
 	const bool math_ok = d.math_mode == HP_MATH_FAST ||
 	                     (k.pair_strict && !d.has_bdy && !d.has_comm && d.comm_world <= 1 && d.dynamic_dt && !d.spec_now);
-	return d.scheme == HP_SCHEME_GODUNOV && d.kernel != HP_KERNEL_BASIC && math_ok &&
+	// never with a tracer: its step stands between every two iterations, as a link group's or an infiltration's does (those are entries of
+	// the boundary list and so never fusable; the tracer is none, so it is named here)
+	return d.scheme == HP_SCHEME_GODUNOV && d.kernel != HP_KERNEL_BASIC && math_ok && !d.tracer_on &&
 	       bdy_ok && (!d.dynamic_dt || reads_primary(d)) &&
 	       k.launch_tail && d.has_tail_words && d.rows >= 5 && d.cols >= 5;
 }
@@ -189,8 +191,8 @@ inline bool spec_wanted(const PlanDomain& d, const PlanKnobs& k, const uint32_t 
 	// register allocator is lucky: such domains run the plain STRICT kernels.
 	const bool fusable_ok = d.spec_fused_kept || !d.fusable;
 	// Never with link groups: the batch that is queued again after a raised word would count their records twice.  Nor with an
-	// infiltration: it would add to F twice.
-	return k.strict_speculate && n >= SPEC_MIN && d.math_mode == HP_MATH_STRICT && d.precision == 8 && !d.has_comm && fusable_ok && !d.has_links && !d.soil_on &&
+	// infiltration: it would add to F twice.  Nor with a tracer: it would move M twice.
+	return k.strict_speculate && n >= SPEC_MIN && d.math_mode == HP_MATH_STRICT && d.precision == 8 && !d.has_comm && fusable_ok && !d.has_links && !d.soil_on && !d.tracer_on &&
 	       d.kernel != HP_KERNEL_BASIC && (d.scheme == HP_SCHEME_GODUNOV || d.scheme == HP_SCHEME_MUSCL_HANCOCK);
 }
 // The exact mode chooses between pairs and single iterations by measurement (hp_engine.hip: run_iterations, tuner_poll).

@@ -51,7 +51,8 @@ EXPORTS = [
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
     "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info",
-    "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_clear", "hp_boundaries_fused", "hp_set_target_time", "hp_set_time",
+    "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_clear", "hp_boundaries_fused",
+    "hp_tracer_enable", "hp_tracer_disable", "hp_tracer_add_source", "hp_tracer_sources_clear", "hp_tracer_read", "hp_tracer_write", "hp_tracer_info", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
     "hp_stream_halo", "hp_comm_load", "hp_comm_unique_id", "hp_strip_comm_init", "hp_strip_step_batch", "hp_strip_update_timestep",
@@ -207,6 +208,11 @@ def soil_ids(values, what="the soil raster"):
     return np.ascontiguousarray(v.astype(np.uint8))
 
 
+# hp_tracer_desc_t
+class TracerDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("initial", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -283,6 +289,14 @@ def load_library(path: str | None = None):
         lib.hp_boundary_add_infiltration.argtypes = [C.c_void_p, C.POINTER(InfiltrationDesc)]
         lib.hp_infiltration_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_infiltration_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_tracer_enable"):                # (absent from older builds, as above)
+        lib.hp_tracer_enable.argtypes = [C.c_void_p, C.POINTER(TracerDesc)]
+        lib.hp_tracer_disable.argtypes = [C.c_void_p]
+        lib.hp_tracer_add_source.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+        lib.hp_tracer_sources_clear.argtypes = [C.c_void_p]
+        lib.hp_tracer_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -1026,6 +1040,56 @@ class Domain:
         _check(self.lib, self.lib.hp_infiltration_read(self.h, out.ctypes.data, row0, nrows), "hp_infiltration_read")
         self.sync()
         return out
+
+    def tracer_enable(self, initial=None):
+        """The passive tracer (hp_tracer_enable): a solute mass per unit area M, fp64, moved once per iteration by the mass fluxes of
+        the flux kernel's exact face solve, upwinded.  `initial`: [rows, cols] M0 in units * m (row 0 = south), or None for zeros.
+        frontend.Tracer is the same arithmetic on the host, bit for bit."""
+        m0 = None
+        if initial is not None:
+            m0 = np.ascontiguousarray(initial, dtype=np.float64)
+            if m0.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial tracer must be [{self.rows}, {self.cols}]")
+        desc = TracerDesc(C.sizeof(TracerDesc), 0, None if m0 is None else m0.ctypes.data)
+        _check(self.lib, self.lib.hp_tracer_enable(self.h, C.byref(desc)), "hp_tracer_enable")
+
+    def tracer_disable(self):
+        _check(self.lib, self.lib.hp_tracer_disable(self.h), "hp_tracer_disable")
+
+    def tracer_add_source(self, cells, series):
+        """One source (hp_tracer_add_source): `cells` flat ids (y * cols + x) or (x, y) pairs, `series` [(time, mass rate)]: every
+        listed cell receives the rate, interpolated by the bed shapes' rule."""
+        c = np.asarray(cells)
+        if c.ndim == 2:
+            c = c[:, 1].astype(np.uint64) * np.uint64(self.cols) + c[:, 0].astype(np.uint64)
+        c = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1)
+        s = np.ascontiguousarray(series, dtype=np.float64).reshape(-1, 2)
+        _check(self.lib, self.lib.hp_tracer_add_source(self.h, c.ctypes.data if c.size else None, c.size, s.ctypes.data if s.size else None, len(s)),
+               "hp_tracer_add_source")
+
+    def tracer_sources_clear(self):
+        _check(self.lib, self.lib.hp_tracer_sources_clear(self.h), "hp_tracer_sources_clear")
+
+    def tracer_read(self, row0=0, nrows=None):
+        """The current M in units * m, fp64 [nrows, cols] (default: every row of the local array); blocks."""
+        nrows = self.rows - row0 if nrows is None else nrows
+        out = np.zeros((max(0, nrows), self.cols), np.float64)
+        _check(self.lib, self.lib.hp_tracer_read(self.h, out.ctypes.data, row0, nrows), "hp_tracer_read")
+        self.sync()
+        return out
+
+    def tracer_write(self, raster, row0=0):
+        """Replace rows row0 .. of the current M by `raster` [nrows, cols]."""
+        m = np.ascontiguousarray(raster, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != self.cols:
+            raise ValueError(f"the raster must be [nrows, {self.cols}]")
+        _check(self.lib, self.lib.hp_tracer_write(self.h, m.ctypes.data, row0, m.shape[0]), "hp_tracer_write")
+
+    def tracer_info(self):
+        """dict(iterations, sources, source_cells): host counters (all 0 without a tracer)."""
+        n, s, c = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_tracer_info(self.h, C.byref(n), C.byref(s), C.byref(c)), "hp_tracer_info")
+        return dict(iterations=n.value, sources=s.value, source_cells=c.value)
 
     def clear_boundaries(self):
         _check(self.lib, self.lib.hp_boundary_clear(self.h), "hp_boundary_clear")

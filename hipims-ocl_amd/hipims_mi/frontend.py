@@ -121,6 +121,7 @@ class Configuration:
     bed_shapes: list = field(default_factory=list)  # dict(name, cells [(x, y)], target [n], series [m, 2]): <bedShape> elements
     links: list = field(default_factory=list)      # dict(a (x, y), b (x, y), kind, one_way, level, size, coeff, limit): rows of the <links> elements' mapFiles
     soil_classes: list = field(default_factory=list)  # dict(ks, suction, deficit, capacity): rows of the <soilClasses> element's source; the id raster is the "soil" data source
+    tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2]): <tracerSource> elements; the initial M is the "tracer" data source
 
 
 def _params(elem):
@@ -188,6 +189,12 @@ def parse_configuration(xml_path):
     for e in data.findall("soilClasses"):
         cfg.soil_classes = [dict(ks=float(r[0]), suction=float(r[1]), deficit=float(r[2]), capacity=float(r[3]))
                             for r in _read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 4)]
+    # the tracer's sources (no reference counterpart): <tracerSource mapFile="cells.csv" source="rate.csv"/>, mapFile rows x, y; source rows
+    # time, mass rate.  The initial M is the raster <dataSource type="raster" value="tracer" source="m0.asc"/>
+    for e in data.findall("tracerSource"):
+        cells = _read_csv(os.path.join(cfg.source_dir, e.get("mapFile"))).reshape(-1, 2)
+        cfg.tracer_sources.append(dict(cells=[(int(r[0]), int(r[1])) for r in cells],
+                                       series=_read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2)))
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -997,6 +1004,196 @@ class Infiltration:
         for name, mask in masks.items():
             self.branches[name].reshape(-1)[at] += mask
         return int(move.sum())
+
+
+class Tracer:
+    """The passive tracer on the host (hp_tracer_enable restated in NumPy, in exactly the operation order of csrc/hp_tracer.hpp):
+    the solute mass per unit area M, fp64 whatever the state's precision.  `apply` is one iteration's tracer on the iteration's
+    source buffer, where the engine launches tracer_sources and tracer_step: behind every boundary, in front of the flux step.
+    The face mass fluxes come from `functions` -- an object with the oracle's `reconstruct(direction, sL, bL, sR, bR)` and
+    `hllc(direction, L, R)` in the state's precision (oracle.OracleFunctions) -- called in godunov_cell's argument order; everything
+    behind them is fp64: separate, correctly rounded adds, multiplies and divides, so M equals the device's bit for bit.  The GPU
+    tests' reference; it also counts which branch each cell took."""
+
+    MAX_SOURCES, MAX_SERIES, MAX_CELLS, DEPTH_MIN = 64, 4096, 1048576, 1e-10
+    DIR_N, DIR_E, DIR_S, DIR_W = 0, 1, 2, 3
+    # per cell and iteration: one of the copy cases or "moved"; for a moved cell, per face, which side gave its concentration
+    # (_pos: the flux is > 0, _neg: it is not), and whether a cell too shallow to have a concentration was among the five
+    BRANCHES = ("ring", "dt_zero", "disabled", "dry5", "moved", "e_pos", "e_neg", "w_pos", "w_neg", "n_pos", "n_neg", "s_pos", "s_neg",
+                "no_concentration", "source")
+
+    def __init__(self, rows, cols, dx, functions, initial=None, dry_threshold=1e-10):
+        self.rows, self.cols = int(rows), int(cols)
+        self.fn = functions
+        self.real = np.dtype(functions.real).type
+        self.dx = np.float64(self.real(dx))                                    # dx as the kernels hold it
+        self.vs = self.real(dry_threshold)
+        if initial is None:
+            self.M = np.zeros((self.rows, self.cols))
+        else:
+            self.M = np.array(initial, dtype=np.float64)
+            if self.M.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial tracer must be [{self.rows}, {self.cols}]")
+            if not np.isfinite(self.M).all() or (self.M < 0).any():
+                bad = int(np.flatnonzero(~(np.isfinite(self.M) & (self.M >= 0)).reshape(-1))[0])
+                raise ValueError(f"cell {bad}: initial must be finite and >= 0")
+        self.sources = []                               # (flat cells, series)
+        self.iterations = 0
+        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES}
+
+    def branch_totals(self):
+        return {k: int(v.sum()) for k, v in self.branches.items()}
+
+    def add_source(self, cells, series):
+        """`cells`: flat ids y * cols + x or (x, y) pairs; `series`: [(time, mass rate)]."""
+        c = np.asarray(cells)
+        if c.ndim == 2 and c.shape[1] == 2:
+            c = c[:, 1].astype(np.int64) * self.cols + c[:, 0].astype(np.int64)
+        c = np.asarray(c, dtype=np.int64).reshape(-1)
+        s = np.array(series, dtype=np.float64).reshape(-1, 2)
+        if not 1 <= len(s) <= self.MAX_SERIES:
+            raise ValueError("entries outside 1..4096")
+        if not 1 <= c.size <= self.MAX_CELLS:
+            raise ValueError("count outside 1..1048576")
+        if not np.isfinite(s[:, 0]).all() or not (np.diff(s[:, 0]) > 0).all():
+            raise ValueError("times must be finite and strictly increasing")
+        if not np.isfinite(s[:, 1]).all():
+            raise ValueError("the mass rate must be finite")
+        if c.min() < 0 or c.max() >= self.rows * self.cols:
+            raise ValueError("a cell lies outside the grid")
+        y, x = c // self.cols, c % self.cols
+        if ((x == 0) | (y == 0) | (x == self.cols - 1) | (y == self.rows - 1)).any():
+            raise ValueError("a cell lies on the grid's edge ring")
+        if len(self.sources) >= self.MAX_SOURCES:
+            raise ValueError("more than 64 sources")
+        everyone = np.concatenate([x[0] for x in self.sources] + [c])
+        if everyone.size > self.MAX_CELLS:
+            raise ValueError("more than 1048576 cells over all sources")
+        uniq, counts = np.unique(everyone, return_counts=True)
+        if (counts > 1).any():
+            raise ValueError(f"cell {int(uniq[counts > 1][0])} is listed twice")
+        self.sources.append((c, s))
+
+    @staticmethod
+    def source_step(M, rate, dt, dx):
+        """tracer_source_add on fp64 arrays."""
+        mass = np.float64(rate) * np.float64(dt)
+        area = np.float64(dx) * np.float64(dx)
+        add = mass / area
+        return np.asarray(M, dtype=np.float64) + add
+
+    @staticmethod
+    def concentration(M, h):
+        """tracer_conc on fp64 arrays."""
+        M, h = np.asarray(M, dtype=np.float64), np.asarray(h, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            return np.where(h > Tracer.DEPTH_MIN, M / np.where(h > Tracer.DEPTH_MIN, h, 1.0), 0.0)
+
+    @staticmethod
+    def update(M, cC, cN, cS, cE, cW, FN, FS, FE, FW, dt, dx):
+        """tracer_update on fp64 arrays -> (M', masks): which side each face took."""
+        a = lambda v: np.asarray(v, dtype=np.float64)
+        M, cC, cN, cS, cE, cW, FN, FS, FE, FW = (a(v) for v in (M, cC, cN, cS, cE, cW, FN, FS, FE, FW))
+        dt, dx = np.float64(dt), np.float64(dx)
+        with np.errstate(invalid="ignore", over="ignore"):
+            e, w, n, s = FE > 0.0, FW > 0.0, FN > 0.0, FS > 0.0
+            GE = np.where(e, FE * cC, FE * cE)
+            GW = np.where(w, FW * cW, FW * cC)
+            GN = np.where(n, FN * cC, FN * cN)
+            GS = np.where(s, FS * cS, FS * cC)
+            ex = GE - GW
+            ey = GN - GS
+            total = ex + ey
+            div = total / dx
+            step = dt * div
+            out = M - step
+        return out, dict(e_pos=e, e_neg=~e, w_pos=w, w_neg=~w, n_pos=n, n_neg=~n, s_pos=s, s_neg=~s)
+
+    def face_fluxes(self, state, bed, x, y):
+        """FN, FS, FE, FW of cell (x, y) as godunov_cell forms them (oracle/swe_oracle.c:472-486), in the state's precision."""
+        f = self.fn
+        c, bC = state[y, x], bed[y, x]
+        L, R, _ = f.reconstruct(self.DIR_N, c, bC, state[y + 1, x], bed[y + 1, x])
+        FN = f.hllc(self.DIR_N, L, R)[0]
+        L, R, _ = f.reconstruct(self.DIR_S, state[y - 1, x], bed[y - 1, x], c, bC)
+        FS = f.hllc(self.DIR_S, L, R)[0]
+        L, R, _ = f.reconstruct(self.DIR_E, c, bC, state[y, x + 1], bed[y, x + 1])
+        FE = f.hllc(self.DIR_E, L, R)[0]
+        L, R, _ = f.reconstruct(self.DIR_W, state[y, x - 1], bed[y, x - 1], c, bC)
+        FW = f.hllc(self.DIR_W, L, R)[0]
+        return FN, FS, FE, FW
+
+    def apply(self, state, bed, dt, t):
+        """One iteration's tracer on `state` (the iteration's source buffer, not changed); `dt`, `t`: the timestep and time scalars of
+        that iteration.  Returns the number of cells moved."""
+        if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or state.dtype != bed.dtype:
+            raise ValueError("state must be [rows, cols, 4] and bed [rows, cols], of one dtype")
+        if state.dtype.type is not self.real:
+            raise ValueError("the face-flux functions and the state differ in precision")
+        real = self.real
+        dt_real = real(dt)
+        dt64, t64 = np.float64(dt_real), np.float64(real(t))
+        self.iterations += 1
+        M0 = self.M
+        # the sources first, in place on the M the step reads
+        if dt64 > 0.0:
+            flat = M0.reshape(-1)
+            for cells, series in self.sources:
+                rate = BedShapes.series_fraction(series, t64)
+                flat[cells] = self.source_step(flat[cells], rate, dt64, self.dx)
+                self.branches["source"].reshape(-1)[cells] += 1
+        yy, xx = np.mgrid[0:self.rows, 0:self.cols]
+        ring = (xx == 0) | (yy == 0) | (xx == self.cols - 1) | (yy == self.rows - 1)
+        self.branches["ring"] += ring
+        if not dt_real > 0:
+            self.branches["dt_zero"] += ~ring
+            return 0
+        z, zmax = state[..., 0], state[..., 1]
+        disabled = ~ring & ((zmax <= real(-9999.0)) | (z == real(-9999.0)))
+        dry = (z - bed) < self.vs                                             # in the state's precision, as the flux kernel tests it
+        dry5 = np.zeros_like(dry)
+        dry5[1:-1, 1:-1] = dry[1:-1, 1:-1] & dry[2:, 1:-1] & dry[:-2, 1:-1] & dry[1:-1, 2:] & dry[1:-1, :-2]
+        dry5 &= ~ring & ~disabled
+        moved = ~ring & ~disabled & ~dry5
+        self.branches["disabled"] += disabled
+        self.branches["dry5"] += dry5
+        self.branches["moved"] += moved
+        ys, xs = np.nonzero(moved)
+        if ys.size == 0:
+            return 0
+        F = np.array([self.face_fluxes(state, bed, int(x), int(y)) for x, y in zip(xs, ys)], dtype=np.float64).reshape(-1, 4)
+        h = z.astype(np.float64) - bed.astype(np.float64)                     # the RAW depth, widened
+        c = self.concentration(M0, h)
+        out, masks = self.update(M0[ys, xs], c[ys, xs], c[ys + 1, xs], c[ys - 1, xs], c[ys, xs + 1], c[ys, xs - 1],
+                                 F[:, 0], F[:, 1], F[:, 2], F[:, 3], dt64, self.dx)
+        for name, mask in masks.items():
+            self.branches[name][ys, xs] += mask
+        shallow = ~(h > self.DEPTH_MIN)
+        self.branches["no_concentration"][ys, xs] += shallow[ys, xs] | shallow[ys + 1, xs] | shallow[ys - 1, xs] | shallow[ys, xs + 1] | shallow[ys, xs - 1]
+        M1 = M0.copy()
+        M1[ys, xs] = out
+        self.M = M1
+        return int(ys.size)
+
+
+def tracer_concentration(M, state, bed):
+    """The concentration M / h where the depth h = Z - bed exceeds 1e-8 m (the outputs' threshold for a velocity), else -9999."""
+    h = np.asarray(state)[..., 0].astype(np.float64) - np.asarray(bed).astype(np.float64)
+    wet = h > 1e-8
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return np.where(wet, np.asarray(M, dtype=np.float64) / np.where(wet, h, 1.0), -9999.0)
+
+
+def write_tracer_source_csv(cells_path, series_path, cells, series):
+    """The mapFile and the source of a <tracerSource> element: what parse_configuration reads back (repr round-trips every double)."""
+    with open(cells_path, "w") as f:
+        f.write("x,y\n")
+        for x, y in cells:
+            f.write(f"{int(x)},{int(y)}\n")
+    with open(series_path, "w") as f:
+        f.write("time,rate\n")
+        for t, r in series:
+            f.write(f"{float(t)!r},{float(r)!r}\n")
 
 
 def write_soil_csv(path, classes):

@@ -182,7 +182,7 @@ class Model:
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
                  probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None,
-                 links=None, infiltration=None):
+                 links=None, infiltration=None, tracer=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -235,6 +235,33 @@ class Model:
             sim.add_infiltration(soil, self.infiltration["classes"], self.infiltration["initial"])
         elif any(what == "infiltration" for what, _ in cfg.targets):
             raise ValueError("an infiltration data target needs a soil data source")
+        # The tracer (no reference counterpart): the initial M of a <dataSource type="raster" value="tracer" source="m0.asc"/> and the
+        # sources of the <tracerSource mapFile="cells.csv" source="rate.csv"/> elements, or `tracer`: dict(initial=, sources=[dict(cells=,
+        # series=)]) with initial an array [rows, cols] (row 0 = south), a raster file or None.  Enabled behind everything that may refuse
+        # it.  It moves inside every iteration, so only an engine that has it on the device will do.  A <dataTarget value="tracer" .../>
+        # writes M at every output time, a <dataTarget value="concentration" .../> M / h (frontend.tracer_concentration).
+        spec = dict(tracer) if tracer is not None else None
+        source = next((src for src in cfg.sources if "tracer" in src[1]), None)
+        if spec is None and (source is not None or cfg.tracer_sources):
+            if source is not None and source[0] != "raster":
+                raise ValueError("the tracer data source must be a raster")
+            spec = dict(initial=os.path.join(cfg.source_dir, source[2]) if source is not None else None, sources=cfg.tracer_sources)
+        self.tracer = None
+        if spec is not None:
+            m0 = spec.get("initial")
+            if m0 is not None:
+                m0 = frontend.read_raster(m0)[0] if isinstance(m0, (str, os.PathLike)) else np.asarray(m0, dtype=np.float64)
+                if m0.shape != (self.rows, self.cols):
+                    raise ValueError(f"the tracer raster is {m0.shape[1]} x {m0.shape[0]} cells, the domain {self.cols} x {self.rows}")
+            if not hasattr(sim, "tracer_enable"):
+                raise NotImplementedError("the tracer moves inside every iteration: it needs an engine with tracer_enable (the HIP engine)")
+            self.tracer = dict(initial=m0, sources=[dict(cells=list(s["cells"]), series=np.asarray(s["series"], dtype=np.float64).reshape(-1, 2))
+                                                    for s in (spec.get("sources") or [])])
+            sim.tracer_enable(m0)
+            for s in self.tracer["sources"]:
+                sim.tracer_add_source(s["cells"], s["series"])
+        elif any(what in ("tracer", "concentration") for what, _ in cfg.targets):
+            raise ValueError("a tracer or concentration data target needs a tracer (a tracer data source, a <tracerSource> element or Model(tracer=...))")
         self.scheme = SchemeDriver(sim, cfg, self.cols * self.rows)
         self.output_format, self.log, self.clock = output_format, log, clock
         self.progress_interval = progress_interval
@@ -467,7 +494,8 @@ class Model:
             return False
         is_peak = [frontend.peak_value_code(what) is not None for what, _ in self.cfg.targets]
         is_soil = [what == "infiltration" for what, _ in self.cfg.targets]     # the cumulative infiltration F: the engine's own raster
-        plain = [what for (what, _), pk, so in zip(self.cfg.targets, is_peak, is_soil) if not pk and not so]
+        is_tracer = [what in ("tracer", "concentration") for what, _ in self.cfg.targets]   # M, or M / h: the engine's own raster
+        plain = [what for (what, _), pk, so, tr in zip(self.cfg.targets, is_peak, is_soil, is_tracer) if not pk and not so and not tr]
         if self.device_outputs:                                    # every target in ONE call, rasters only over the host link
             derived = self.sim.derive(plain) if plain else {}
         elif plain or not self.cfg.targets:
@@ -498,6 +526,10 @@ class Model:
                 arr = peaks[frontend.peak_value_code(what)]
             elif is_soil[k]:
                 arr = self.sim.infiltration_read()
+            elif is_tracer[k]:
+                arr = self.sim.tracer_read()
+                if what == "concentration":
+                    arr = frontend.tracer_concentration(arr, self.sim.download(), self.sim.download_bed() if hasattr(self.sim, "download_bed") else self.bed)
             else:
                 arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
             out[what] = arr

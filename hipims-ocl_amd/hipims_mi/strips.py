@@ -253,6 +253,25 @@ class HipEngine:
     def infiltration_read(self, row0=0, nrows=None):
         return self.domain.infiltration_read(row0, nrows)
 
+    # the tracer (Domain.tracer_*)
+    def tracer_enable(self, initial=None):
+        self.domain.tracer_enable(initial)
+
+    def tracer_disable(self):
+        self.domain.tracer_disable()
+
+    def tracer_add_source(self, cells, series):
+        self.domain.tracer_add_source(cells, series)
+
+    def tracer_read(self, row0=0, nrows=None):
+        return self.domain.tracer_read(row0, nrows)
+
+    def tracer_write(self, raster, row0=0):
+        self.domain.tracer_write(raster, row0)
+
+    def tracer_info(self):
+        return self.domain.tracer_info()
+
     # the peak tracker (Domain.peaks_*)
     def peaks_enable(self, values, arrival_depth=0.01):
         self.domain.peaks_enable(values, arrival_depth=arrival_depth)
@@ -694,6 +713,21 @@ class StripRunner:
             f0 = np.ascontiguousarray(f0[self.local_slice()])
         self.engine.add_infiltration(np.ascontiguousarray(ids[self.local_slice()]), classes, f0)
         self._infiltration = True
+
+    # ---- the tracer: a strip has none (hp_tracer_enable answers HP_ERR_UNSUPPORTED: M's ghost rows would need an exchange of their own);
+    #      the refusal is the engine's own and is passed through ----
+    def tracer_enable(self, initial_global=None):
+        """`initial_global`: the [rows, cols] raster of the WHOLE grid (row 0 = south), or None.  On more than one strip the engine
+        refuses (hipims_mi.HipimsError, HP_ERR_UNSUPPORTED), and so does this call."""
+        if not hasattr(self.engine, "tracer_enable"):
+            raise RuntimeError("tracer_enable: this engine has no tracer (the HIP engine's hp_tracer_enable)")
+        m0 = None
+        if initial_global is not None:
+            m0 = np.asarray(initial_global, dtype=np.float64)
+            if m0.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial tracer must be [{self.rows}, {self.cols}]")
+            m0 = np.ascontiguousarray(m0[self.local_slice()])
+        self.engine.tracer_enable(m0)
 
     def gather_infiltration(self):
         """The cumulative infiltration F of the whole grid on rank 0 (fp64 [rows, cols], equal to the single domain's

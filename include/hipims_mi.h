@@ -512,7 +512,9 @@ int hp_bed_info(hp_domain_t* d, hp_bed_info_t* out);   /* BLOCKS */
  * sink: the probe recorder's rule.
  * While the domain has an infiltration (hp_boundary_add_infiltration), hp_state_save also copies F and hp_state_restore puts it
  * back.  If the infiltration was added or cleared since the snapshot, hp_state_restore leaves F as it is and sends one
- * HP_LOG_WARNING to the log sink. */
+ * HP_LOG_WARNING to the log sink.
+ * While the domain has a tracer (hp_tracer_enable), hp_state_save also copies the current M with its phase and iteration counter
+ * and hp_state_restore puts them back, by the infiltration's rule. */
 int hp_state_save(hp_domain_t* d);
 int hp_state_restore(hp_domain_t* d);
 
@@ -673,6 +675,78 @@ int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups to
  * the boundary kernels as separate launches like the reference (CSchemeGodunov.cpp:1637-1643).  Results are identical
  * either way; bench.py reports it. */
 int hp_boundaries_fused(hp_domain_t* d, int* fused);
+
+/* ---- the passive tracer: a solute carried with the water (no reference counterpart: the reference moves water only).  It answers
+ *      where water came from and where something dissolved in it goes: a spill at an outfall, the share of river water in a
+ *      basement.  The stored quantity is a MASS PER UNIT AREA M (units * m: concentration x depth), not a concentration: rain
+ *      dilutes it without touching it, the sum of M over a closed domain is conserved to rounding, and a cell that dries keeps
+ *      its residue.
+ *      STATE.  Two fp64 rasters of the local array in device memory (the old and the new M, 16 bytes per cell) with a phase of
+ *      their own, independent of the state's ping-pong buffers, whatever the domain's precision.  Nothing of it exists on a
+ *      domain that never calls hp_tracer_enable, and such a domain queues exactly what it queued without these calls.  A domain
+ *      with it is not fusable (hp_boundaries_fused is false), runs single iterations, never iteration pairs, and never runs a
+ *      speculative STRICT batch (a batch queued again would move M twice).
+ *      THE STEP.  Once per iteration, behind EVERY boundary of the list whatever the order added and in front of the flux
+ *      launch: the kernel (csrc/hp_tracer.hpp: tracer_step, one lane per cell) reads the source buffer the flux kernel is about
+ *      to read and the "Timestep" scalar dt before the flux launch advances it, and writes only M.  T is the domain's precision.
+ *        0. Sources first (tracer_sources): if dt > 0, M += (rate(t) * dt) / (dx * dx) at each listed cell, rate the source's
+ *      {time, mass rate} series at the device's "Time" scalar by the bed shapes' rule (hp_bed_shape_add: the first value at or
+ *      before the first time, the last at or after the last, r_k + (r_k+1 - r_k) * ((t - t_k) / (t_k+1 - t_k)) in between), all
+ *      of it in fp64.
+ *        1. Copy cases, M' = M: a ring cell (column 0 or cols - 1, row 0 or rows - 1: the cells the flux kernel never writes);
+ *      any cell when dt <= 0; a disabled cell (Zmax <= -9999 or Z == -9999); a cell for which Z - bed < dry_threshold (in T)
+ *      holds in the cell and in its four neighbours (quirk Q3's condition, under which no water moves).
+ *        2. The four face mass fluxes FN, FS, FE, FW exactly as the flux kernel's exact arithmetic forms them: the first
+ *      component of the HLLC flux behind the reconstruction, same argument order, in precision T -- the STRICT face solve
+ *      WHATEVER the domain's math_mode: the tracer's arithmetic is one thing, not two.
+ *        3. Everything below in fp64, the values widened first; correctly rounded add, multiply, divide and compare only, never
+ *      fused.  h_k = (double)Z_k - (double)bed_k from the RAW source state, not the reconstructed one;
+ *      c_k = h_k > 1e-10 ? M_k / h_k : 0, for the cell (C) and its four neighbours.
+ *        4. Each face takes the concentration of the cell the water leaves: GE = FE > 0 ? FE * cC : FE * cE;
+ *      GW = FW > 0 ? FW * cW : FW * cC; GN = FN > 0 ? FN * cC : FN * cN; GS = FS > 0 ? FS * cS : FS * cC.
+ *        5. M' = M - dt * (((GE - GW) + (GN - GS)) / dx), in this order, dx as the kernels hold it (rounded to T, widened).
+ *      There is no clamp and no limiter.  The two cells of a face take the same upwind concentration, so what one loses the
+ *      other gains, up to the rounding of the face flux as each of the two forms it and of the final M - dt * (...).  A face
+ *      whose neighbour is a copy case still carries its flux; a wall gives F = 0 by the reconstruction.
+ *      frontend.Tracer restates all of it in NumPy; tests/tracer_probe.cpp holds steps 0 and 3 to 5 to it bit for bit.
+ *      WHAT IT SAYS ABOUT THE WATER.  The flux kernel zeroes net changes below the dry threshold and snaps nearly dry cells to
+ *      the bed, and in FAST arithmetic its fluxes differ from the STRICT ones in the last bits: so M / h can leave
+ *      [min c, max c] by rounding-sized amounts and at drying fronts, while M itself stays conserved.  The uniform loss rate
+ *      takes water and leaves M (evaporation).  hp_bed_apply keeps the depth and so leaves M alone.
+ *      REFUSED, HP_ERR_UNSUPPORTED, with the reason in the message: a scheme other than Godunov; a strip
+ *      (global_rows != rows: M's ghost rows would need an exchange of their own); a domain with link groups or an infiltration
+ *      (both move water that would have to carry M) -- and hp_boundary_add_links / hp_boundary_add_infiltration on a traced
+ *      domain likewise.
+ *      hp_domain_upload does not touch M; hp_boundary_clear does not touch the tracer; hp_domain_destroy frees it.
+ *      hp_state_save / hp_state_restore carry the current M, its phase and the iteration counter; if the tracer was enabled or
+ *      disabled since the snapshot, hp_state_restore leaves M as it is and sends one HP_LOG_WARNING to the log sink. ---- */
+typedef struct {
+	uint32_t struct_size;
+	uint32_t reserved;                 /* 0 */
+	const double* initial;             /* cols*rows M0 of the LOCAL array in units * m (finite, >= 0), row 0 = south, or NULL for zeros */
+} hp_tracer_desc_t;
+/* Argument errors -- a NULL desc, a bad struct_size, a negative or non-finite initial (the message names the first bad cell) --
+ * are HP_ERR_INVALID before any device call.  Between hp_step_begin and hp_step_end the call returns HP_ERR_STATE, as does a
+ * second enable.  If an allocation fails the call returns HP_ERR_HIP and the domain stays usable without a tracer.  `initial`
+ * is free on return. */
+int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc);
+int hp_tracer_disable(hp_domain_t* d);                 /* frees M and the sources; idempotent (also done by hp_domain_destroy) */
+/* One source: `count` cells (flat ids of the grid, y * cols + x) that each receive the mass rate of `series` (`entries` pairs
+ * {time in s, rate in units per second}, times finite and strictly increasing, rates finite; a negative rate takes mass out).
+ * Argument errors -- a NULL pointer, entries outside 1..4096, count outside 1..1048576, a cell outside the grid, on the edge
+ * ring or listed twice over all sources, more than 64 sources or 1 048 576 cells in all -- are HP_ERR_INVALID before any device
+ * call; HP_ERR_STATE before hp_tracer_enable and between hp_step_begin and hp_step_end.  The arrays are free on return. */
+int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries);
+int hp_tracer_sources_clear(hp_domain_t* d);
+/* Rows row0 .. row0 + nrows - 1 of the current M (fp64, cols values a row).  Enqueued; valid after hp_sync (the host memory must
+ * stay alive until then).  A NULL raster or a row range outside the array is HP_ERR_INVALID; a domain without a tracer, or a
+ * call between hp_step_begin and hp_step_end, HP_ERR_STATE; nrows == 0 is HP_OK. */
+int hp_tracer_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows);
+/* ... and the reverse: the rows of the current M are replaced (the values are the caller's: no check).  The raster is free on return. */
+int hp_tracer_write(hp_domain_t* d, const double* raster, int64_t row0, int64_t nrows);
+/* Host counters, does not block: the iterations the tracer has been stepped through since hp_tracer_enable (as restored by
+ * hp_state_restore), its sources and their cells (all 0 without a tracer); any pointer may be NULL. */
+int hp_tracer_info(hp_domain_t* d, uint64_t* iterations, uint32_t* sources, uint64_t* source_cells);
 
 /* ---- time control ---- */
 int hp_set_target_time(hp_domain_t* d, double t);     /* CScheme::setTargetTime -> "Target time (sync)" buffer (:1166-1176) */
