@@ -297,6 +297,15 @@ struct hp_domain {
 	size_t           still_rec_slots = 0;             // records per half
 	int              still_rec_half = 0;
 	bool             still_rec_last = false;          // the last pair launch wrote records (hp_pair_stats)
+	// block order of the same launches (hp_order.hpp; round 18): two table halves of bands x tiles-per-band words -- the one the last launch's
+	// tail block wrote in half order_half --, then the flags (a word per band and group), then a counter (hp_pair_stats).  order_shape:
+	// the (bands, groups, tall, short segments) the buffer was sized for; order_launch: flux_launches as that launch left it -- the next
+	// pair launch reads the table only if it is the domain's very next flux launch and of the same shape; order_read: whether the last did
+	unsigned*        order_buf = nullptr;
+	int              order_shape[4] = {0, 0, 0, 0};
+	int              order_half = 0;
+	uint64_t         order_launch = 0;
+	bool             order_written = false, order_read = false;
 	uint64_t         pair_cold_starts = 0;
 	// STRICT: pairs or single iterations, by measurement (pair_tuner: the two are the same bits; which is faster depends on how much of
 	// the water stands still)

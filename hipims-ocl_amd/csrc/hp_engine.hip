@@ -191,6 +191,13 @@ const LaunchKnobs& launch_knobs()
 	                              std::getenv("HP_NBANDS") ? std::atoi(std::getenv("HP_NBANDS")) : 0};
 	return k;
 }
+// HP_PAIR_ORDER=0: the pair kernel's record launches raise no flags and read no table -- blocks take their tiles tile-row by tile-row
+// (A/B runs; hp_order.hpp).  Once per process, like the switches above.
+static bool pair_order_on()
+{
+	static const bool on = !(std::getenv("HP_PAIR_ORDER") && std::atoi(std::getenv("HP_PAIR_ORDER")) == 0);
+	return on;
+}
 
 // Rows one flux launch updates: everything between the never-written edge ring / the outermost ghost rows.  A strip with
 // two reaches of ghost rows (ghost_rows = 2g) also updates, on the iteration that follows an exchange, the g ghost rows
@@ -606,6 +613,26 @@ static int still_rec_alloc(hp_domain* d, const int windows)
 	d->still_rec_slots = slots;
 	return HP_OK;
 }
+// Block order of the same launches (hp_order.hpp; hp_kernels.hpp: OrderHook): the flags and the two table halves, sized for one tiling.
+// Both halves start as the order without a hint, so a half is a permutation of every band's tiles whoever wrote it last -- also behind a
+// tail block that gave up and built nothing.  Nothing about the state hangs on it: no fact of hp_facts.hpp is involved.
+static int order_alloc(hp_domain* d, const TileMap& tm)
+{
+	const int shape[4] = {tm.nbands, tm.groups, tm.nbig, tm.ntail};
+	if (d->order_buf && std::equal(shape, shape + 4, d->order_shape)) return HP_OK;
+	hipFree(d->order_buf);
+	d->order_buf = nullptr;
+	d->order_written = d->order_read = false;
+	const unsigned groups = (unsigned)tm.groups, nseg = (unsigned)(tm.nbig + tm.ntail), per_band = groups * nseg, table = (unsigned)tm.nbands * per_band;
+	std::vector<unsigned> words((size_t)2 * table + (size_t)tm.nbands * groups + 1, 0u);
+	for (unsigned i = 0; i < 2 * table; ++i) words[i] = order_entry(groups, nseg, 0ull, i % per_band);
+	HIP_TRY(hipMalloc((void**)&d->order_buf, words.size() * sizeof(unsigned)));
+	HIP_TRY(hipMemcpyAsync(d->order_buf, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));                            // (`words` leaves with this call; once per domain and tiling)
+	std::copy(shape, shape + 4, d->order_shape);
+	d->order_half = 0;
+	return HP_OK;
+}
 // Area boundaries: the pair kernel needs the primary buffer priced WITH the first iteration's boundaries (slot[SLOT_M1]).  Every BDY
 // pair leaves that figure for its successor; where there is no such predecessor -- the first pair after single iterations, an upload,
 // a new target time -- the first half of iteration k is done the reference's own way: the stand-alone boundary pass on the primary
@@ -676,6 +703,19 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 		aux.still_in = d->facts->still_rec_valid ? base + (size_t)d->still_rec_half * d->still_rec_slots : nullptr;
 		aux.still_rows = d->desc.rows;
 	}
+	// block order (hp_order.hpp): the instantiation that writes records -- with or without them -- raises its flags and leaves a table; it
+	// reads the last one if that launch was the domain's flux launch just before this one, of this tiling (anything else: tile-row by tile-row)
+	const bool ordered = pair_order_on() && d->desc.precision == 8 && d->desc.math_mode != HP_MATH_STRICT && !strip && !bdy && !exact &&
+	                     tm.groups <= (int)ORDER_MAX_GROUPS;
+	bool order_read = false;
+	if (ordered) {
+		if ((rc = order_alloc(d, tm)) != HP_OK) return rc;
+		order_read = d->order_written && d->flux_launches == d->order_launch + 1;   // (make_tail, above, has counted this launch)
+		const size_t table = (size_t)tm.nbands * tm.groups * (tm.nbig + tm.ntail);
+		aux.order_in = order_read ? d->order_buf + (size_t)d->order_half * table : nullptr;
+		aux.order_out = d->order_buf + (size_t)(d->order_half ^ 1) * table;
+		aux.order_flags = d->order_buf + 2 * table;
+	}
 	const void* src = d->state[0];
 	void* dst = d->state[1];
 	// flux-kernel timing (hp_kernel_timing): as in step_begin_impl -- a sampled launch here covers two iterations
@@ -701,6 +741,8 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 	HIP_TRY(hipGetLastError());
 	if (recs) d->still_rec_half ^= 1;
 	d->facts.pair_launched(recs); d->still_rec_last = recs;
+	if (ordered) { d->order_half ^= 1; d->order_launch = d->flux_launches; }
+	d->order_written = ordered; d->order_read = order_read;
 	if (sample) { HIP_TRY(hipEventRecord(d->timing_events[d->timing_used].second, d->stream)); d->timing_used++; }
 	// the pass wrote state k + 2 into the other buffer: that buffer IS the primary one from here on (two single iterations would
 	// have left the newest state in the primary buffer; the two buffers' edge rings are equal -- pair_eligible -- and so are their maxima)
@@ -998,7 +1040,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->state[0]); hipFree(d->state[1]); hipFree(d->bed); hipFree(d->manning);
 	hipFree(d->scalars); hipFree(d->cfl_slot);
 	hipFree(d->saved_state); hipFree(d->saved_scalars); hipFree(d->fused_list); hipFree(d->tail_words);
-	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec);
+	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec); hipFree(d->order_buf);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
 	observers_destroy(d); actors_destroy(d);
@@ -2199,6 +2241,18 @@ int hp_pair_stats(hp_domain_t* d, uint64_t out[12])
 		HIP_TRY(hipMemcpyAsync(host_counts, counts, sizeof host_counts, hipMemcpyDeviceToHost, d->stream));
 		HIP_TRY(hipStreamSynchronize(d->stream));
 		out[9] = host_counts[0]; out[10] = host_counts[1];
+	}
+	if (d->order_buf && d->order_read) {                                  // (the half the last pair launch read: the one it did not write)
+		const unsigned per_band = (unsigned)(d->order_shape[1] * (d->order_shape[2] + d->order_shape[3])), table = (unsigned)d->order_shape[0] * per_band;
+		unsigned* const count = d->order_buf + 2 * (size_t)table + (size_t)d->order_shape[0] * d->order_shape[1];
+		HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned), d->stream));
+		hipLaunchKernelGGL(order_count, dim3(16), dim3(256), 0, d->stream, d->order_buf + (size_t)(d->order_half ^ 1) * table, (unsigned)d->order_shape[1],
+		                   per_band, table, count);
+		HIP_TRY(hipGetLastError());
+		unsigned moved = 0;
+		HIP_TRY(hipMemcpyAsync(&moved, count, sizeof moved, hipMemcpyDeviceToHost, d->stream));
+		HIP_TRY(hipStreamSynchronize(d->stream));
+		out[11] = moved;
 	}
 	if (d->haz_words) {
 		unsigned long long used = 0;

@@ -3,6 +3,7 @@
 
 #include "hp_math.hpp"
 #include "hp_tiling.hpp"
+#include "hp_order.hpp"
 
 namespace hp {
 
@@ -357,8 +358,42 @@ __device__ __forceinline__ void tail_block_done(const LaunchTail<T>& tail, const
 // blocks of the same batch see the word and return at once, and the host finds it wherever it next blocks on the stream
 // (hp_sync, hp_read_scalars; hp_engine.hip: tail_error_check) and fails the domain with HP_ERR_STATE.  The clock is only read on
 // the slow path (a word found empty), the common case is one load per word as before.
+// What the tail block of a pair launch does for the NEXT launch's block order (hp_order.hpp; nullptr for every other kernel): the flags
+// the launch's marching waves raised -- one word per (band, group), a count of those waves -- become, per band, the table `out` of the
+// launch that follows, and are zeroed again.  Waves 1-3 do it, a band per wave at a time and without a barrier, while wave 0 advances
+// the time; it waits for nothing.  The counts are a hint and are handled as one: adds and loads are relaxed, and what makes a launch's
+// adds visible here is only that each block's done word, stored after them, has been seen.  An add that arrives after its word was zeroed
+// is counted into the next launch; a tail block that gives up (time-out) zeroes nothing, and whatever stays in the words weighs on
+// later thresholds -- a large stale count can keep a lesser group from going first -- until the next tail block that gets here zeroes
+// them.  Timing only: every table is a permutation of the band's tiles.
+// ORDER_SHARE: with "any wave marched" (a share of nothing) the ring's tile row flags every group of the two outer bands and the order
+// there stays tile-row by tile-row; the larger the share asked for, the more lightly marching groups -- a front that has just entered
+// a group, the ring's column groups (a quarter of the dam's groups' waves) -- are left among the skipped tiles and start late.  An
+// eighth keeps every group whose tiles march in more than a couple of tile rows of the band; it was set on S-DAM at 4096^2 (counts
+// 88 / 22 / 4) and on the developed flood only its sum was seen (-3 %): where every group marches alike, all pass and the order is
+// the one without a hint.
+constexpr unsigned ORDER_SHARE = 8;      // a group goes first with at least 1 / ORDER_SHARE of its band's largest count (order_build)
+struct OrderHook { unsigned* flags; unsigned* out; unsigned nbands, groups, nseg; };
+__device__ __forceinline__ void order_build(const OrderHook& h)
+{
+	const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const unsigned per_band = h.groups * h.nseg;
+	for (unsigned band = wave - 1u; band < h.nbands; band += 3u) {
+		unsigned* const f = h.flags + band * h.groups;
+		// The word counts the group's marching waves.  A group goes first if it holds at least an eighth of what the band's busiest group
+		// holds: the band beside the edge ring has ONE tile row that marches in every group (the ring's row never matches the pool), and a
+		// plain "any wave marched" would flag every group there and leave that band -- the launch's longest -- in tile-row order
+		// (profiles/r18_pair_order_stage.txt)
+		const unsigned count = lane < h.groups ? __hip_atomic_load(f + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+		unsigned most = count;
+		for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)most, off); most = o > most ? o : most; }
+		const unsigned long long mask = __ballot(count != 0u && count >= (most + ORDER_SHARE - 1u) / ORDER_SHARE);
+		if (lane < h.groups) order_fill_group(h.groups, h.nseg, mask, lane, h.out + band * per_band);
+		if (count != 0u) __hip_atomic_store(f + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
 template <typename T>
-__device__ __forceinline__ void launch_tail(const Params<T>& p, const LaunchTail<T>& tail)
+__device__ __forceinline__ void launch_tail(const Params<T>& p, const LaunchTail<T>& tail, const OrderHook* const order = nullptr)
 {
 	__shared__ T part[4];
 	__shared__ int failed_before, late_any;     // two words: a wave that times out early must not look like "an earlier launch failed" to a slower wave's first read
@@ -412,7 +447,10 @@ __device__ __forceinline__ void launch_tail(const Params<T>& p, const LaunchTail
 		if (tail.pair == 2) for (int w = 1; w < 4; ++w) if (part1[w] > m1) m1 = part1[w];
 	}
 	__syncthreads();                                            // (part[0] for wave 0)
-	if (threadIdx.x >= 64) return;
+	if (threadIdx.x >= 64) {
+		if (order != nullptr) order_build(*order);               // (every done word has been seen: the launch's flags are in)
+		return;
+	}
 	if (tail.fresh & 4) {
 		const T local = (tail.fresh & 1) ? part[0] : atomic_peek(tail.slot);
 		const T all = peer_reduce_max(tail.box, local);
@@ -619,7 +657,8 @@ __device__ __forceinline__ Side<T> side_from_east(const Side<T>& s)
 // (struct TileMap -- how one launch's blocks map to tiles -- is in hp_tiling.hpp, with the host code that fills it)
 
 // rows [y0, y1) and the column strip of this wave; false if the block / wave has nothing to do (wave-uniform)
-__device__ __forceinline__ bool tile_rows(const TileMap& tm, const int wave, long& strip, long& y0, long& y1)
+// `order`: the band's blocks take their tiles in this table's order (hp_order.hpp; the pair kernel's record launches) -- nullptr: tile-row by tile-row
+__device__ __forceinline__ bool tile_rows(const TileMap& tm, const int wave, long& strip, long& y0, long& y1, const unsigned* const order = nullptr)
 {
 	const unsigned band = blockIdx.x % (unsigned)tm.nbands, i = blockIdx.x / (unsigned)tm.nbands;
 	const unsigned nbig_tiles = (unsigned)(tm.groups * tm.nbig);
@@ -627,7 +666,14 @@ __device__ __forceinline__ bool tile_rows(const TileMap& tm, const int wave, lon
 	const long band_y1 = (band_y0 + tm.band_rows < tm.y_end) ? (band_y0 + tm.band_rows) : tm.y_end;
 	unsigned g;
 	long h;
-	if (i < nbig_tiles) {
+	if (order != nullptr) {
+		// (a word that is no tile of the band -- there is none in a table order_build wrote -- fails the guard below like a block beyond the band)
+		const unsigned e = order[band * (unsigned)(tm.groups * (tm.nbig + tm.ntail)) + i], seg = order_seg(e);
+		g = order_g(e);
+		const bool big = seg < (unsigned)tm.nbig;
+		h = big ? tm.rseg : tm.rseg_tail;
+		y0 = band_y0 + (big ? (long)seg * tm.rseg : (long)tm.nbig * tm.rseg + (long)(seg - (unsigned)tm.nbig) * tm.rseg_tail);
+	} else if (i < nbig_tiles) {
 		g = i % (unsigned)tm.groups;
 		h = tm.rseg;
 		y0 = band_y0 + (long)(i / (unsigned)tm.groups) * tm.rseg;
@@ -728,6 +774,13 @@ template <typename T> struct PairAux {
 	StillRec*             still_out;
 	const StillRec*       still_in;
 	long                  still_rows;
+	// (block order, hp_order.hpp; the still-record instantiation only) order_in: the table this launch's blocks take their tiles by, written
+	// by the tail block of the launch before -- nullptr: tile-row by tile-row; order_flags: one word per (band, group), in which this
+	// launch's marching waves count themselves and from which its tail block builds order_out -- nullptr: no counts, no table (HP_PAIR_ORDER=0).
+	// (One base pointer with the three addresses derived in the kernel was built too: 37 / 26 scalar registers spilled against 33 / 24.)
+	const unsigned*       order_in;
+	unsigned*             order_out;
+	unsigned*             order_flags;
 };
 
 // FUSED (round 3): the instantiation a domain with fusable area boundaries runs.  The reference applies rain / loss IN PLACE
@@ -1222,8 +1275,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	State4<T>* __restrict__ dst, const T* __restrict__ manning, T* cfl_slot, const T* __restrict__ edge_max,
 	const TileMap tm, const LaunchTail<T> tail, const PairAux<T> aux)
 {
+	constexpr bool ORDERED = !STRICT && !BDY && !HZ && TAIL == 1 && sizeof(T) == 8;  // (the still-record instantiation, RECS below: the one whose tiles differ most in length)
 	if (TAIL != 0 && blockIdx.x >= tail.flux_blocks) {
-		launch_tail(p, tail);
+		if (ORDERED && aux.order_flags != nullptr) {
+			const OrderHook hook{aux.order_flags, aux.order_out, (unsigned)tm.nbands, (unsigned)tm.groups, (unsigned)(tm.nbig + tm.ntail)};
+			launch_tail(p, tail, &hook);
+		} else launch_tail(p, tail);
 		return;
 	}
 	// (BDY) increments of the three boundary applications a pair can meet -- [0] the first iteration's, on the source rows as they are
@@ -1234,8 +1291,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	long strip, y0, y1;                                                            // rows [y0, y1) receive state k + 2
 	T wave_vmax = T(0), wave_vmax1 = T(0);
-	if (tile_rows(tm, wave, strip, y0, y1)) {
+	if (tile_rows(tm, wave, strip, y0, y1, ORDERED ? aux.order_in : nullptr)) {
 
+	// (block order) the word in which this wave counts itself if it marches: formed here, where band and group are at hand -- one
+	// scalar pair waits for the still run's verdict instead of the tiling's words
+	unsigned* const order_word = (ORDERED && aux.order_flags != nullptr)
+		? aux.order_flags + (blockIdx.x % (unsigned)tm.nbands) * (unsigned)tm.groups + (unsigned)(strip >> 2) : nullptr;
 	const long x = strip * MARCH2_COLS - 1 + lane;                                 // lane 2 is the strip's first updated column
 	const long xc = x < 0 ? 0 : (x < p.cols ? x : (p.cols - 1));
 	const bool out_x = lane >= 2 && lane <= MARCH2_COLS + 1 && x <= p.cols - 2;    // x >= 1 is implied
@@ -1795,6 +1856,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	const long yb = (RUNS && !skip_a && !skip_b) ? still_run() : y0;              // the still rows at the tile's start, if any
 	write_recs(STILL_TAG_RUN);                                                     // (RECS; before the march: nothing of it lives into the loop)
 	if (!RUNS || yb < y1) {
+		// (block order) this wave marches: it counts itself in its group's word (no value comes back); nothing of it lives into the march
+		if constexpr (ORDERED) { if (order_word != nullptr && lane == 0) __hip_atomic_fetch_add(order_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 		prime(yb);
 		// steady state: stage A on row r, stage B on row r - 1
 		long r = yb + 1;
@@ -1892,6 +1955,15 @@ __global__ __launch_bounds__(256) void still_rec_count(const StillRec* __restric
 	}
 	for (int off = 32; off > 0; off >>= 1) { skipped += __shfl_down(skipped, off); still += __shfl_down(still, off); }
 	if ((threadIdx.x & 63) == 0 && (skipped | still)) { atomicAdd(counts, skipped); atomicAdd(counts + 1, still); }
+}
+// hp_pair_stats: entries of the block-order table the last pair launch read that differ from the order without a hint (hp_order.hpp)
+__global__ __launch_bounds__(256) void order_count(const unsigned* __restrict__ table, const unsigned groups, const unsigned per_band, const unsigned n,
+                                                   unsigned* count)
+{
+	unsigned moved = 0;
+	for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) moved += !order_is_identity(groups, i % per_band, table[i]);
+	for (int off = 32; off > 0; off >>= 1) moved += __shfl_down(moved, off);
+	if ((threadIdx.x & 63) == 0 && moved) atomicAdd(count, moved);
 }
 
 // Cold start of iteration pairs on a domain with area boundaries (hp_engine.hip: pair_cold_start): the stand-alone boundary pass and the

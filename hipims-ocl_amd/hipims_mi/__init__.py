@@ -1265,7 +1265,7 @@ class Domain:
         _check(self.lib, self.lib.hp_pair_stats(self.h, out), "hp_pair_stats")
         return dict(pairs=out[0], cold_starts=out[1], stamped_last=out[2], stamped_ever=out[3], tune_samples=out[4],
                     tune_switches=out[5], prefers_pairs=bool(out[6]), pair_over_single=out[7] / 1000.0, stale_used=out[8],
-                    skipped_rows=out[9], still_rows=out[10])
+                    skipped_rows=out[9], still_rows=out[10], reordered_tiles=out[11])
 
     def kernel_timing_overhead(self):
         """Cost of an empty event pair (ms) that kernel_timing_read() has taken off every sample (0.0 with a library that

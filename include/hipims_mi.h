@@ -901,6 +901,8 @@ int hp_kernel_timing_overhead(hp_domain_t* d, double* overhead_ms);
  *                        the same bits)                    HP_PAIR_EXACT=0 / 1   the exact flavour nowhere / everywhere
  *   HP_PAIR_BDY=0        domains with area boundaries keep single iterations      HP_PAIR_STRICT=0   so does STRICT arithmetic
  *   HP_PAIR_SKIP=0       FAST fp64 pairs keep no still records and skip no tiles (the same bits; A/B runs)
+ *   HP_PAIR_ORDER=0      the same launches start their tiles tile-row by tile-row, not the column groups that marched last time first
+ *                        (the same bits; A/B runs)
  * hp_launch_counts and hp_pair_stats show what ran. */
 /* How many whole-domain flux launches the domain has queued since it was created, and how many of them carried their own tail
  * block (reduction + time advance inside the flux launch: an iteration is then ONE launch; otherwise the flux launch is followed
@@ -917,7 +919,9 @@ int hp_launch_counts(hp_domain_t* d, uint64_t* flux_launches, uint64_t* with_tai
  * stamps would have got wrong on this run (0: it would have left the same bits); FAST fp64 single domains (the pair kernel's still
  * records; HP_PAIR_SKIP=0 switches them off): out[9] window rows (60 columns each) the LAST pair launch skipped -- found in one
  * still state on their whole stencil by the launch before, neither loaded nor stored -- and out[10] window rows it recorded as
- * still (skipped, or stored as found by a still run; its updated rows x ceil((cols - 2) / 60) in all); out[11] reserved. */
+ * still (skipped, or stored as found by a still run; its updated rows x ceil((cols - 2) / 60) in all); out[11] (the same launches'
+ * block order; HP_PAIR_ORDER=0 switches it off) tiles the LAST pair launch ran at another position of its band's block stream than
+ * tile-row by tile-row order gives them -- 0 where no column group, or every one alike, marched in the launch before, or no table was read. */
 int hp_pair_stats(hp_domain_t* d, uint64_t out[12]);
 
 #ifdef __cplusplus
