@@ -291,7 +291,7 @@ struct hp_domain {
 	unsigned long long* haz_words = nullptr;          // two words: [g & 1] == g <=> pair launch g stamped something
 	unsigned         pair_gen = 0;                    // number of the last pair launch -- the one that wrote the current state while facts->other_stale holds
 	// still records of the FAST fp64 pair kernel (hp_kernels.hpp: StillRec; round 8): two halves of windows x rows records, the last launch's
-	// in half still_rec_half, then two counters (hp_pair_stats).  Valid (facts->still_rec_valid) while no writer of either state buffer has run
+	// in half still_rec_half, then four counters (hp_pair_stats, hp_pair_wall_stats).  Valid (facts->still_rec_valid) while no writer of either state buffer has run
 	// since that launch other than such launches themselves
 	void*            still_rec = nullptr;
 	size_t           still_rec_slots = 0;             // records per half

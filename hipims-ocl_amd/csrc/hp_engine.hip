@@ -59,7 +59,7 @@ const PlanKnobs& plan_knobs()
 		k.two_step = num("HP_TWO_STEP", -1);
 		k.launch_tail = !off("HP_LAUNCH_TAIL"); k.strip_reduce_always = on("HP_STRIP_REDUCE_ALWAYS");
 		k.pair_bdy = !off("HP_PAIR_BDY"); k.pair_strict = !off("HP_PAIR_STRICT"); k.pair_exact = force("HP_PAIR_EXACT");
-		k.pair_skip = !off("HP_PAIR_SKIP"); k.fill_after_pairs = !off("HP_FILL_AFTER_PAIRS");
+		k.pair_skip = !off("HP_PAIR_SKIP"); k.pair_wall = !off("HP_PAIR_WALL"); k.fill_after_pairs = !off("HP_FILL_AFTER_PAIRS");
 		k.strict_speculate = on("HP_STRICT_SPECULATE"); k.pair_tune = !off("HP_PAIR_TUNE"); k.sweep_alternate = force("HP_SWEEP_ALTERNATE");
 		k.tail_max_blocks = (unsigned)num("HP_TAIL_MAX_BLOCKS", (int)TAIL_MAX_BLOCKS);
 		k.tail_max_blocks_k2k6 = (unsigned)num("HP_TAIL_MAX_BLOCKS_K2K6", (int)TAIL_MAX_BLOCKS);
@@ -703,6 +703,7 @@ template <typename T> int run_pair_t(hp_domain* d, const bool strip, const bool 
 		aux.still_in = d->facts->still_rec_valid ? base + (size_t)d->still_rec_half * d->still_rec_slots : nullptr;
 		aux.still_rows = d->desc.rows;
 	}
+	aux.wall = pair_wall_runs(knobs, recs) ? 1 : 0;
 	// block order (hp_order.hpp): the instantiation that writes records -- with or without them -- raises its flags and leaves a table; it
 	// reads the last one if that launch was the domain's flux launch just before this one, of this tiling (anything else: tile-row by tile-row)
 	const bool ordered = pair_order_on() && d->desc.precision == 8 && d->desc.math_mode != HP_MATH_STRICT && !strip && !bdy && !exact &&
@@ -2220,6 +2221,33 @@ int hp_kernel_timing_read(hp_domain_t* d, double* avg_ms, uint32_t* samples)
 	return HP_OK;
 }
 
+// the last pair launch's records by tag, counted on the device (still_rec_count): window rows skipped, recorded, and the same two for the
+// windows next to the edge ring alone
+static int still_rec_counts(hp_domain* d, unsigned long long host_counts[4])
+{
+	std::fill(host_counts, host_counts + 4, 0ull);
+	if (!d->still_rec || !d->still_rec_last) return HP_OK;
+	const StillRec* half = (const StillRec*)d->still_rec + (size_t)d->still_rec_half * d->still_rec_slots;
+	unsigned long long* counts = (unsigned long long*)((StillRec*)d->still_rec + 2 * d->still_rec_slots);
+	HIP_TRY(hipMemsetAsync(counts, 0, 32, d->stream));
+	hipLaunchKernelGGL(still_rec_count, dim3(256), dim3(256), 0, d->stream, half, d->still_rec_slots, counts);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(host_counts, counts, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(hipStreamSynchronize(d->stream));
+	return HP_OK;
+}
+
+int hp_pair_wall_stats(hp_domain_t* d, uint64_t out[2])
+{
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!out) return fail(HP_ERR_INVALID, "out == NULL");
+	unsigned long long counts[4];
+	if ((rc = still_rec_counts(d, counts)) != HP_OK) return rc;
+	out[0] = counts[2]; out[1] = counts[3];
+	return HP_OK;
+}
+
 int hp_pair_stats(hp_domain_t* d, uint64_t out[12])
 {
 	int rc = check_domain(d);
@@ -2231,15 +2259,9 @@ int hp_pair_stats(hp_domain_t* d, uint64_t out[12])
 	out[4] = d->tune_samples; out[5] = d->tune_switches; out[6] = d->tune_prefer_pairs ? 1 : 0;
 	out[7] = d->tune_single_ms > 0.f ? (uint64_t)(1000.0 * d->tune_pair_ms / d->tune_single_ms) : 0;
 	out[8] = out[9] = out[10] = out[11] = 0;
-	if (d->still_rec && d->still_rec_last) {                              // (counted on the device, as the stamps below)
-		const StillRec* half = (const StillRec*)d->still_rec + (size_t)d->still_rec_half * d->still_rec_slots;
-		unsigned long long* counts = (unsigned long long*)((StillRec*)d->still_rec + 2 * d->still_rec_slots);
-		HIP_TRY(hipMemsetAsync(counts, 0, 16, d->stream));
-		hipLaunchKernelGGL(still_rec_count, dim3(256), dim3(256), 0, d->stream, half, d->still_rec_slots, counts);
-		HIP_TRY(hipGetLastError());
-		unsigned long long host_counts[2] = {0, 0};
-		HIP_TRY(hipMemcpyAsync(host_counts, counts, sizeof host_counts, hipMemcpyDeviceToHost, d->stream));
-		HIP_TRY(hipStreamSynchronize(d->stream));
+	{                                                                     // (counted on the device, as the stamps below)
+		unsigned long long host_counts[4];
+		if ((rc = still_rec_counts(d, host_counts)) != HP_OK) return rc;
 		out[9] = host_counts[0]; out[10] = host_counts[1];
 	}
 	if (d->order_buf && d->order_read) {                                  // (the half the last pair launch read: the one it did not write)

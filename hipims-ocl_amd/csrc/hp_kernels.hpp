@@ -758,8 +758,10 @@ template <typename T> __device__ __forceinline__ State4<T> stamp_state(const Sta
 // the row's still state -- level and bed bits -- where the launch stored the row as it found it (a still run that raised no Zmax, or a
 // skipped tile), the sentinel (all-ones level bits: no wet, finite level has them) everywhere else.  `tag` tells the two kinds apart for
 // hp_pair_stats (STILL_TAG_*); the vote of the next launch reads the first 16 bytes only.
+// Windows next to the edge ring (round 19) record the state of their INTERIOR lanes: their ring lanes held the wall (godunov_march2:
+// wall_ok), which no launch writes and every launch that skips such a tile reads again.  Their rows carry tags of their own.
 struct StillRec { unsigned long long z, b; unsigned tag, pad[3]; };
-constexpr unsigned STILL_TAG_RUN = 1, STILL_TAG_SKIP = 2;
+constexpr unsigned STILL_TAG_RUN = 1, STILL_TAG_SKIP = 2, STILL_TAG_WALL_RUN = 3, STILL_TAG_WALL_SKIP = 4;
 template <typename T> struct PairAux {
 	StampBufs<T>          stamps;      // rec == nullptr: no stamps (nothing to look up, nothing written down).  (By value: kernel arguments are
 	                                   // uniform by construction -- loaded through a pointer the addresses came back as per-lane values and every
@@ -774,6 +776,7 @@ template <typename T> struct PairAux {
 	StillRec*             still_out;
 	const StillRec*       still_in;
 	long                  still_rows;
+	int                   wall;        // still water beside the edge ring is taken in runs and skipped too (HP_PAIR_WALL=0: as before round 19)
 	// (block order, hp_order.hpp; the still-record instantiation only) order_in: the table this launch's blocks take their tiles by, written
 	// by the tail block of the launch before -- nullptr: tile-row by tile-row; order_flags: one word per (band, group), in which this
 	// launch's marching waves count themselves and from which its tail block builds order_out -- nullptr: no counts, no table (HP_PAIR_ORDER=0).
@@ -1484,9 +1487,91 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	// still state s (wet, finite, discharge +0, Zmax neither raised nor disabled) and that the launch found the row in s in the buffer this
 	// launch writes.  Then this launch's source is s on the whole stencil, still_run would cover every row of the tile and store its source
 	// row as it is, and the destination holds those bits already: nothing to load, nothing to store.  Tiles next to the edge ring (whose
-	// rows and columns no launch writes) are never skipped.
+	// rows and columns no launch writes) have no such records for the ring's part: wall_tile_known, below.
+	// Still water beside the edge ring (round 19; WALL: the record instantiation).  A window next to the ring has the ring's cells in its
+	// stencil: lanes left of column 1 or right of column cols - 2 (lanes beyond the grid are clamped copies of the ring), rows 0 and
+	// rows - 1.  Every closed domain keeps a wall there -- a dry cell on a bed of 9999.9 -- that no launch ever writes, and the lake
+	// beside it marched identical bits to identical bits in every launch.  Whether a cell in the still state s stays in s next to a wall
+	// cell w is a question of s's and w's bits (hp_math.hpp: the half ulp of the wall that face_solve_fast keeps can survive the
+	// update's flush), so the wave ASKS, once, before any loop: it runs the march's own device functions, with this launch's two
+	// timesteps, on one lane per position a cell can have -- w to the west or east or neither, times w to the south or north or
+	// neither; -ffp-contract=off: the bits the march would produce -- and takes s for still beside w only if every position its window
+	// has returns s bit for bit at both steps.  (Without the friction term: it leaves a +0 discharge as it is whatever Manning's n, and
+	// a discharge that is not +0 has failed the test in front of it.)  s is what the window's first updated cell holds, w what the
+	// domain's corner cell holds: still_run and wall_tile_known hold every lane against the two.
+	constexpr bool WALL = RECS;
+	const long xw = strip * MARCH2_COLS - 1;                                       // lane 0's column
+	const bool near_w = xw < 1, near_e = xw + 63 > p.cols - 2, near_s = y0 - 2 < 1, near_n = y1 + 1 > last_row - 1;   // (wave-uniform)
+	const bool near_ring = near_w || near_e || near_s || near_n;
+	unsigned long long wall_z = 0, wall_b = 0, wall_qx = 0, wall_qy = 0;           // w's bits (wave-uniform)
+	bool wall_ok = false;
+	if constexpr (WALL) {
+		// (four cells across at least: a cell then has the wall on one side of an axis at most, which is all the positions above cover)
+		if (aux.wall != 0 && near_ring && !skip_a && !skip_b && p.cols >= 4 && p.rows >= 4) {
+			const size_t id_s = (size_t)y0 * p.cols + (size_t)(xw + 2);
+			const State4<T> cs = src[id_s], cw = src[0];
+			const T sz = first_lane(cs.z), sb = first_lane(bed[id_s]), wz = first_lane(cw.z), wb = first_lane(bed[0]);
+			const T wqx = first_lane(cw.qx), wqy = first_lane(cw.qy);
+			const bool s_fits = (sz - sb) > vs && (sz - sb) < T(1e100) && sz != T(-9999.0) && wave_all(value_bits(cs.qx) == 0 && value_bits(cs.qy) == 0);
+			if (s_fits && (wz - wb) < vs) {                                            // (wave-uniform) a wet, finite state at rest beside a dry wall
+				const int cx = lane % 3, cy = (lane / 3) % 3;                           // 0: the lake on both sides, 1: w to the west / south, 2: w to the east / north
+				const Side<T> sS = make_side<STRICT>(sz, T(0), T(0), sb, vs), sW = make_side<STRICT>(wz, wqx, wqy, wb, vs);
+				auto side_of = [&](const bool wall) {
+					Side<T> o;
+					o.eta = wall ? sW.eta : sS.eta; o.zb = wall ? sW.zb : sS.zb; o.qx = wall ? sW.qx : sS.qx; o.qy = wall ? sW.qy : sS.qy;
+					o.u0 = wall ? sW.u0 : sS.u0; o.v0 = wall ? sW.v0 : sS.v0;
+					return o;
+				};
+				const FaceFlux<T> fW = face_solve<AXIS_X, STRICT, true, true>(side_of(cx == 1), sS, vs).forR;
+				const FaceFlux<T> fE = face_solve<AXIS_X, STRICT, true, true>(sS, side_of(cx == 2), vs).forL;
+				const FaceFlux<T> fS = face_solve<AXIS_Y, STRICT, true, true>(side_of(cy == 1), sS, vs).forR;
+				const FaceFlux<T> fN = face_solve<AXIS_Y, STRICT, true, true>(sS, side_of(cy == 2), vs).forL;
+				State4<T> c0; c0.z = sz; c0.zmax = sz; c0.qx = T(0); c0.qy = T(0);
+				const State4<T> ua = godunov_update_impl<STRICT, false, true>(c0, sb, T(0), dt_a, fN, fE, fS, fW, p.dx, inv_dx, vs, false, (T*)nullptr, NoProbe(), ka);
+				const State4<T> ub = godunov_update_impl<STRICT, false, true>(c0, sb, T(0), dt_b, fN, fE, fS, fW, p.dx, inv_dx, vs, false, (T*)nullptr, NoProbe(), kb);
+				auto is_s = [&](const State4<T>& u) { return value_bits(u.z) == value_bits(sz) && value_bits(u.qx) == 0 && value_bits(u.qy) == 0; };
+				const bool met = (cx == 0 || (cx == 1 ? near_w : near_e)) && (cy == 0 || (cy == 1 ? near_s : near_n));
+				wall_ok = wave_all(!met || (is_s(ua) && is_s(ub)));
+				wall_z = value_bits(wz); wall_b = value_bits(wb); wall_qx = value_bits(wqx); wall_qy = value_bits(wqy);
+				still_kz = value_bits(sz); still_kb = value_bits(sb);
+			}
+		}
+	}
+	// A tile next to the ring is known (tile_known, below) when the records of the windows and rows that exist say so as for any tile, in
+	// the state the test above passed for, and the ring's part of the stencil -- read here: a column is one lane per row, a row one load --
+	// holds w.  (Both state buffers keep the ring they were uploaded with; reading this launch's source asks nothing of that.)
+	auto wall_tile_known = [&]() -> bool {
+		if (!wall_ok || y1 - y0 > 32) return false;
+		const int nr = (int)(y1 - y0) + 4, n = 3 * nr;
+		const long w_lo = strip > 0 ? strip - 1 : 0;
+		const __amdgpu_buffer_rsrc_t srd = make_srd(aux.still_in + (size_t)w_lo * aux.still_rows, (size_t)3 * aux.still_rows * sizeof(StillRec));
+		auto wanted = [&](const int i, long& win, long& row) {                     // entry i: window strip - 1 + i / nr, row y0 - 2 + i % nr, if both exist
+			const int w = i < nr ? 0 : (i < 2 * nr ? 1 : 2);
+			win = strip - 1 + w; row = y0 - 2 + (i - w * nr);
+			return i < n && win >= 0 && win < tm.nstrips && row >= 1 && row <= last_row - 1;
+		};
+		auto entry_ok = [&](const int i) {
+			long win, row;
+			const bool want = wanted(i, win, row);
+			const hp_u32x4 e = __builtin_amdgcn_raw_buffer_load_b128(srd, want ? (int)(unsigned)(((win - w_lo) * aux.still_rows + row) * (long)sizeof(StillRec)) : (int)HP_OOB, 0, 0);
+			return !want || ((((unsigned long long)e.y << 32) | e.x) == still_kz && (((unsigned long long)e.w << 32) | e.z) == still_kb);
+		};
+		const bool recs_ok = entry_ok(lane) && entry_ok(lane + 64);
+		auto is_w = [&](const long row, const long col) {
+			const size_t id = (size_t)row * p.cols + (size_t)col;
+			const State4<T> c = src[id];
+			return value_bits(c.z) == wall_z && value_bits(bed[id]) == wall_b && value_bits(c.qx) == wall_qx && value_bits(c.qy) == wall_qy;
+		};
+		bool ring_ok = true;
+		const long row_l = y0 - 2 + lane < 0 ? 0 : (y0 - 2 + lane > last_row ? last_row : y0 - 2 + lane);   // (lanes past the stencil's rows ask for nothing)
+		if (near_w) ring_ok = ring_ok && (lane >= nr || is_w(row_l, 0));
+		if (near_e) ring_ok = ring_ok && (lane >= nr || is_w(row_l, p.cols - 1));
+		if (near_s) ring_ok = ring_ok && is_w(0, xc);
+		if (near_n) ring_ok = ring_ok && is_w(last_row, xc);
+		return wave_all(recs_ok && ring_ok);
+	};
 	auto tile_known = [&]() -> bool {
-		const long xw = strip * MARCH2_COLS - 1;                                   // lane 0's column
+		if (WALL && near_ring) return wall_tile_known();
 		if (xw < 1 || xw + 63 > p.cols - 2 || y0 - 2 < 1 || y1 + 1 > last_row - 1 || y1 - y0 > 32) return false;
 		const int nr = (int)(y1 - y0) + 4, n = 3 * nr;                             // entries: window strip - 1 + w, row y0 - 2 + r  (<= 108)
 		const __amdgpu_buffer_rsrc_t srd = make_srd(aux.still_in + (size_t)(strip - 1) * aux.still_rows, (size_t)3 * aux.still_rows * sizeof(StillRec));
@@ -1802,6 +1887,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	// tile's start: the row-by-row skip of STRICT, or a vote on every row that could start a run mid-tile, costs this flavour's loop
 	// 14 % more vector instructions and 8-14 spilled registers; an outer loop that goes back and forth between the two spills 140 --
 	// compiler figures, LAB_NOTES R7.1.  In the dam break a window of columns is still for all its rows or for none.)
+	bool wall_run = false;                                                         // (WALL) the run was taken with the ring's lanes held against w: its records say so
 	auto still_run = [&]() -> long {
 		auto load_rz = [&](const long yl) {                                        // (rows beyond y1 + 1 are not loaded: they end the run)
 			unsigned vs_ = yl <= y1 + 1 ? voff_state : HP_OOB, vc_ = yl <= y1 + 1 ? voff_scalar : HP_OOB;
@@ -1816,19 +1902,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 		RowRegs<T> q[4];
 		#pragma unroll
 		for (int j = 0; j < 4; ++j) q[j] = load_rz(y - 2 + j);
-		const T z0 = first_lane(q[0].c.z), b0 = first_lane(q[0].zb), h0 = z0 - b0;
+		// (WALL, a window next to the edge ring whose still state passed wall_ok: that state, and every ring cell holds w instead)
+		const bool walled = WALL && wall_ok;
+		const T z0 = walled ? T(__longlong_as_double((long long)still_kz)) : first_lane(q[0].c.z);
+		const T b0 = walled ? T(__longlong_as_double((long long)still_kb)) : first_lane(q[0].zb), h0 = z0 - b0;
 		if (!(h0 > vs && h0 < T(1e100) && z0 != T(-9999.0))) return y;          // (wave-uniform) a wet, finite state
 		const unsigned long long run_z = value_bits(z0), run_b = value_bits(b0);
-		auto in_run = [&](const RowRegs<T>& q_) {
-			return wave_all(value_bits(q_.c.z) == run_z && value_bits(q_.zb) == run_b && value_bits(q_.c.qx) == 0 && value_bits(q_.c.qy) == 0 &&
-			                !(q_.c.zmax <= T(-9999.0))) != 0;
+		auto in_run = [&](const RowRegs<T>& q_, const long yl) {
+			const bool is_s = value_bits(q_.c.z) == run_z && value_bits(q_.zb) == run_b && value_bits(q_.c.qx) == 0 && value_bits(q_.c.qy) == 0 &&
+			                  !(q_.c.zmax <= T(-9999.0));
+			if constexpr (WALL) {
+				const bool is_w = value_bits(q_.c.z) == wall_z && value_bits(q_.zb) == wall_b && value_bits(q_.c.qx) == wall_qx && value_bits(q_.c.qy) == wall_qy;
+				const bool ring_cell = walled && (ring_x || yl <= 0 || yl >= last_row);
+				return wave_all(ring_cell ? is_w : is_s) != 0;
+			} else return wave_all(is_s) != 0;
 		};
-		if (!(in_run(q[0]) && in_run(q[1]) && in_run(q[2]) && in_run(q[3]))) return y;
+		if (!(in_run(q[0], y - 2) && in_run(q[1], y - 1) && in_run(q[2], y) && in_run(q[3], y + 1))) return y;
+		wall_run = walled;
 		const T spd = cfl_speed<STRICT>(q[2].c.z, q[2].c.zmax, q[2].c.qx, q[2].c.qy, q[2].zb, p.qs);
 		still_kz = run_z; still_kb = run_b;
 		auto put = [&](State4<T> c, const long yy) {
 			// (the record: the row leaves as it came -- no Zmax raised -- and prices as s does: no NaN Zmax, which cfl_speed reads as disabled)
-			if (RECS && !wave_any(!(c.zmax > T(-9999.0)) || (c.z > c.zmax && c.zmax > T(-9990.0)))) still_marks |= 1u << (unsigned)(yy - y0);
+			// (WALL: the ring lanes of a walled run are not the row's to answer for -- nothing stores or prices them)
+			if (RECS && !wave_any(!(WALL && walled && ring_x) && (!(c.zmax > T(-9999.0)) || (c.z > c.zmax && c.zmax > T(-9990.0))))) still_marks |= 1u << (unsigned)(yy - y0);
 			if (c.z > c.zmax && c.zmax > T(-9990.0)) c.zmax = c.z;                    // :375-376
 			const unsigned row_k = (unsigned)__builtin_amdgcn_readfirstlane((int)(yy - row_base));
 			buf_store_state(c, srd_dst, out_x ? voff_state : HP_OOB, row_k * row_state);
@@ -1840,13 +1936,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 			if (y >= y1) return y;
 			#pragma unroll
 			for (int j = 0; j < 4; ++j) q[j] = load_rz(y + 2 + j);
-			if (!in_run(q[0])) return y;
+			if (!in_run(q[0], y + 2)) return y;
 			put(a, y);
-			if (y + 1 >= y1 || !in_run(q[1])) return y + 1;
+			if (y + 1 >= y1 || !in_run(q[1], y + 3)) return y + 1;
 			put(b, y + 1);
-			if (y + 2 >= y1 || !in_run(q[2])) return y + 2;
+			if (y + 2 >= y1 || !in_run(q[2], y + 4)) return y + 2;
 			put(q[0].c, y + 2);
-			if (y + 3 >= y1 || !in_run(q[3])) return y + 3;
+			if (y + 3 >= y1 || !in_run(q[3], y + 5)) return y + 3;
 			put(q[1].c, y + 3);
 			a = q[2].c; b = q[3].c;
 			y += 4;
@@ -1854,7 +1950,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 	};
 
 	const long yb = (RUNS && !skip_a && !skip_b) ? still_run() : y0;              // the still rows at the tile's start, if any
-	write_recs(STILL_TAG_RUN);                                                     // (RECS; before the march: nothing of it lives into the loop)
+	write_recs(wall_run ? STILL_TAG_WALL_RUN : STILL_TAG_RUN);                                                   // (RECS; before the march: nothing of it lives into the loop)
 	if (!RUNS || yb < y1) {
 		// (block order) this wave marches: it counts itself in its group's word (no value comes back); nothing of it lives into the march
 		if constexpr (ORDERED) { if (order_word != nullptr && lane == 0) __hip_atomic_fetch_add(order_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1900,7 +1996,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 		// (round 8) the tile is skipped: its records say so again for the launch after this one, and the state prices as still_run would
 		// price it -- one speed in every updated lane, if any of the tile's rows is priced at all
 		still_marks = ~0u;
-		write_recs(STILL_TAG_SKIP);
+		write_recs(WALL && near_ring ? STILL_TAG_WALL_SKIP : STILL_TAG_SKIP);
 		if (CFL_MODE == 1 && out_x && (int)y1 > tm.price_lo && (int)y0 < tm.price_hi)
 			vmax = cfl_speed<STRICT>(T(__longlong_as_double((long long)still_kz)), T(0), T(0), T(0), T(__longlong_as_double((long long)still_kb)), p.qs);
 		vmax1 = vmax;
@@ -1945,16 +2041,24 @@ __global__ __launch_bounds__(256) void stamps_count(const StampBufs<T> b, const 
 	for (int off = 32; off > 0; off >>= 1) { last += __shfl_down(last, off); any += __shfl_down(any, off); }
 	if ((threadIdx.x & 63) == 0 && (last | any)) { atomicAdd(counts, last); atomicAdd(counts + 1, any); }
 }
-// hp_pair_stats: window rows the last pair launch skipped (its records tagged STILL_TAG_SKIP) and window rows it recorded as found (either tag)
+// hp_pair_stats: window rows the last pair launch skipped (its records tagged STILL_TAG_SKIP or STILL_TAG_WALL_SKIP) and window rows it recorded as found (any tag)
 __global__ __launch_bounds__(256) void still_rec_count(const StillRec* __restrict__ rec, const size_t n, unsigned long long* counts)
 {
-	unsigned long long skipped = 0, still = 0;
+	// (counts[2], counts[3]: the same two figures for the rows of windows next to the edge ring alone -- they are part of the first two)
+	unsigned long long skipped = 0, still = 0, wall_skipped = 0, wall_still = 0;
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const unsigned tag = rec[i].tag;
-		skipped += (tag == STILL_TAG_SKIP); still += (tag == STILL_TAG_SKIP || tag == STILL_TAG_RUN);
+		wall_skipped += (tag == STILL_TAG_WALL_SKIP); wall_still += (tag == STILL_TAG_WALL_SKIP || tag == STILL_TAG_WALL_RUN);
+		skipped += (tag == STILL_TAG_SKIP || tag == STILL_TAG_WALL_SKIP); still += (tag >= STILL_TAG_RUN && tag <= STILL_TAG_WALL_SKIP);
 	}
-	for (int off = 32; off > 0; off >>= 1) { skipped += __shfl_down(skipped, off); still += __shfl_down(still, off); }
-	if ((threadIdx.x & 63) == 0 && (skipped | still)) { atomicAdd(counts, skipped); atomicAdd(counts + 1, still); }
+	for (int off = 32; off > 0; off >>= 1) {
+		skipped += __shfl_down(skipped, off); still += __shfl_down(still, off);
+		wall_skipped += __shfl_down(wall_skipped, off); wall_still += __shfl_down(wall_still, off);
+	}
+	if ((threadIdx.x & 63) == 0 && (skipped | still)) {
+		atomicAdd(counts, skipped); atomicAdd(counts + 1, still);
+		if (wall_still) { atomicAdd(counts + 2, wall_skipped); atomicAdd(counts + 3, wall_still); }
+	}
 }
 // hp_pair_stats: entries of the block-order table the last pair launch read that differ from the order without a hint (hp_order.hpp)
 __global__ __launch_bounds__(256) void order_count(const unsigned* __restrict__ table, const unsigned groups, const unsigned per_band, const unsigned n,

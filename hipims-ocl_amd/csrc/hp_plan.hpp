@@ -28,6 +28,7 @@ struct PlanKnobs {
 	bool     pair_strict = true;               // HP_PAIR_STRICT=0: the exact mode does not pair
 	int      pair_exact = -1;                  // HP_PAIR_EXACT: 1 every pair keeps quirk Q3 exact, 0 none
 	bool     pair_skip = true;                 // HP_PAIR_SKIP=0: no still records, nothing skipped
+	bool     pair_wall = true;                 // HP_PAIR_WALL=0: still water beside the edge ring marches (pair_wall_runs)
 	bool     fill_after_pairs = true;          // HP_FILL_AFTER_PAIRS=0: the device copy instead of K1's FILL flag
 	bool     strict_speculate = false;         // HP_STRICT_SPECULATE=1: speculative STRICT fp64 batches
 	bool     pair_tune = true;                 // HP_PAIR_TUNE=0: the exact mode always pairs where eligible
@@ -167,6 +168,9 @@ inline bool pair_records(const PlanDomain& d, const PlanKnobs& k, const bool str
 {
 	return d.precision == 8 && k.pair_skip && !strip && !d.has_bdy && !exact && d.math_mode != HP_MATH_STRICT && tile_rows <= 32;
 }
+// ... and among those launches, whether windows next to the edge ring take their still water in runs and skip it (hp_kernels.hpp: wall_ok):
+// part of the records, so HP_PAIR_SKIP=0 switches it off with them; HP_PAIR_WALL=0 switches off this part alone.
+inline bool pair_wall_runs(const PlanKnobs& k, const bool records) { return records && k.pair_wall; }
 
 // after iteration pairs the non-current buffer is out of date; K1 brings it up to date by itself (its FILL flag: every cell of the
 // launch's rows is stored), any other kernel gets the device copy first

@@ -59,7 +59,7 @@ EXPORTS = [
     "hp_strip_comm_destroy", "hp_strip_info", "hp_strip_peer_ticket", "hp_strip_peer_connect", "hp_strip_peer_round",
     "hp_strip_peer_disconnect", "hp_timer_start",
     "hp_timer_stop", "hp_kernel_timing", "hp_kernel_timing_read", "hp_kernel_timing_overhead",
-    "hp_launch_counts", "hp_pair_stats",
+    "hp_launch_counts", "hp_pair_stats", "hp_pair_wall_stats",
 ]
 
 
@@ -1266,6 +1266,15 @@ class Domain:
         return dict(pairs=out[0], cold_starts=out[1], stamped_last=out[2], stamped_ever=out[3], tune_samples=out[4],
                     tune_switches=out[5], prefers_pairs=bool(out[6]), pair_over_single=out[7] / 1000.0, stale_used=out[8],
                     skipped_rows=out[9], still_rows=out[10], reordered_tiles=out[11])
+
+    def pair_wall_stats(self):
+        """(window rows next to the edge ring that the last pair launch skipped, such rows it recorded as still): hp_pair_wall_stats."""
+        if not hasattr(self.lib, "hp_pair_wall_stats"):      # (absent from older builds loaded through HIPIMS_MI_LIB for A/B runs)
+            return None
+        out = (C.c_uint64 * 2)()
+        self.lib.hp_pair_wall_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        _check(self.lib, self.lib.hp_pair_wall_stats(self.h, out), "hp_pair_wall_stats")
+        return out[0], out[1]
 
     def kernel_timing_overhead(self):
         """Cost of an empty event pair (ms) that kernel_timing_read() has taken off every sample (0.0 with a library that

@@ -901,6 +901,7 @@ int hp_kernel_timing_overhead(hp_domain_t* d, double* overhead_ms);
  *                        the same bits)                    HP_PAIR_EXACT=0 / 1   the exact flavour nowhere / everywhere
  *   HP_PAIR_BDY=0        domains with area boundaries keep single iterations      HP_PAIR_STRICT=0   so does STRICT arithmetic
  *   HP_PAIR_SKIP=0       FAST fp64 pairs keep no still records and skip no tiles (the same bits; A/B runs)
+ *   HP_PAIR_WALL=0       ... keep them, but march the still water in the windows next to the edge ring (the same bits; A/B runs)
  *   HP_PAIR_ORDER=0      the same launches start their tiles tile-row by tile-row, not the column groups that marched last time first
  *                        (the same bits; A/B runs)
  * hp_launch_counts and hp_pair_stats show what ran. */
@@ -923,6 +924,12 @@ int hp_launch_counts(hp_domain_t* d, uint64_t* flux_launches, uint64_t* with_tai
  * block order; HP_PAIR_ORDER=0 switches it off) tiles the LAST pair launch ran at another position of its band's block stream than
  * tile-row by tile-row order gives them -- 0 where no column group, or every one alike, marched in the launch before, or no table was read. */
 int hp_pair_stats(hp_domain_t* d, uint64_t out[12]);
+/* The part of out[9] and out[10] that lies in windows next to the edge ring (a window's 60 columns plus its two halo columns either
+ * side reach column 0 or cols - 1, or its tile's stencil reaches row 0 or rows - 1): out[0] such window rows the LAST pair launch skipped,
+ * out[1] such rows it recorded as still.  There the lake is at rest beside the wall every closed domain has -- dry cells on a high bed
+ * that no launch writes -- and the launch has checked, with its own update on its own two timesteps, that this lake stays as it is
+ * beside this wall.  HP_PAIR_WALL=0 switches that part off alone (the same bits; A/B runs), HP_PAIR_SKIP=0 with the rest.  Blocks. */
+int hp_pair_wall_stats(hp_domain_t* d, uint64_t out[2]);
 
 #ifdef __cplusplus
 }
