@@ -18,6 +18,7 @@ static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, 
 static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
 static_assert(sizeof(hp_soil_class_t) == 32 && sizeof(hp_infiltration_desc_t) == 32, "hp_soil_class_t / hp_infiltration_desc_t layout");
 static_assert(sizeof(hp_tracer_desc_t) == 16, "hp_tracer_desc_t layout");
+static_assert(sizeof(hp_open_segment_t) == 24 && sizeof(hp_open_record_t) == 32 && sizeof(OpenDev) == 24, "hp_open_*_t layout");
 
 // ---- the boundaries ----
 // an area boundary as the kernels read it: the stand-alone pass and the fused one are handed the same descriptor
@@ -56,6 +57,12 @@ template <typename T> int apply_boundaries(hp_domain* d, void* target)
 			flush();
 			hipLaunchKernelGGL(bdy_links<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
 			                   (const LinkDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->links.records + b.entries);
+			continue;
+		}
+		if (b.kind == BDY_OPEN) {
+			flush();
+			hipLaunchKernelGGL(bdy_open<T>, dim3((unsigned)((b.count + 63) / 64)), dim3(64), 0, d->stream, p, (const Scalars<T>*)d->scalars,
+			                   (const OpenDev*)b.cells, (unsigned long long)b.count, (State4<T>*)target, (const T*)d->bed, d->open.records + b.entries);
 			continue;
 		}
 		if (b.kind == BDY_INFILTRATION) {
@@ -272,6 +279,65 @@ int soil_restore(hp_domain* d)
 	return HP_OK;
 }
 
+// ---- the open boundary (hp_open.hpp): what a checkpoint and hp_boundary_clear do for its records ----
+void open_destroy(hp_domain* d)
+{
+	OpenStore& O = d->open;
+	hipFree(O.records); hipFree(O.saved);
+	O.records = nullptr; O.saved = nullptr;
+	O.room = O.saved_room = 0;
+}
+// hp_boundary_clear (the stream is idle): the segments go with the list, and their records with them
+int open_clear(hp_domain* d)
+{
+	OpenStore& O = d->open;
+	if (!O.segments) return HP_OK;
+	hipFree(O.records);
+	O.records = nullptr;
+	O.room = 0;
+	O.segments = 0;
+	O.cells = 0;
+	O.taken.clear();
+	++O.epoch;
+	return HP_OK;
+}
+// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+int open_save_reserve(hp_domain* d)
+{
+	OpenStore& O = d->open;
+	if (!O.cells || O.cells <= O.saved_room) return HP_OK;
+	hp_open_record_t* grown = nullptr;
+	int rc = alloc_or_fail((void**)&grown, (size_t)O.cells * sizeof(hp_open_record_t), "hp_state_save: cannot allocate the copy of the open boundary's records: ");
+	if (rc != HP_OK) return rc;
+	if (O.saved) {
+		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
+		hipFree(O.saved);
+	}
+	O.saved = grown;
+	O.saved_room = O.cells;
+	return HP_OK;
+}
+int open_save(hp_domain* d)
+{
+	OpenStore& O = d->open;
+	O.saved_taken = true;
+	O.saved_epoch = O.epoch;
+	if (O.cells) HIP_TRY(hipMemcpyAsync(O.saved, O.records, (size_t)O.cells * sizeof(hp_open_record_t), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+int open_restore(hp_domain* d)
+{
+	OpenStore& O = d->open;
+	if (!O.saved_taken) return HP_OK;
+	if (O.saved_epoch != O.epoch) {                                           // (the links' rule)
+		log_line(HP_LOG_WARNING, "hp_state_restore: open segments were added or cleared after the state was saved: the open boundary's records start from zero");
+		if (O.cells) HIP_TRY(hipMemsetAsync(O.records, 0, (size_t)O.cells * sizeof(hp_open_record_t), d->stream));
+		return HP_OK;
+	}
+	if (O.cells) HIP_TRY(hipMemcpyAsync(O.records, O.saved, (size_t)O.cells * sizeof(hp_open_record_t), hipMemcpyDeviceToDevice, d->stream));
+	return HP_OK;
+}
+
 // ---- the tracer (hp_tracer.hpp): its launches in front of the flux kernel, and what a checkpoint does for M ----
 // One iteration's tracer: the sources onto the current M, then the step from it into the other buffer, which becomes the current one.
 // `source`: the state buffer the flux launch of this iteration reads (the boundaries have been applied to it)
@@ -333,6 +399,7 @@ int actors_save_reserve(hp_domain* d)
 	int rc = bed_save_reserve(d);
 	if (rc == HP_OK) rc = links_save_reserve(d);
 	if (rc == HP_OK) rc = soil_save_reserve(d);
+	if (rc == HP_OK) rc = open_save_reserve(d);
 	return rc != HP_OK ? rc : tracer_save_reserve(d);
 }
 int actors_save(hp_domain* d)
@@ -340,6 +407,7 @@ int actors_save(hp_domain* d)
 	int rc = bed_save(d);
 	if (rc == HP_OK) rc = links_save(d);
 	if (rc == HP_OK) rc = soil_save(d);
+	if (rc == HP_OK) rc = open_save(d);
 	return rc != HP_OK ? rc : tracer_save(d);
 }
 int actors_restore(hp_domain* d)
@@ -347,9 +415,10 @@ int actors_restore(hp_domain* d)
 	int rc = bed_restore(d);
 	if (rc == HP_OK) rc = links_restore(d);
 	if (rc == HP_OK) rc = soil_restore(d);
+	if (rc == HP_OK) rc = open_restore(d);
 	return rc != HP_OK ? rc : tracer_restore(d);
 }
-void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); tracer_destroy(d); }
+void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); open_destroy(d); tracer_destroy(d); }
 
 } // namespace
 
@@ -582,6 +651,7 @@ int hp_boundary_clear(hp_domain_t* d)
 	d->bdy_on_ring = false;
 	if ((rc = links_clear(d)) != HP_OK) return rc;
 	if ((rc = soil_clear(d)) != HP_OK) return rc;
+	if ((rc = open_clear(d)) != HP_OK) return rc;
 	return refresh_fusable(d);
 }
 
@@ -728,6 +798,95 @@ int hp_infiltration_info(hp_domain_t* d, uint32_t* classes, uint64_t* pervious_c
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	if (classes) *classes = d->soil.classes;
 	if (pervious_cells) *pervious_cells = d->soil.pervious;
+	return HP_OK;
+}
+
+// ---- the open boundary (hp_open.hpp) ----
+int hp_boundary_add_open(hp_domain_t* d, const hp_open_segment_t* segments, uint32_t count)
+{
+	// argument checks first: none of them touches the device (hp_open.hpp: validate_open)
+	const std::string who = "hp_boundary_add_open";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	OpenStore& O = d->open;
+	const int64_t cols = d->desc.cols, grows = d->desc.global_rows;
+	std::vector<uint64_t> taken;
+	std::string why;
+	if (!validate_open(segments, count, O.segments, cols, grows, O.taken, taken, why)) return fail(HP_ERR_INVALID, why);
+	if (d->desc.scheme != HP_SCHEME_GODUNOV)
+		return fail(HP_ERR_UNSUPPORTED, who + ": the record of an open cell is the Godunov scheme's face flux; this domain runs another scheme");
+	// a strip with two reaches of ghost rows holds the outer one on every second iteration only: the records there would drift from their owners'
+	if (d->ghost_rows > stencil_reach(d->desc) && (d->desc.row_offset > 0 || d->desc.row_offset + d->desc.rows < d->desc.global_rows))
+		return fail(HP_ERR_UNSUPPORTED, who + ": this strip stores two reaches of ghost rows, the outer one valid on every second iteration only: "
+		            "the ring cells there would take stale neighbours (exchange after every iteration instead)");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	// this strip's share: the ring cells whose row lies in its local array, ghost rows included (open_strip_keeps); every cell has its record slot
+	const int64_t lo = d->desc.row_offset, hi = d->desc.row_offset + d->desc.rows;
+	std::vector<OpenDev> dev;
+	for (uint32_t k = 0; k < count; ++k)
+		for (int64_t at = segments[k].first; at <= segments[k].last; ++at) {
+			const OpenPlace pl = open_place(segments[k].edge, at, cols, grows);
+			OpenDev o;
+			o.edge = segments[k].edge; o.pad = 0;
+			if (open_strip_keeps(pl.ry, pl.iy, lo, hi)) {
+				o.r = (unsigned long long)((pl.ry - lo) * cols + pl.rx);
+				o.i = (unsigned long long)((pl.iy - lo) * cols + pl.ix);
+			} else {
+				o.r = o.i = OPEN_ABSENT;
+			}
+			dev.push_back(o);
+		}
+	const uint64_t n = dev.size(), total = O.cells + n;
+	// everything it needs first: if any of it cannot be had, the domain stays as it is
+	hp_open_record_t* records = nullptr;
+	void* cells = nullptr;
+	if ((rc = alloc_or_fail((void**)&records, (size_t)total * sizeof(hp_open_record_t), who + ": cannot allocate the records: ")) != HP_OK) return rc;
+	if ((rc = alloc_or_fail(&cells, (size_t)n * sizeof(OpenDev), who + ": cannot allocate the cells: ")) != HP_OK) { hipFree(records); return rc; }
+	// the records there are move over; the new cells' start from zero.  Queued iterations still write the old block: in stream order
+	hipError_t e = hipMemcpyAsync(cells, dev.data(), (size_t)n * sizeof(OpenDev), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess && O.cells) e = hipMemcpyAsync(records, O.records, (size_t)O.cells * sizeof(hp_open_record_t), hipMemcpyDeviceToDevice, d->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(records + O.cells, 0, (size_t)n * sizeof(hp_open_record_t), d->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (`dev` goes with this call; the old block is free behind it)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		hipFree(records); hipFree(cells);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the cells: " + hipGetErrorString(e));
+	}
+	hipFree(O.records);
+	O.records = records;
+	O.room = total;
+	Boundary b{};
+	b.kind = BDY_OPEN; b.cells = cells; b.count = n; b.entries = O.cells;
+	d->facts.boundaries_or_bed_changed();
+	d->bdy.push_back(b);
+	d->bdy_on_ring = true;                                                    // ring cells change on every iteration: the ring is priced anew (plan_single)
+	O.cells = total;
+	O.segments += count;
+	O.taken.swap(taken);
+	++O.epoch;
+	return refresh_fusable(d);
+}
+
+int hp_open_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_open_record_t* out)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (first > d->open.cells || count > d->open.cells - first) return fail(HP_ERR_INVALID, "hp_open_read: first + count beyond the domain's open cells");
+	if (count == 0) return HP_OK;
+	if (!out) return fail(HP_ERR_INVALID, "hp_open_read: out == NULL");
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (d->in_step) return fail(HP_ERR_STATE, "hp_open_read between hp_step_begin and hp_step_end");
+	HIP_TRY(hipMemcpyAsync(out, d->open.records + first, (size_t)count * sizeof(hp_open_record_t), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+
+int hp_open_info(hp_domain_t* d, uint32_t* segments, uint64_t* cells)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	if (segments) *segments = d->open.segments;
+	if (cells) *cells = d->open.cells;
 	return HP_OK;
 }
 

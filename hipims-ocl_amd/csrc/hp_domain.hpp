@@ -17,6 +17,7 @@
 #include "hp_bed.hpp"
 #include "hp_links.hpp"
 #include "hp_soil.hpp"
+#include "hp_open.hpp"
 #include "hp_tracer.hpp"
 #include <rccl/rccl.h>          // types and prototypes only: the library itself is dlopen'ed (hp_comm_load)
 
@@ -87,7 +88,8 @@ inline long stencil_reach(const hp_domain_desc_t& desc) { return desc.scheme == 
 // ---- the actors' state (their code: hp_actors.hpp) ----
 // a boundary, in the order added.  The first two are the AREA boundaries (AreaBdy, hp_kernels.hpp): consecutive ones share a launch
 enum BoundaryKind { BDY_UNIFORM, BDY_GRIDDED, BDY_CELL, BDY_LINKS,           // BDY_LINKS: cells is its LinkDev array, entries its first record
-                    BDY_INFILTRATION };                                       // BDY_INFILTRATION: everything of it is the domain's SoilStore
+                    BDY_INFILTRATION,                                         // BDY_INFILTRATION: everything of it is the domain's SoilStore
+                    BDY_OPEN };                                               // BDY_OPEN: cells is its OpenDev array, entries its first record
 struct Boundary {
 	BoundaryKind kind;
 	int      definition;
@@ -190,6 +192,21 @@ struct SoilStore {
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's F belongs to one epoch
 	double*          saved = nullptr;                 // hp_state_save's copy of F
 	bool             saved_taken = false;             // a checkpoint exists (with or without infiltration) ...
+	uint64_t         saved_epoch = 0;                 // ... of this epoch
+};
+
+// the open boundary (hp_open.hpp; hp_boundary_add_open): its calls are Boundary entries of kind BDY_OPEN, in the order added; this is what
+// they share.  Nothing of it exists while the domain has never had an open segment
+struct OpenStore {
+	uint32_t         segments = 0;
+	uint64_t         cells = 0;                       // listed ring cells of all segments (of the GLOBAL grid: a strip has a record slot for each)
+	hp_open_record_t* records = nullptr;              // device: `room` records, by segment in the order added, by ascending index inside one
+	uint64_t         room = 0;
+	std::vector<uint64_t> taken;                      // GLOBAL ids of every listed ring cell, sorted: the repeated-cell check
+	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's records belong to one epoch
+	hp_open_record_t* saved = nullptr;                // hp_state_save's copy (`saved_room` records)
+	uint64_t         saved_room = 0;
+	bool             saved_taken = false;             // a checkpoint exists (with or without segments) ...
 	uint64_t         saved_epoch = 0;                 // ... of this epoch
 };
 
@@ -338,6 +355,7 @@ struct hp_domain {
 	BedShapes        beds;
 	LinkStore        links;
 	SoilStore        soil;
+	OpenStore        open;
 	TracerStore      tracer;
 };
 

@@ -84,7 +84,7 @@ PlanDomain plan_domain(const hp_domain* d)
 	p.has_tail_words = d->tail_words != nullptr; p.tail_allowed = d->tail_allowed; p.halo_overlap = d->halo_overlap; p.split_now = d->split_now;
 	p.strip_any_bdy = d->strip_any_bdy; p.strip_first = d->strip_first; p.strip_any_full = d->strip_any_full;
 	p.spec_now = d->spec_now; p.has_stamps = d->z_state != nullptr; p.march2_pays = d->tiling.march2_pays;
-	p.has_links = d->links.groups != 0; p.soil_on = d->soil.on; p.tracer_on = d->tracer.on;
+	p.has_links = d->links.groups != 0; p.soil_on = d->soil.on; p.tracer_on = d->tracer.on; p.open_on = d->open.segments != 0;
 #ifdef HP_KEEP_SPEC_FUSED
 	p.spec_fused_kept = true;                                             // (launch_march: the instantiation kept buildable for study)
 #endif

@@ -57,7 +57,7 @@ struct PlanDomain {
 	bool     spec_now = false;
 	bool     has_stamps = false;               // the stamps' buffers exist (z_state)
 	bool     march2_pays = false;              // hp_tiling.hpp: the pair launch is at least two rounds of blocks at 12-row tiles
-	bool     has_links = false, soil_on = false, tracer_on = false;
+	bool     has_links = false, soil_on = false, tracer_on = false, open_on = false;
 	bool     spec_fused_kept = false;          // the library was built with -DHP_KEEP_SPEC_FUSED
 };
 
@@ -195,8 +195,10 @@ inline bool spec_wanted(const PlanDomain& d, const PlanKnobs& k, const uint32_t 
 	// register allocator is lucky: such domains run the plain STRICT kernels.
 	const bool fusable_ok = d.spec_fused_kept || !d.fusable;
 	// Never with link groups: the batch that is queued again after a raised word would count their records twice.  Nor with an
-	// infiltration: it would add to F twice.  Nor with a tracer: it would move M twice.
+	// infiltration: it would add to F twice.  Nor with a tracer: it would move M twice.  Nor with an open boundary: it would add to its
+	// records' volume twice.
 	return k.strict_speculate && n >= SPEC_MIN && d.math_mode == HP_MATH_STRICT && d.precision == 8 && !d.has_comm && fusable_ok && !d.has_links && !d.soil_on && !d.tracer_on &&
+	       !d.open_on &&
 	       d.kernel != HP_KERNEL_BASIC && (d.scheme == HP_SCHEME_GODUNOV || d.scheme == HP_SCHEME_MUSCL_HANCOCK);
 }
 // The exact mode chooses between pairs and single iterations by measurement (hp_engine.hip: run_iterations, tuner_poll).

@@ -51,7 +51,7 @@ EXPORTS = [
     "hp_zones_enable", "hp_zones_disable", "hp_zones_reset", "hp_zones_sample", "hp_zones_read", "hp_zones_info",
     "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info",
-    "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_clear", "hp_boundaries_fused",
+    "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_add_open", "hp_open_read", "hp_open_info", "hp_boundary_clear", "hp_boundaries_fused",
     "hp_tracer_enable", "hp_tracer_disable", "hp_tracer_add_source", "hp_tracer_sources_clear", "hp_tracer_read", "hp_tracer_write", "hp_tracer_info", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
@@ -175,6 +175,38 @@ def pack_links(links, cols):
     return out
 
 
+EDGE_SOUTH, EDGE_NORTH, EDGE_WEST, EDGE_EAST = 0, 1, 2, 3      # HP_EDGE_*
+EDGES = {"south": EDGE_SOUTH, "north": EDGE_NORTH, "west": EDGE_WEST, "east": EDGE_EAST}
+# hp_open_segment_t and hp_open_record_t as NumPy records: arrays of them go through the ABI as they are
+OPEN_SEGMENT_DTYPE = np.dtype([("edge", np.int32), ("reserved", np.int32), ("first", np.int64), ("last", np.int64)])
+OPEN_RECORD_DTYPE = np.dtype([("q_last", np.float64), ("volume", np.float64), ("active", np.uint64), ("reserved", np.uint64)])
+
+
+def pack_open_segments(segments, cols, global_rows):
+    """Segments of the edge ring as an array of OPEN_SEGMENT_DTYPE.  `segments`: such an array, or a sequence of dicts(edge, first, last)
+    / tuples (edge, first, last) / bare edges, where an edge is an HP_EDGE_* code or its name; first and last are GLOBAL indices along the
+    edge (the column for south and north, the row for west and east), inclusive, and default to the whole edge without its corners."""
+    if isinstance(segments, np.ndarray) and segments.dtype == OPEN_SEGMENT_DTYPE:
+        return np.ascontiguousarray(segments).reshape(-1)
+    if isinstance(segments, (str, int, np.integer, dict)):
+        segments = [segments]
+    out = np.zeros(len(segments), OPEN_SEGMENT_DTYPE)
+    for k, s in enumerate(segments):
+        if isinstance(s, (str, int, np.integer)):
+            s = dict(edge=s)
+        s = dict(s) if isinstance(s, dict) else dict(zip(("edge", "first", "last"), s))
+        edge = s["edge"]
+        if isinstance(edge, str):
+            if edge.lower() not in EDGES:
+                raise ValueError(f"segment {k}: unknown edge {edge!r}")
+            edge = EDGES[edge.lower()]
+        n = int(cols) if int(edge) in (EDGE_SOUTH, EDGE_NORTH) else int(global_rows)
+        first = 1 if s.get("first") is None else int(s["first"])
+        last = n - 2 if s.get("last") is None else int(s["last"])
+        out[k] = (int(edge), int(s.get("reserved", 0)), first, last)
+    return out
+
+
 # hp_soil_class_t as a NumPy record, and hp_infiltration_desc_t
 SOIL_CLASS_DTYPE = np.dtype([("ks", np.float64), ("suction", np.float64), ("deficit", np.float64), ("capacity", np.float64)])
 
@@ -289,6 +321,10 @@ def load_library(path: str | None = None):
         lib.hp_boundary_add_infiltration.argtypes = [C.c_void_p, C.POINTER(InfiltrationDesc)]
         lib.hp_infiltration_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_infiltration_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_boundary_add_open"):            # (absent from older builds, as above)
+        lib.hp_boundary_add_open.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.hp_open_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.hp_open_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     if hasattr(lib, "hp_tracer_enable"):                # (absent from older builds, as above)
         lib.hp_tracer_enable.argtypes = [C.c_void_p, C.POINTER(TracerDesc)]
         lib.hp_tracer_disable.argtypes = [C.c_void_p]
@@ -1006,6 +1042,29 @@ class Domain:
         count = self.links_info()["links"] - first if count is None else count
         out = np.zeros(count, LINK_RECORD_DTYPE)
         _check(self.lib, self.lib.hp_links_read(self.h, first, count, out.ctypes.data_as(C.c_void_p)), "hp_links_read")
+        self.sync()
+        return out
+
+    def add_open(self, segments):
+        """The open boundary (hp_boundary_add_open): every ring cell of the segments takes the depth and the outward momentum of its
+        inward neighbour once per iteration, at its place in the order the boundaries were added, and records the discharge that leaves
+        through its face.  `segments`: see pack_open_segments -- dict(edge="east", first=.., last=..), or just "east" for the whole
+        edge; indices are GLOBAL.  frontend.Open is the same arithmetic on the host, bit for bit."""
+        a = pack_open_segments(segments, self.cols, int(self.desc.global_rows) or self.rows)
+        _check(self.lib, self.lib.hp_boundary_add_open(self.h, a.ctypes.data_as(C.c_void_p), a.size), "hp_boundary_add_open")
+
+    def open_info(self):
+        """dict(segments, cells): host counters."""
+        n, c = C.c_uint32(0), C.c_uint64(0)
+        _check(self.lib, self.lib.hp_open_info(self.h, C.byref(n), C.byref(c)), "hp_open_info")
+        return dict(segments=n.value, cells=c.value)
+
+    def open_read(self, first=0, count=None):
+        """The open cells' records as an array of OPEN_RECORD_DTYPE (q_last, volume, active): by segment in the order added, by
+        ascending index inside a segment; blocks."""
+        count = self.open_info()["cells"] - first if count is None else count
+        out = np.zeros(count, OPEN_RECORD_DTYPE)
+        _check(self.lib, self.lib.hp_open_read(self.h, first, count, out.ctypes.data_as(C.c_void_p)), "hp_open_read")
         self.sync()
         return out
 

@@ -121,6 +121,7 @@ class Configuration:
     bed_shapes: list = field(default_factory=list)  # dict(name, cells [(x, y)], target [n], series [m, 2]): <bedShape> elements
     links: list = field(default_factory=list)      # dict(a (x, y), b (x, y), kind, one_way, level, size, coeff, limit): rows of the <links> elements' mapFiles
     soil_classes: list = field(default_factory=list)  # dict(ks, suction, deficit, capacity): rows of the <soilClasses> element's source; the id raster is the "soil" data source
+    open_edges: list = field(default_factory=list)  # dict(edge, name, first, last): <domainEdge treatment="open"> elements; first / last None = the whole edge
     tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2]): <tracerSource> elements; the initial M is the "tracer" data source
 
 
@@ -213,6 +214,15 @@ def parse_configuration(xml_path):
         for e in bc.findall("domainEdge"):
             if (e.get("treatment") or "").lower() == "closed":
                 cfg.closed_edges.add((e.get("edge") or "").lower())
+            # the open boundary (no reference counterpart): <domainEdge edge="east" treatment="open" name="outlet" from="8" to="23"/>,
+            # from / to: indices along the edge, inclusive; without them the whole edge (its corners excepted)
+            elif (e.get("treatment") or "").lower() == "open":
+                edge = (e.get("edge") or "").lower()
+                if edge not in ("north", "south", "east", "west"):
+                    raise ValueError(f"unknown domainEdge {edge!r}")
+                cfg.open_edges.append(dict(edge=edge, name=e.get("name") or f"{edge}{len(cfg.open_edges)}",
+                                           first=None if e.get("from") is None else int(e.get("from")),
+                                           last=None if e.get("to") is None else int(e.get("to"))))
         for ts in bc.findall("timeseries"):
             kind = (ts.get("type") or "").lower()
             series = _read_csv(os.path.join(bdir, ts.get("source")))
@@ -895,6 +905,170 @@ class Links:
         self.active = self.active + move.astype(np.uint64)
         self.applies += 1
         return int(move.sum())
+
+
+class Open:
+    """The open boundary on the host (hp_boundary_add_open restated in NumPy, in exactly the operation order of csrc/hp_open.hpp:
+    open_impose and open_record): segments of the edge ring whose cells take the depth and the outward momentum of their inward
+    neighbours and record the discharge that leaves through their faces.  `apply` acts in place on state[rows, cols, 4], the
+    iteration's source buffer, where the engine launches bdy_open; the arrays' dtype decides the single rounding of a stored value.
+    The face mass flux comes from `functions` -- an object with the oracle's `reconstruct` and `hllc` in the state's precision
+    (oracle.OracleFunctions), called in godunov_cell's argument order as frontend.Tracer.face_fluxes calls them; everything else is
+    fp64: separate, correctly rounded adds, subtracts and multiplies, so state and records equal the device's bit for bit.  The GPU
+    tests' reference; it also counts which branch each cell took.  `segments`: see pack_open_segments (GLOBAL indices); a strip
+    (row_offset, global_rows) keeps the ring cells whose row lies in its `rows` local rows."""
+
+    SOUTH, NORTH, WEST, EAST = 0, 1, 2, 3
+    MAX_SEGMENTS = 64
+    DIRECTION = {0: 2, 1: 0, 2: 3, 3: 1}                   # the edge's face of the inward neighbour, as Tracer.DIR_*
+    # per cell and iteration: inert, or any of dry (d == 0), level_capped (step 3's cap), inward_zeroed (an inward Qn_i was not taken),
+    # and one of outflow (out > 0) / inflow (out < 0) / neither
+    BRANCHES = ("inert", "dry", "level_capped", "inward_zeroed", "outflow", "inflow")
+
+    def __init__(self, rows, cols, dx, functions, segments, row_offset=0, global_rows=None, dry_threshold=1e-10):
+        from . import pack_open_segments
+        self.rows, self.cols, self.row_offset = int(rows), int(cols), int(row_offset)
+        self.global_rows = self.rows if global_rows is None else int(global_rows)
+        self.fn = functions
+        self.real = np.dtype(functions.real).type
+        self.dx = np.float64(self.real(dx))                                    # dx as the kernels hold it
+        self.vs = self.real(dry_threshold)
+        if segments is None:
+            raise ValueError("segments == NULL")
+        S = pack_open_segments(segments, self.cols, self.global_rows)
+        if len(S) < 1:
+            raise ValueError("count == 0")
+        if len(S) > self.MAX_SEGMENTS:
+            raise ValueError("more than 64 segments on the domain")
+        edge, seg, at = [], [], []
+        for k, s in enumerate(S):
+            if int(s["edge"]) not in (0, 1, 2, 3):
+                raise ValueError(f"segment {k}: unknown edge")
+            if int(s["reserved"]) != 0:
+                raise ValueError(f"segment {k}: reserved must be 0")
+            if s["first"] > s["last"]:
+                raise ValueError(f"segment {k}: first > last")
+            n = self.cols if int(s["edge"]) in (self.SOUTH, self.NORTH) else self.global_rows
+            if s["first"] < 1 or s["last"] > n - 2:
+                raise ValueError(f"segment {k}: index {int(s['first']) if s['first'] < 1 else n - 1} lies outside 1..{n - 2}")
+            idx = np.arange(int(s["first"]), int(s["last"]) + 1)
+            at.append(idx); edge.append(np.full(len(idx), int(s["edge"]))); seg.append(np.full(len(idx), k))
+        self.segments = S
+        self.edge, self.segment_of, at = np.concatenate(edge), np.concatenate(seg), np.concatenate(at)
+        e, last_row, last_col = self.edge, self.global_rows - 1, self.cols - 1
+        # the ring cell and its inward neighbour as (column, GLOBAL row)
+        self.rx = np.where(e == self.WEST, 0, np.where(e == self.EAST, last_col, at))
+        self.ry = np.where(e == self.SOUTH, 0, np.where(e == self.NORTH, last_row, at))
+        self.ix = np.where(e == self.WEST, 1, np.where(e == self.EAST, last_col - 1, at))
+        self.iy = np.where(e == self.SOUTH, 1, np.where(e == self.NORTH, last_row - 1, at))
+        self.cells = self.ry.astype(np.int64) * self.cols + self.rx            # GLOBAL flat ids of the listed ring cells, in the records' order
+        uniq, first_at, counts = np.unique(self.cells, return_index=True, return_counts=True)
+        if (counts > 1).any():
+            twice = int(uniq[counts > 1][0])
+            later = int(self.segment_of[np.flatnonzero(self.cells == twice)[1]])
+            raise ValueError(f"segment {later}: cell {twice} is listed twice")
+        lo, hi = self.row_offset, self.row_offset + self.rows
+        self.kept = (self.ry >= lo) & (self.ry < hi) & (self.iy >= lo) & (self.iy < hi)      # the strip's selection
+        n = len(self.cells)
+        self.q_last, self.volume, self.active = np.zeros(n), np.zeros(n), np.zeros(n, np.uint64)
+        self.applies = 0
+        self.branches = {k: np.zeros(n, np.int64) for k in self.BRANCHES}    # per cell: iterations in which it took the branch
+
+    def records(self):
+        from . import OPEN_RECORD_DTYPE
+        out = np.zeros(len(self.cells), OPEN_RECORD_DTYPE)
+        out["q_last"], out["volume"], out["active"] = self.q_last, self.volume, self.active
+        return out
+
+    def branch_totals(self):
+        return {k: int(v.sum()) for k, v in self.branches.items()}
+
+    def segment_totals(self):
+        """Per segment (discharge, volume): math.fsum over its cells' records -- exactly rounded, so independent of any order."""
+        import math
+        return [(math.fsum(self.q_last[self.segment_of == k]), math.fsum(self.volume[self.segment_of == k])) for k in range(len(self.segments))]
+
+    @staticmethod
+    def impose(edge, zmax_r, bed_r, z_i, zmax_i, qn_i, qs_i, bed_i, dt):
+        """open_impose on fp64 arrays, one element per cell -> (inert, lvl, qn, qs, dry, capped, zeroed): the level before it is rounded."""
+        a = lambda v: np.asarray(v, dtype=np.float64)
+        zmax_r, bed_r, z_i, zmax_i, qn_i, qs_i, bed_i = (a(v) for v in (zmax_r, bed_r, z_i, zmax_i, qn_i, qs_i, bed_i))
+        edge, dt = np.asarray(edge), np.asarray(dt, dtype=np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            inert = (dt <= 0.0) | ~((zmax_r > -9999.0) & (bed_r <= 9999.0)) | ~((zmax_i > -9999.0) & (bed_i <= 9999.0))
+            d = z_i - bed_i
+            d = np.where(d > 0.0, d, 0.0)
+            lvl = bed_r + d
+            capped = lvl > z_i
+            lvl = np.where(capped, np.where(z_i > bed_r, z_i, bed_r), lvl)
+            dry = d == 0.0
+            positive = (edge == Open.EAST) | (edge == Open.NORTH)
+            outward = np.where(positive, qn_i > 0.0, qn_i < 0.0)
+            qn = np.where(~dry & outward, qn_i, 0.0)
+            qs = np.where(~dry, qs_i, 0.0)
+            zeroed = ~dry & ~outward & (qn_i != 0.0)
+        live = ~inert
+        return inert, lvl, qn, qs, live & dry, live & capped, live & zeroed
+
+    @staticmethod
+    def record(q_last, volume, active, inert, edge, F, dt, dx):
+        """open_record on fp64 arrays -> (q_last, volume, active, out)."""
+        F, dt, dx = (np.asarray(v, dtype=np.float64) for v in (F, dt, dx))
+        inert = np.asarray(inert, dtype=bool)
+        positive = (np.asarray(edge) == Open.EAST) | (np.asarray(edge) == Open.NORTH)
+        with np.errstate(invalid="ignore", over="ignore"):
+            out = np.where(positive, F, -F)
+            q1 = np.where(inert, 0.0, out * dx)
+            v1 = np.where(inert, volume, volume + (out * dt) * dx)
+            a1 = np.asarray(active, dtype=np.uint64) + (~inert & (out > 0.0)).astype(np.uint64)
+        return q1, v1, a1, out
+
+    def face_flux(self, state, bed, k):
+        """F of listed cell k (local rows): the face between the inward neighbour and the ring cell as godunov_cell forms it for the
+        neighbour (Tracer.face_fluxes' statement for that face)."""
+        f, direction = self.fn, self.DIRECTION[int(self.edge[k])]
+        ry, iy, rx, ix = int(self.ry[k]) - self.row_offset, int(self.iy[k]) - self.row_offset, int(self.rx[k]), int(self.ix[k])
+        if int(self.edge[k]) in (self.EAST, self.NORTH):
+            L, R, _ = f.reconstruct(direction, state[iy, ix], bed[iy, ix], state[ry, rx], bed[ry, rx])
+        else:
+            L, R, _ = f.reconstruct(direction, state[ry, rx], bed[ry, rx], state[iy, ix], bed[iy, ix])
+        return f.hllc(direction, L, R)[0]
+
+    def apply(self, state, bed, dt):
+        """One iteration's open boundary, in place on `state` (the iteration's source buffer); `dt`: the timestep scalar of that
+        iteration.  Returns the number of cells through which water left."""
+        if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or state.dtype != bed.dtype:
+            raise ValueError("state must be [rows, cols, 4] and bed [rows, cols], of one dtype")
+        if state.dtype.type is not self.real:
+            raise ValueError("the face-flux functions and the state differ in precision")
+        real = self.real
+        dt64 = np.float64(real(dt))
+        kept = np.flatnonzero(self.kept)
+        e = self.edge[kept]
+        ry, iy, rx, ix = self.ry[kept] - self.row_offset, self.iy[kept] - self.row_offset, self.rx[kept], self.ix[kept]
+        along_x = (e == self.WEST) | (e == self.EAST)
+        inner = state[iy, ix].astype(np.float64)
+        qn_i, qs_i = np.where(along_x, inner[:, 2], inner[:, 3]), np.where(along_x, inner[:, 3], inner[:, 2])
+        inert, lvl, qn, qs, dry, capped, zeroed = self.impose(e, state[ry, rx, 1].astype(np.float64), bed[ry, rx].astype(np.float64), inner[:, 0], inner[:, 1],
+                                                              qn_i, qs_i, bed[iy, ix].astype(np.float64), dt64)
+        live = ~inert
+        z_new = lvl.astype(real)
+        ring = state[ry, rx]
+        ring[:, 0] = np.where(live, z_new, ring[:, 0])
+        ring[:, 1] = np.where(live & ~(ring[:, 1] > z_new), z_new, ring[:, 1])
+        ring[:, 2] = np.where(live, np.where(along_x, qn, qs).astype(real), ring[:, 2])
+        ring[:, 3] = np.where(live, np.where(along_x, qs, qn).astype(real), ring[:, 3])
+        state[ry, rx] = ring
+        F = np.zeros(len(kept))
+        for j in np.flatnonzero(live):
+            F[j] = np.float64(self.face_flux(state, bed, int(kept[j])))
+        q1, v1, a1, out = self.record(self.q_last[kept], self.volume[kept], self.active[kept], inert, e, F, dt64, self.dx)
+        self.q_last[kept], self.volume[kept], self.active[kept] = q1, v1, a1
+        for name, mask in (("inert", inert), ("dry", dry), ("level_capped", capped), ("inward_zeroed", zeroed),
+                           ("outflow", live & (out > 0.0)), ("inflow", live & (out < 0.0))):
+            self.branches[name][kept] += mask
+        self.applies += 1
+        return int((live & (out > 0.0)).sum())
 
 
 class Infiltration:

@@ -182,7 +182,7 @@ class Model:
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
                  probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None,
-                 links=None, infiltration=None, tracer=None):
+                 links=None, infiltration=None, tracer=None, open_edges=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -208,6 +208,22 @@ class Model:
             if cfg.scheme == frontend.SCHEME_MUSCL_HANCOCK and log:
                 log("Warning: link groups are inert under MUSCL-Hancock, like every boundary condition (quirk Q8)")
             sim.add_links(self.link_list)
+        # The open boundary (no reference counterpart): the model file's <domainEdge edge="east" treatment="open" name="outlet" from="8"
+        # to="23"/> elements and the dict(edge=, name=, first=, last=) entries (or bare edge names) of `open_edges`, one call behind the
+        # file's boundaries and the links.  It acts inside every iteration, so only an engine that has it on the device will do.
+        self.open_list = []
+        for k, e in enumerate(list(cfg.open_edges) + list(open_edges or [])):
+            e = dict(edge=e) if isinstance(e, str) else dict(e)
+            e.setdefault("name", f"{e['edge']}{k}")
+            self.open_list.append(e)
+        self.open_series = []                                      # [(time, [(discharge, volume) per segment])]: one entry per output time
+        if self.open_list:
+            from . import pack_open_segments
+            if not hasattr(sim, "add_open"):
+                raise NotImplementedError("the open boundary acts inside every iteration: it needs an engine with add_open (the HIP engine)")
+            segments = pack_open_segments([dict(edge=e["edge"], first=e.get("first"), last=e.get("last")) for e in self.open_list], self.cols, self.rows)
+            self.open_segment_of = np.concatenate([np.full(int(s["last"]) - int(s["first"]) + 1, k) for k, s in enumerate(segments)])
+            sim.add_open(segments)
         # The infiltration (no reference counterpart): the raster of a <dataSource type="raster" value="soil" source="..."/> with the
         # classes of <soilClasses source="soil.csv"/> (columns ks, suction, deficit, capacity), or `infiltration`: dict(soil=, classes=,
         # initial=) with soil an array [rows, cols] (row 0 = south; 0 = impervious) or a raster file.  Behind the file's boundaries and
@@ -470,6 +486,22 @@ class Model:
                 for t, rec in self.link_series:
                     f.write(",".join([repr(float(t))] + [f"{float(r['q_last'])!r},{float(r['volume'])!r}" for r in rec]) + "\n")
 
+    def write_outflow(self):
+        """outflow.csv in the target directory: a row per output time, t, then discharge and cumulative volume of every open segment in
+        the order given -- math.fsum over the segment's cell records: exactly rounded, so independent of any order."""
+        if not self.open_list:
+            return
+        import math
+        rec = self.sim.open_read()
+        self.open_series.append((self.current_time, [(math.fsum(rec["q_last"][self.open_segment_of == k]), math.fsum(rec["volume"][self.open_segment_of == k]))
+                                                     for k in range(len(self.open_list))]))
+        if self.cfg.target_dir and self.output_format:
+            os.makedirs(self.cfg.target_dir, exist_ok=True)
+            with open(os.path.join(self.cfg.target_dir, "outflow.csv"), "w") as f:
+                f.write(",".join(["t"] + [f"discharge_{e['name']},volume_{e['name']}" for e in self.open_list]) + "\n")
+                for t, totals in self.open_series:
+                    f.write(",".join([repr(float(t))] + [f"{q!r},{v!r}" for q, v in totals]) + "\n")
+
     def peaks(self):
         """{name: array} of the tracked peak values so far."""
         if not self.peak_names:
@@ -559,6 +591,7 @@ class Model:
         self.write_probes()
         self.write_zones()
         self.write_links()
+        self.write_outflow()
         self.outputs.append((self.current_time, out))
         self.last_output_time = self.current_time
         self.scheme.force_time_advance()

@@ -246,6 +246,13 @@ class HipEngine:
     def links_read(self, first=0, count=None):
         return self.domain.links_read(first, count)
 
+    # the open boundary (Domain.add_open)
+    def add_open(self, segments):
+        self.domain.add_open(segments)
+
+    def open_read(self, first=0, count=None):
+        return self.domain.open_read(first, count)
+
     # the infiltration (Domain.add_infiltration)
     def add_infiltration(self, soil, classes, initial=None):
         self.domain.add_infiltration(soil, classes, initial)
@@ -686,6 +693,49 @@ class StripRunner:
         if self.rank != 0:
             return None
         out = np.zeros(len(L), LINK_RECORD_DTYPE)
+        for idx, rec in parts:
+            out[idx] = rec
+        return out
+
+    # ---- the open boundary: every rank adds every segment with GLOBAL indices; a strip keeps the ring cells whose row it stores (ghost
+    #      rows included) and recomputes the west and east ones on its ghost rows redundantly with their owners ----
+    def add_open(self, segments):
+        """`segments`: see hipims_mi.pack_open_segments; every rank calls it with the same arguments.  A strip with two reaches of
+        ghost rows is refused by the engine (HP_ERR_UNSUPPORTED)."""
+        from . import pack_open_segments
+        if not hasattr(self.engine, "add_open"):
+            raise RuntimeError("add_open: this engine has no open boundary (the HIP engine's hp_boundary_add_open)")
+        S = pack_open_segments(segments, self.cols, self.rows)
+        self.engine.add_open(S)                         # (may still refuse the segments: only what the engine took is remembered)
+        self._open = S if getattr(self, "_open", None) is None else np.concatenate([self._open, S])
+
+    def open_rows(self):
+        """The GLOBAL row of every listed ring cell, in the records' order."""
+        from . import EDGE_NORTH, EDGE_SOUTH
+        rows = []
+        for s in self._open:
+            n = int(s["last"]) - int(s["first"]) + 1
+            if int(s["edge"]) == EDGE_SOUTH:
+                rows.append(np.zeros(n, np.int64))
+            elif int(s["edge"]) == EDGE_NORTH:
+                rows.append(np.full(n, self.rows - 1, np.int64))
+            else:
+                rows.append(np.arange(int(s["first"]), int(s["last"]) + 1, dtype=np.int64))
+        return np.concatenate(rows)
+
+    def gather_open(self):
+        """The records of all open cells on rank 0 (an array of hipims_mi.OPEN_RECORD_DTYPE, equal to the single domain's
+        Domain.open_read() in every bit), None on the other ranks: a cell's record is the one of the strip that owns its row.
+        Collective."""
+        from . import OPEN_RECORD_DTYPE
+        if getattr(self, "_open", None) is None:
+            raise RuntimeError("gather_open: no open segment was added")
+        rows = self.open_rows()
+        mine = np.flatnonzero((rows >= self.own_lo) & (rows < self.own_hi))
+        parts = self._gather_parts((mine, self.engine.open_read()[mine]))
+        if self.rank != 0:
+            return None
+        out = np.zeros(len(rows), OPEN_RECORD_DTYPE)
         for idx, rec in parts:
             out[idx] = rec
         return out

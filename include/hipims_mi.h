@@ -668,7 +668,74 @@ int hp_infiltration_read(hp_domain_t* d, double* raster, int64_t row0, int64_t n
 /* Host counters, does not block: the classes of the domain's infiltration and its cells of a class other than 0 (both 0 without
  * one); either pointer may be NULL. */
 int hp_infiltration_info(hp_domain_t* d, uint32_t* classes, uint64_t* pervious_cells);
-int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups too (and their records), and the infiltration with its F */
+/* ---- the open boundary: water LEAVES the model -- the downstream edge of a catchment, the seaward side of an estuary (no reference
+ *      counterpart: the reference's edges are closed walls or never-written cells).  An open boundary is a set of SEGMENTS of the
+ *      grid's edge ring; it is the sixth boundary kind, next to uniform, gridded, cell, link groups and the infiltration: applied once
+ *      per iteration on the iteration's source buffer, at its place in the order added.  Every ring cell of a segment takes the depth
+ *      and the outward momentum of its inward neighbour -- a zero-gradient, outflow-only edge -- and records the discharge that leaves
+ *      through its face.  The kernel is one lane per listed ring cell (csrc/hp_open.hpp: bdy_open): a ring cell is in at most one
+ *      segment of the domain, so it needs no atomics and does not depend on any order.
+ *      A domain that never calls hp_boundary_add_open allocates nothing and queues exactly what it queued without this call.  A
+ *      domain with an open boundary is not fusable (hp_boundaries_fused is false, as with a cell boundary), so it runs single
+ *      iterations, never iteration pairs; and it never runs a speculative STRICT batch (a batch that is queued again would add to
+ *      `volume` twice).  The ring's part of the timestep is priced anew on every iteration, as with a cell boundary on ring cells.
+ *      THE CONTRACT.  All arithmetic in fp64 whatever the domain's precision, the stored values widened first; correctly rounded add,
+ *      subtract, multiply and compare only, never fused; each stored value is rounded once to the domain's precision T.  dt is the
+ *      "Timestep" scalar, dx the cell size as the kernels hold it (rounded to T and widened).  r is the ring cell, i its inward
+ *      neighbour (the cell next to it across the edge's face), n the state component normal to the edge (Qx for west / east, Qy for
+ *      south / north), s the other one.  Per listed ring cell and iteration:
+ *        1. Inert.  The cell is inert if dt <= 0, or if r or i is not counted in the sense of hp_domain_stats (a cell is counted when
+ *      Zmax > -9999 and bed <= 9999): a closed-edge wall inside a segment is simply inert.  An inert cell sets q_last = +0.0 and
+ *      changes nothing else.
+ *        2. Depth.  d = Z_i - bed_i.  If !(d > 0) then d = 0.
+ *        3. Level.  lvl = bed_r + d.  If lvl > Z_i then lvl = Z_i > bed_r ? Z_i : bed_r: the ring never stands above the water that
+ *      feeds it, and nothing runs in downhill from outside.
+ *        4. Momentum.  If d == 0 then Qn = Qs = +0.0.  Otherwise Qs = Qs_i, and Qn = Qn_i if it points out of the grid (> 0 on east
+ *      and north, < 0 on west and south), else Qn = +0.0.
+ *        5. Stores.  Z_r = (T)lvl; Zmax_r = Zmax_r > Z_r ? Zmax_r : Z_r; Qx and Qy as above.
+ *        6. Record.  F is the first component (the mass flux) of the exact face solve between i and the ring cell as just stored: the
+ *      STRICT make_side / face_solve of csrc/hp_math.hpp in the domain's precision whatever the domain's math_mode, with the argument
+ *      order the flux kernel uses for that face of i (the tracer's rule: one arithmetic, not two).  out = +F on east and north, -F on
+ *      west and south.  q_last = out * dx; volume = volume + (out * dt) * dx, one add per iteration, in iteration order;
+ *      active += (out > 0).
+ *      WHAT THE RECORD IS.  The face flux that the flux launch that follows uses for cell i -- in the exact arithmetic; a FAST domain's
+ *      own flux differs from it by that mode's tolerance.  It is not i's realised loss: the flux kernel zeroes net changes below the dry
+ *      threshold and snaps nearly dry cells to the bed, so the sum of the records and the water that left the interior differ by at
+ *      most a few dry thresholds per cell and iteration.
+ *      frontend.Open restates all of it in NumPy; tests/open_probe.cpp holds the two to each other bit for bit.
+ *      STRIPS.  Every rank adds every segment with GLOBAL indices.  A strip keeps the ring cells whose row lies in its local array,
+ *      ghost rows included; west and east cells on ghost rows are recomputed redundantly (their inward neighbour lies in the same row
+ *      and is valid with one reach of ghost rows).  A cell's record is the one held by the strip that owns its row.  A strip with two
+ *      reaches of ghost rows holds its outermost reach on every second iteration only, and the records there would drift from their
+ *      owners': on such a strip hp_boundary_add_open returns HP_ERR_UNSUPPORTED (the infiltration's rule and reason). ---- */
+enum { HP_EDGE_SOUTH = 0, HP_EDGE_NORTH = 1, HP_EDGE_WEST = 2, HP_EDGE_EAST = 3 };
+typedef struct {
+	int32_t edge;                      /* HP_EDGE_* */
+	int32_t reserved;                  /* 0 */
+	int64_t first, last;               /* inclusive, along the edge in the GLOBAL grid: the column x for south and north, the global row for
+	                                      west and east; both in 1 .. n - 2 (the four corner cells touch no interior cell) */
+} hp_open_segment_t;
+typedef struct {
+	double   q_last;                   /* the discharge through the cell's face in the last iteration, m3/s, outward positive */
+	double   volume;                   /* what has passed since the segment was added, m3, outward positive */
+	uint64_t active;                   /* iterations in which water left through the face */
+	uint64_t reserved;
+} hp_open_record_t;
+/* Adds `count` segments (at most 64 over the domain).  Records are ordered by segment in the order added, and by ascending index
+ * inside a segment.  Argument errors -- a NULL pointer, count 0, more than 64 segments on the domain, an unknown edge, a non-zero
+ * `reserved`, first > last, an index outside 1 .. n - 2, a ring cell listed twice over all segments of the domain -- are
+ * HP_ERR_INVALID before any device call, and the message names the segment and the first offending cell; between hp_step_begin and
+ * hp_step_end the call returns HP_ERR_STATE.  HP_ERR_UNSUPPORTED, with the reason in the message: a scheme other than Godunov (the
+ * record is the Godunov face flux; under MUSCL-Hancock every boundary is inert anyway, quirk Q8), and a strip with two reaches of ghost
+ * rows. */
+int hp_boundary_add_open(hp_domain_t* d, const hp_open_segment_t* segments, uint32_t count);
+/* Records first .. first + count - 1.  Enqueued; valid after hp_sync (the host memory must stay alive until then).  first + count
+ * beyond the domain's listed ring cells is HP_ERR_INVALID; count == 0 is HP_OK. */
+int hp_open_read(hp_domain_t* d, uint64_t first, uint64_t count, hp_open_record_t* out);
+int hp_open_info(hp_domain_t* d, uint32_t* segments, uint64_t* cells);   /* host counters (cells: of the GLOBAL grid); either pointer may be NULL */
+/* hp_state_save / hp_state_restore keep and restore the open boundary's records by the links' rule: if segments were added or cleared
+ * since the snapshot, the restore zeroes the records and sends one HP_LOG_WARNING. */
+int hp_boundary_clear(hp_domain_t* d);                 /* removes link groups too (and their records), the infiltration with its F, and the open boundary with its records */
 /* Are the domain's area boundaries carried by the flux kernel itself (rain / loss of iteration n+1 added to the state
  * iteration n stores, no separate pass over the grid)?  True for the Godunov scheme with up to three uniform / gridded
  * boundaries, no cell boundary among them, and rain grids of at least 64 model cells per grid cell; everything else runs
