@@ -3,7 +3,7 @@
 // the bed shapes (hp_bed.hpp), and the tracer that rides on the water they move (hp_tracer.hpp).
 // Here: their entry points of include/hipims_mi.h, the boundary pass the engine queues in front of an iteration (apply_boundaries)
 // and the choice of what the flux kernel carries of it instead (refresh_fusable), and what hp_state_save / hp_state_restore /
-// hp_domain_destroy do for the bed, the links and the infiltration (*_save, *_restore, *_destroy; actors_* calls them in order).  Their
+// hp_domain_destroy do for their stores (*_save_reserve, *_save, *_restore, *_destroy) and in which order (PARTICIPANTS, the observers included).  Their
 // state is declared in hp_domain.hpp (Boundary, BedShapes, LinkStore, SoilStore, TracerStore).  Included once by hp_engine.hip, after hp_observers.hpp: the library
 // stays one translation unit.
 #pragma once
@@ -137,53 +137,45 @@ BedLists bed_lists(void* block, const BedLayout& l, const size_t n, const unsign
 	L.shapes = shapes;
 	return L;
 }
-void bed_destroy(hp_domain* d) { hipFree(d->beds.block); hipFree(d->beds.info); hipFree(d->beds.saved); }
+void bed_destroy(hp_domain* d) { hipFree(d->beds.block); hipFree(d->beds.info); slot_free(d->beds.saved); }
 
-// hp_state_save, before it touches anything: room for the bed at the listed cells (peaks_save_reserve's rule: a failure leaves the
-// checkpoint before it untouched)
+// What a checkpoint does for the five actors' stores (SaveSlot, hp_domain.hpp): hp_state_save reserves the copy before it touches anything,
+// grown with the store or allocated once, and takes it behind the state's copies -- the mark also while the store is off or empty;
+// hp_state_restore asks the mark, and what a stale store does stands with its *_restore.  The answer, with the store's `warning` sent if STALE:
+Verdict restore_verdict(const SaveSlot& s, const uint64_t epoch, const char* warning)
+{
+	const Verdict v = s.mark.verdict(epoch);
+	if (v == Verdict::STALE) log_line(HP_LOG_WARNING, warning);
+	return v;
+}
+// the bed at the listed cells: gathered into the copy and scattered from it
 int bed_save_reserve(hp_domain* d)
 {
 	BedShapes& B = d->beds;
-	if (!B.shapes || B.lists.count <= B.saved_room) return HP_OK;
-	void* grown = nullptr;
-	int rc = alloc_or_fail(&grown, (size_t)B.lists.count * d->esize, "hp_state_save: cannot allocate the copy of the listed cells' bed: ");
-	if (rc != HP_OK) return rc;
-	if (B.saved) {
-		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
-		hipFree(B.saved);
-	}
-	B.saved = grown;
-	B.saved_room = (size_t)B.lists.count;
-	return HP_OK;
+	return slot_reserve(d->stream, B.saved, B.shapes ? B.lists.count : 0, d->esize, "hp_state_save: cannot allocate the copy of the listed cells' bed: ");
 }
-// ... and behind the state's copies: hp_state_restore brings back neither the bed nor the boundary list, and levels of one bed over
-// another are no state
+// (hp_state_restore brings back neither the bed nor the boundary list, and levels of one bed over another are no state)
 int bed_save(hp_domain* d)
 {
 	BedShapes& B = d->beds;
-	B.saved_taken = true;
-	B.saved_epoch = B.epoch;
+	B.saved.mark.take(B.epoch);
 	if (!B.shapes || !B.lists.count) return HP_OK;
 	with_real(d, [&](auto zero) { using T = decltype(zero);
-		hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (const T*)d->bed, B.lists.cells, 0ull, B.lists.count, (T*)B.saved);
+		hipLaunchKernelGGL((bed_gather<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (const T*)d->bed, B.lists.cells, 0ull, B.lists.count, (T*)B.saved.copy);
 	});
 	HIP_TRY(hipGetLastError());
 	return HP_OK;
 }
-// hp_state_restore, behind the state's copies
+// stale: the bed is left as it is
 int bed_restore(hp_domain* d)
 {
 	BedShapes& B = d->beds;
-	if (!B.saved_taken) return HP_OK;
-	if (B.saved_epoch != B.epoch) {                                           // (the probe recorder's rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: bed shapes were added or cleared after the state was saved: the bed is left as it is");
-		return HP_OK;
-	}
-	if (!B.shapes) return HP_OK;
+	const Verdict v = restore_verdict(B.saved, B.epoch, "hp_state_restore: bed shapes were added or cleared after the state was saved: the bed is left as it is");
+	if (v != Verdict::BRING_BACK || !B.shapes) return HP_OK;
 	d->facts.boundaries_or_bed_changed();
 	if (B.lists.count) {
 		with_real(d, [&](auto zero) { using T = decltype(zero);
-			hipLaunchKernelGGL((bed_scatter<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (T*)d->bed, B.lists.cells, B.lists.count, (const T*)B.saved);
+			hipLaunchKernelGGL((bed_scatter<T>), dim3(stream_blocks((size_t)B.lists.count)), dim3(256), 0, d->stream, (T*)d->bed, B.lists.cells, B.lists.count, (const T*)B.saved.copy);
 		});
 		HIP_TRY(hipGetLastError());
 	}
@@ -192,53 +184,41 @@ int bed_restore(hp_domain* d)
 }
 
 // ---- link groups (hp_links.hpp): what a checkpoint and hp_boundary_clear do for the links' records ----
-void links_destroy(hp_domain* d) { hipFree(d->links.records); hipFree(d->links.saved); }
+void links_destroy(hp_domain* d) { hipFree(d->links.records); slot_free(d->links.saved); }
+inline size_t links_bytes(const LinkStore& L) { return (size_t)L.links * sizeof(hp_link_record_t); }
 // hp_boundary_clear: the link groups go with the list, and their records with them
 int links_clear(hp_domain* d)
 {
 	LinkStore& L = d->links;
 	if (!L.groups) return HP_OK;
-	HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
+	HIP_TRY(hipMemsetAsync(L.records, 0, links_bytes(L), d->stream));
 	L.links = 0;
 	L.groups = 0;
 	L.taken.clear();
 	++L.epoch;
 	return HP_OK;
 }
-// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+// the copy: LINK_MAX records, once the domain has a link
 int links_save_reserve(hp_domain* d)
 {
-	LinkStore& L = d->links;
-	if (!L.links || L.saved) return HP_OK;
-	return alloc_or_fail((void**)&L.saved, (size_t)LINK_MAX * sizeof(hp_link_record_t), "hp_state_save: cannot allocate the copy of the links' records: ");
+	return slot_reserve(d->stream, d->links.saved, d->links.links ? LINK_MAX : 0, sizeof(hp_link_record_t), "hp_state_save: cannot allocate the copy of the links' records: ");
 }
-int links_save(hp_domain* d)
-{
-	LinkStore& L = d->links;
-	L.saved_taken = true;
-	L.saved_epoch = L.epoch;
-	if (L.links) HIP_TRY(hipMemcpyAsync(L.saved, L.records, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
-}
+int links_save(hp_domain* d) { return slot_take(d->stream, d->links.saved, d->links.records, links_bytes(d->links), d->links.epoch); }
+// stale: the records start from zero
 int links_restore(hp_domain* d)
 {
 	LinkStore& L = d->links;
-	if (!L.saved_taken) return HP_OK;
-	if (L.saved_epoch != L.epoch) {                                           // (the probe recorder's rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: link groups were added or cleared after the state was saved: the links' records start from zero");
-		if (L.links) HIP_TRY(hipMemsetAsync(L.records, 0, (size_t)L.links * sizeof(hp_link_record_t), d->stream));
-		return HP_OK;
-	}
-	if (L.links) HIP_TRY(hipMemcpyAsync(L.records, L.saved, (size_t)L.links * sizeof(hp_link_record_t), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
+	const Verdict v = restore_verdict(L.saved, L.epoch, "hp_state_restore: link groups were added or cleared after the state was saved: the links' records start from zero");
+	if (v == Verdict::STALE && L.links) HIP_TRY(hipMemsetAsync(L.records, 0, links_bytes(L), d->stream));
+	return v == Verdict::BRING_BACK ? slot_bring_back(d->stream, L.saved, L.records, links_bytes(L)) : HP_OK;
 }
 
 // ---- the infiltration (hp_soil.hpp): what a checkpoint and hp_boundary_clear do for F ----
 void soil_destroy(hp_domain* d)
 {
 	SoilStore& S = d->soil;
-	hipFree(S.ids); hipFree(S.F); hipFree(S.table); hipFree(S.saved);
-	S.ids = nullptr; S.F = nullptr; S.table = nullptr; S.saved = nullptr;
+	hipFree(S.ids); hipFree(S.F); hipFree(S.table); slot_free(S.saved);
+	S.ids = nullptr; S.F = nullptr; S.table = nullptr;
 }
 // hp_boundary_clear (the stream is idle): the infiltration goes with the list, and F with it
 int soil_clear(hp_domain* d)
@@ -252,41 +232,30 @@ int soil_clear(hp_domain* d)
 	++S.epoch;
 	return HP_OK;
 }
-// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+// the copy: F of every cell, while the domain has an infiltration (hp_boundary_clear frees it with the rest)
+inline size_t soil_bytes(const hp_domain* d) { return d->soil.on ? d->cells * sizeof(double) : 0; }
 int soil_save_reserve(hp_domain* d)
 {
-	SoilStore& S = d->soil;
-	if (!S.on || S.saved) return HP_OK;
-	return alloc_or_fail((void**)&S.saved, d->cells * sizeof(double), "hp_state_save: cannot allocate the copy of the cumulative infiltration: ");
+	return slot_reserve(d->stream, d->soil.saved, d->soil.on ? d->cells : 0, sizeof(double), "hp_state_save: cannot allocate the copy of the cumulative infiltration: ");
 }
-int soil_save(hp_domain* d)
-{
-	SoilStore& S = d->soil;
-	S.saved_taken = true;
-	S.saved_epoch = S.epoch;
-	if (S.on) HIP_TRY(hipMemcpyAsync(S.saved, S.F, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
-}
+int soil_save(hp_domain* d) { return slot_take(d->stream, d->soil.saved, d->soil.F, soil_bytes(d), d->soil.epoch); }
+// stale: F is left as it is
 int soil_restore(hp_domain* d)
 {
 	SoilStore& S = d->soil;
-	if (!S.saved_taken) return HP_OK;
-	if (S.saved_epoch != S.epoch) {                                           // (the bed shapes' rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: the infiltration was added or cleared after the state was saved: the cumulative infiltration is left as it is");
-		return HP_OK;
-	}
-	if (S.on) HIP_TRY(hipMemcpyAsync(S.F, S.saved, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
+	const Verdict v = restore_verdict(S.saved, S.epoch, "hp_state_restore: the infiltration was added or cleared after the state was saved: the cumulative infiltration is left as it is");
+	return v == Verdict::BRING_BACK ? slot_bring_back(d->stream, S.saved, S.F, soil_bytes(d)) : HP_OK;
 }
 
 // ---- the open boundary (hp_open.hpp): what a checkpoint and hp_boundary_clear do for its records ----
 void open_destroy(hp_domain* d)
 {
 	OpenStore& O = d->open;
-	hipFree(O.records); hipFree(O.saved);
-	O.records = nullptr; O.saved = nullptr;
-	O.room = O.saved_room = 0;
+	hipFree(O.records); slot_free(O.saved);
+	O.records = nullptr;
+	O.room = 0;
 }
+inline size_t open_bytes(const OpenStore& O) { return (size_t)O.cells * sizeof(hp_open_record_t); }
 // hp_boundary_clear (the stream is idle): the segments go with the list, and their records with them
 int open_clear(hp_domain* d)
 {
@@ -301,41 +270,19 @@ int open_clear(hp_domain* d)
 	++O.epoch;
 	return HP_OK;
 }
-// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+// the copy: a record for every listed cell, grown with the segments
 int open_save_reserve(hp_domain* d)
 {
-	OpenStore& O = d->open;
-	if (!O.cells || O.cells <= O.saved_room) return HP_OK;
-	hp_open_record_t* grown = nullptr;
-	int rc = alloc_or_fail((void**)&grown, (size_t)O.cells * sizeof(hp_open_record_t), "hp_state_save: cannot allocate the copy of the open boundary's records: ");
-	if (rc != HP_OK) return rc;
-	if (O.saved) {
-		HIP_TRY(hipStreamSynchronize(d->stream));                             // (a queued restore may still read the smaller one)
-		hipFree(O.saved);
-	}
-	O.saved = grown;
-	O.saved_room = O.cells;
-	return HP_OK;
+	return slot_reserve(d->stream, d->open.saved, d->open.cells, sizeof(hp_open_record_t), "hp_state_save: cannot allocate the copy of the open boundary's records: ");
 }
-int open_save(hp_domain* d)
-{
-	OpenStore& O = d->open;
-	O.saved_taken = true;
-	O.saved_epoch = O.epoch;
-	if (O.cells) HIP_TRY(hipMemcpyAsync(O.saved, O.records, (size_t)O.cells * sizeof(hp_open_record_t), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
-}
+int open_save(hp_domain* d) { return slot_take(d->stream, d->open.saved, d->open.records, open_bytes(d->open), d->open.epoch); }
+// stale: the records start from zero
 int open_restore(hp_domain* d)
 {
 	OpenStore& O = d->open;
-	if (!O.saved_taken) return HP_OK;
-	if (O.saved_epoch != O.epoch) {                                           // (the links' rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: open segments were added or cleared after the state was saved: the open boundary's records start from zero");
-		if (O.cells) HIP_TRY(hipMemsetAsync(O.records, 0, (size_t)O.cells * sizeof(hp_open_record_t), d->stream));
-		return HP_OK;
-	}
-	if (O.cells) HIP_TRY(hipMemcpyAsync(O.records, O.saved, (size_t)O.cells * sizeof(hp_open_record_t), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
+	const Verdict v = restore_verdict(O.saved, O.epoch, "hp_state_restore: open segments were added or cleared after the state was saved: the open boundary's records start from zero");
+	if (v == Verdict::STALE && O.cells) HIP_TRY(hipMemsetAsync(O.records, 0, open_bytes(O), d->stream));
+	return v == Verdict::BRING_BACK ? slot_bring_back(d->stream, O.saved, O.records, open_bytes(O)) : HP_OK;
 }
 
 // ---- the tracer (hp_tracer.hpp): its launches in front of the flux kernel, and what a checkpoint does for M ----
@@ -358,67 +305,58 @@ template <typename T> int apply_tracer(hp_domain* d, const void* source)
 void tracer_destroy(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.block); hipFree(R.saved);
-	R.M[0] = R.M[1] = nullptr; R.block = nullptr; R.saved = nullptr;
+	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.block); slot_free(R.saved);
+	R.M[0] = R.M[1] = nullptr; R.block = nullptr;
 }
-// hp_state_save, before it touches anything (peaks_save_reserve's rule)
+// the copy: the current M of every cell, while the domain has a tracer (hp_tracer_disable frees it with the rest); `iterations` goes with it
+inline size_t tracer_bytes(const hp_domain* d) { return d->tracer.on ? d->cells * sizeof(double) : 0; }
 int tracer_save_reserve(hp_domain* d)
 {
-	TracerStore& R = d->tracer;
-	if (!R.on || R.saved) return HP_OK;
-	return alloc_or_fail((void**)&R.saved, d->cells * sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
+	return slot_reserve(d->stream, d->tracer.saved, d->tracer.on ? d->cells : 0, sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
 }
 int tracer_save(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	R.saved_taken = true;
-	R.saved_epoch = R.epoch;
-	R.saved_iterations = R.iterations;
-	if (R.on) HIP_TRY(hipMemcpyAsync(R.saved, R.M[R.phase], d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
-	return HP_OK;
+	return slot_take(d->stream, R.saved, R.M[R.phase], tracer_bytes(d), R.epoch, R.iterations);
 }
-// (the phase names a buffer, nothing more: the saved M goes into the buffer that is current now, and the counter comes back)
+// stale: M is left as it is.  (The phase names a buffer, nothing more: the saved M goes into the buffer that is current now, and the counter comes back)
 int tracer_restore(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	if (!R.saved_taken) return HP_OK;
-	if (R.saved_epoch != R.epoch) {                                           // (the infiltration's rule)
-		log_line(HP_LOG_WARNING, "hp_state_restore: the tracer was enabled or disabled after the state was saved: the tracer is left as it is");
-		return HP_OK;
-	}
-	if (R.on) {
-		HIP_TRY(hipMemcpyAsync(R.M[R.phase], R.saved, d->cells * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
-		R.iterations = R.saved_iterations;
-	}
-	return HP_OK;
+	const Verdict v = restore_verdict(R.saved, R.epoch, "hp_state_restore: the tracer was enabled or disabled after the state was saved: the tracer is left as it is");
+	if (v != Verdict::BRING_BACK || !R.on) return HP_OK;
+	const int rc = slot_bring_back(d->stream, R.saved, R.M[R.phase], tracer_bytes(d));
+	if (rc == HP_OK) R.iterations = R.saved.mark.count;
+	return rc;
 }
 
-// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the four ----
-int actors_save_reserve(hp_domain* d)
+// ---- who takes part in a checkpoint, in the order hp_state_save (the reserve: before it touches anything; the save), hp_state_restore and
+//      hp_domain_destroy go through them: the observers (hp_observers.hpp) before the actors.  The output stage is only freed ----
+struct Participant {
+	int  (*reserve)(hp_domain*);
+	int  (*save)(hp_domain*);
+	int  (*restore)(hp_domain*);
+	void (*destroy)(hp_domain*);
+};
+const Participant PARTICIPANTS[] = {
+	{nullptr, nullptr, nullptr, out_destroy},
+	{peaks_save_reserve, peaks_save, peaks_restore, peaks_destroy},
+	{nullptr, probes_save, probes_restore, probes_destroy},
+	{nullptr, zones_save, zones_restore, zones_destroy},
+	{bed_save_reserve, bed_save, bed_restore, bed_destroy},
+	{links_save_reserve, links_save, links_restore, links_destroy},
+	{soil_save_reserve, soil_save, soil_restore, soil_destroy},
+	{open_save_reserve, open_save, open_restore, open_destroy},
+	{tracer_save_reserve, tracer_save, tracer_restore, tracer_destroy},
+};
+// one phase of a checkpoint (&Participant::reserve, ::save, ::restore): stops at the first participant that fails
+int participants_do(hp_domain* d, int (*Participant::*phase)(hp_domain*))
 {
-	int rc = bed_save_reserve(d);
-	if (rc == HP_OK) rc = links_save_reserve(d);
-	if (rc == HP_OK) rc = soil_save_reserve(d);
-	if (rc == HP_OK) rc = open_save_reserve(d);
-	return rc != HP_OK ? rc : tracer_save_reserve(d);
+	for (const Participant& p : PARTICIPANTS)
+		if (p.*phase) { const int rc = (p.*phase)(d); if (rc != HP_OK) return rc; }
+	return HP_OK;
 }
-int actors_save(hp_domain* d)
-{
-	int rc = bed_save(d);
-	if (rc == HP_OK) rc = links_save(d);
-	if (rc == HP_OK) rc = soil_save(d);
-	if (rc == HP_OK) rc = open_save(d);
-	return rc != HP_OK ? rc : tracer_save(d);
-}
-int actors_restore(hp_domain* d)
-{
-	int rc = bed_restore(d);
-	if (rc == HP_OK) rc = links_restore(d);
-	if (rc == HP_OK) rc = soil_restore(d);
-	if (rc == HP_OK) rc = open_restore(d);
-	return rc != HP_OK ? rc : tracer_restore(d);
-}
-void actors_destroy(hp_domain* d) { bed_destroy(d); links_destroy(d); soil_destroy(d); open_destroy(d); tracer_destroy(d); }
+void participants_destroy(hp_domain* d) { for (const Participant& p : PARTICIPANTS) p.destroy(d); }
 
 } // namespace
 
@@ -509,8 +447,7 @@ int hp_bed_shapes_clear(hp_domain_t* d)
 	bed_destroy(d);
 	BedShapes none;
 	none.epoch = B.epoch + 1;
-	none.saved_taken = B.saved_taken;
-	none.saved_epoch = B.saved_epoch;
+	none.saved.mark = B.saved.mark.carried();
 	B = none;
 	return HP_OK;
 }

@@ -1,12 +1,13 @@
 // hp_domain.hpp -- what the parts of libhipims_mi.so's host side share: the error and log plumbing of the C ABI, struct hp_domain,
 // the map of its pinned host block and the helpers more than one part uses (with_real, alloc_or_fail, upload_or_fail, stream_blocks,
-// stencil_reach, state_replaced).  Internal to the library's one translation unit: hp_engine.hip includes it, then hp_observers.hpp
+// stencil_reach, state_replaced) and the slot a store has in a checkpoint (SaveSlot, slot_*).  Internal to the library's one translation unit: hp_engine.hip includes it, then hp_observers.hpp
 // (the code of the four observers whose state is declared here, and of the RecordLog two of them share) and hp_actors.hpp (the code
 // of the boundaries, the link groups and the infiltration among them, the moving bed and the tracer: Boundary, LinkStore, SoilStore,
 // BedShapes and TracerStore below).
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_facts.hpp"
+#include "hp_checkpoint.hpp"
 #include "hp_plan.hpp"
 #include "hp_kernels.hpp"
 #include "hp_peaks.hpp"
@@ -79,6 +80,43 @@ int upload_or_fail(void** dev, const void* host, const size_t bytes, const std::
 	return fail(HP_ERR_HIP, what + hipGetErrorString(e));
 }
 
+// ---- a store's slot in a checkpoint: hp_state_save's device copy of it and the mark (hp_checkpoint.hpp) ----
+struct SaveSlot {
+	void*    copy = nullptr;
+	SaveMark mark;
+};
+// hp_state_save, before it touches anything: room for `units` units of `unit_bytes` (`what`: the store's message when it cannot be had).  A
+// failure leaves the copy and the mark as they were: the checkpoint before it is untouched
+int slot_reserve(hipStream_t stream, SaveSlot& s, const uint64_t units, const size_t unit_bytes, const char* what)
+{
+	if (!s.mark.needs_room(units)) return HP_OK;
+	void* grown = nullptr;
+	const int rc = alloc_or_fail(&grown, (size_t)units * unit_bytes, what);
+	if (rc != HP_OK) return rc;
+	if (s.copy) {
+		HIP_TRY(hipStreamSynchronize(stream));                                // (a queued restore may still read the smaller one)
+		hipFree(s.copy);
+	}
+	s.copy = grown;
+	s.mark.got_room(units);
+	return HP_OK;
+}
+// ... behind the state's copies: `bytes` of the store as it lies (0 while it is off or empty), and the mark once the copy is queued
+int slot_take(hipStream_t stream, SaveSlot& s, const void* store, const size_t bytes, const uint64_t epoch, const uint64_t count = 0)
+{
+	s.mark.drop();
+	if (bytes) HIP_TRY(hipMemcpyAsync(s.copy, store, bytes, hipMemcpyDeviceToDevice, stream));
+	s.mark.take(epoch, count);
+	return HP_OK;
+}
+// hp_state_restore, behind the state's copies, for a store whose mark says BRING_BACK
+int slot_bring_back(hipStream_t stream, const SaveSlot& s, void* store, const size_t bytes)
+{
+	if (bytes) HIP_TRY(hipMemcpyAsync(store, s.copy, bytes, hipMemcpyDeviceToDevice, stream));
+	return HP_OK;
+}
+void slot_free(SaveSlot& s) { hipFree(s.copy); s.copy = nullptr; s.mark.lost_room(); }
+
 // a streaming pass over n elements: a few blocks per CU, the rest by grid stride (the result never depends on the shape)
 inline unsigned stream_blocks(const size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
 
@@ -122,9 +160,7 @@ struct PeakTracker {
 	double*          acc = nullptr;                   // count x cells fp64, followed by the PeakBlock
 	uint64_t         samples = 0;                     // samples queued since enable / reset (its parity picks the time slot)
 	uint64_t         epoch = 0;                       // counts enable / disable: a checkpoint's peaks belong to one epoch
-	void*            saved = nullptr;                 // hp_state_save's copy of acc (accumulators + block)
-	bool             saved_valid = false;
-	uint64_t         saved_epoch = 0, saved_samples = 0;
+	SaveSlot         saved;                           // hp_state_save's copy of acc (accumulators + block), in bytes; comes back with `samples`
 };
 // What the probe and the zone recorder share: a log of `capacity` records of `stride` 8-byte words each in device memory, one
 // record per sample, and its lifecycle (hp_observers.hpp: log_*).  Nothing of it exists while recording is off.
@@ -135,8 +171,7 @@ struct RecordLog {
 	uint64_t         capacity = 0, stride = 0;
 	uint64_t         samples = 0;                     // records queued since enable / reset: the next sample's index
 	uint64_t         epoch = 0;                       // counts enable / disable / reset: a checkpoint's count belongs to one epoch
-	bool             saved_valid = false;
-	uint64_t         saved_epoch = 0, saved_samples = 0;
+	SaveMark         saved;                           // hp_state_save keeps the sample count only
 };
 // the probe recorder (hp_probes.hpp; hp_probes_*): log.input holds the lists (`lists` points into it)
 struct ProbeRecorder {
@@ -160,11 +195,7 @@ struct BedShapes {
 	uint64_t         applies = 0;                     // applies queued since the first shape was added (its parity picks the counter word)
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's beds belong to one epoch
 	BedHost          host;                            // host copies of the lists: a new shape rewrites the device block as a whole
-	// hp_state_save's copy of the bed at the listed cells
-	void*            saved = nullptr;
-	size_t           saved_room = 0;                  // cells it holds
-	bool             saved_taken = false;             // a checkpoint exists (with or without shapes) ...
-	uint64_t         saved_epoch = 0;                 // ... of this epoch
+	SaveSlot         saved;                           // hp_state_save's copy of the bed at the listed cells, in cells
 };
 
 // link groups (hp_links.hpp; hp_boundary_add_links): the groups themselves are Boundary entries of kind BDY_LINKS, in the order added; this
@@ -175,9 +206,7 @@ struct LinkStore {
 	hp_link_record_t* records = nullptr;              // device: LINK_MAX records, in the order the links were added
 	std::vector<uint64_t> taken;                      // GLOBAL ids of every end of every link, sorted: the repeated-cell check
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's records belong to one epoch
-	hp_link_record_t* saved = nullptr;                // hp_state_save's copy (LINK_MAX records)
-	bool             saved_taken = false;             // a checkpoint exists (with or without links) ...
-	uint64_t         saved_epoch = 0;                 // ... of this epoch
+	SaveSlot         saved;                           // hp_state_save's copy (LINK_MAX records)
 };
 
 // the infiltration (hp_soil.hpp; hp_boundary_add_infiltration): the boundary itself is a Boundary entry of kind BDY_INFILTRATION, at
@@ -190,9 +219,7 @@ struct SoilStore {
 	uint32_t         classes = 0;
 	uint64_t         pervious = 0;                    // cells of a class other than 0
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's F belongs to one epoch
-	double*          saved = nullptr;                 // hp_state_save's copy of F
-	bool             saved_taken = false;             // a checkpoint exists (with or without infiltration) ...
-	uint64_t         saved_epoch = 0;                 // ... of this epoch
+	SaveSlot         saved;                           // hp_state_save's copy of F, in cells
 };
 
 // the open boundary (hp_open.hpp; hp_boundary_add_open): its calls are Boundary entries of kind BDY_OPEN, in the order added; this is what
@@ -204,10 +231,7 @@ struct OpenStore {
 	uint64_t         room = 0;
 	std::vector<uint64_t> taken;                      // GLOBAL ids of every listed ring cell, sorted: the repeated-cell check
 	uint64_t         epoch = 0;                       // counts add / clear: a checkpoint's records belong to one epoch
-	hp_open_record_t* saved = nullptr;                // hp_state_save's copy (`saved_room` records)
-	uint64_t         saved_room = 0;
-	bool             saved_taken = false;             // a checkpoint exists (with or without segments) ...
-	uint64_t         saved_epoch = 0;                 // ... of this epoch
+	SaveSlot         saved;                           // hp_state_save's copy, in records
 };
 
 // the tracer (hp_tracer.hpp; hp_tracer_enable): the solute mass per unit area M, its two buffers and the sources' lists.  Nothing of it
@@ -222,10 +246,7 @@ struct TracerStore {
 	unsigned         sources = 0;
 	TracerHost       host;
 	uint64_t         epoch = 0;                       // counts enable / disable: a checkpoint's M belongs to one epoch
-	double*          saved = nullptr;                 // hp_state_save's copy of the current M
-	uint64_t         saved_iterations = 0;
-	bool             saved_taken = false;             // a checkpoint exists (with or without a tracer) ...
-	uint64_t         saved_epoch = 0;                 // ... of this epoch
+	SaveSlot         saved;                           // hp_state_save's copy of the current M, in cells; comes back with `iterations`
 };
 
 } // namespace

@@ -1044,7 +1044,7 @@ int hp_domain_destroy(hp_domain_t* d)
 	hipFree(d->z_state); hipFree(d->haz_words); hipFree(d->still_rec); hipFree(d->order_buf);
 	for (hipEvent_t e : d->tune_ev) if (e) hipEventDestroy(e);
 	hipFree(d->spec_state); hipFree(d->spec_scalars);
-	observers_destroy(d); actors_destroy(d);
+	participants_destroy(d);
 	if (d->host_scalars) hipHostFree(d->host_scalars);
 	if (d->ev_start) hipEventDestroy(d->ev_start);
 	if (d->ev_stop) hipEventDestroy(d->ev_stop);
@@ -1108,8 +1108,7 @@ int hp_state_save(hp_domain_t* d)
 	if (rc != HP_OK) return rc;
 	if (d->in_step) return fail(HP_ERR_STATE, "hp_state_save between hp_step_begin and hp_step_end");
 	if ((rc = repair_other_buffer(d)) != HP_OK) return rc;           // (after iteration pairs: see run_pair)
-	if ((rc = observers_save_reserve(d)) != HP_OK) return rc;        // (first: a failure leaves the checkpoint before it untouched)
-	if ((rc = actors_save_reserve(d)) != HP_OK) return rc;
+	if ((rc = participants_do(d, &Participant::reserve)) != HP_OK) return rc;    // (first: a failure leaves the checkpoint before it untouched)
 	const size_t bytes = d->cells * 4 * d->esize;
 	const size_t sc_bytes = d->desc.precision == 8 ? sizeof(Scalars<double>) : sizeof(Scalars<float>);
 	// BOTH ping-pong buffers: the one the next iteration writes is not dead -- cells whose whole neighbourhood is dry are left
@@ -1120,8 +1119,7 @@ int hp_state_save(hp_domain_t* d)
 	if ((rc = snapshot_take(d, d->saved_state, d->saved_scalars, d->facts->use_alt)) != HP_OK) return rc;
 	d->facts.checkpoint_taken();
 	d->saved_valid = true;
-	if ((rc = observers_save(d)) != HP_OK) return rc;
-	return actors_save(d);
+	return participants_do(d, &Participant::save);
 }
 
 int hp_state_restore(hp_domain_t* d)
@@ -1153,8 +1151,7 @@ int hp_state_restore(hp_domain_t* d)
 	                                                                      // iterations bench.py's restore found one in flight nearly every time and the timed
 	                                                                      // region ran on a choice made for the pre-warmed flood)
 	d->fork_is_advance = false;
-	if ((rc = observers_restore(d)) != HP_OK) return rc;
-	return actors_restore(d);
+	return participants_do(d, &Participant::restore);
 }
 
 int hp_domain_download(hp_domain_t* d, int which, void* host, int64_t row0, int64_t nrows)

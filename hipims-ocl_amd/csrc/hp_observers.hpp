@@ -1,7 +1,7 @@
 // hp_observers.hpp -- the four observers of a domain, host side: the output stage (hp_output.hpp, hp_overview.hpp, hp_sparse.hpp), the peak tracker
 // (hp_peaks.hpp), the probe recorder (hp_probes.hpp) and the zone recorder (hp_zones.hpp).  They read the state the solver leaves behind and never change it.  Here:
 // their entry points of include/hipims_mi.h, and what hp_state_save / hp_state_restore / hp_domain_destroy do for each of them
-// (*_save, *_restore, *_destroy; observers_* calls them in order).  The two recorders share one record log (log_*): their own entry points keep the argument
+// (*_save, *_restore, *_destroy; hp_actors.hpp's PARTICIPANTS lists them in order).  The two recorders share one record log (log_*): their own entry points keep the argument
 // checks, what they upload and the launch.  Their state is declared in hp_domain.hpp (OutputStage, PeakTracker, RecordLog, ProbeRecorder, ZoneRecorder).  Included
 // once by hp_engine.hip, after hp_domain.hpp: the library stays one translation unit.
 #pragma once
@@ -112,12 +112,12 @@ int peaks_reset_queue(hp_domain* d)
 	return HP_OK;
 }
 
-void peaks_destroy(hp_domain* d) { hipFree(d->peaks.acc); hipFree(d->peaks.saved); }
+void peaks_destroy(hp_domain* d) { hipFree(d->peaks.acc); slot_free(d->peaks.saved); }
 
-// frees the tracker (the stream is drained first: queued samples and reads still use the accumulators)
+// frees the tracker, the mark of its checkpoint included (the stream is drained first: queued samples and reads still use the accumulators)
 int peaks_release(hp_domain* d)
 {
-	if (!d->peaks.on && !d->peaks.saved) return HP_OK;
+	if (!d->peaks.on && !d->peaks.saved.copy) return HP_OK;
 	HIP_TRY(hipStreamSynchronize(d->stream));
 	peaks_destroy(d);
 	const uint64_t epoch = d->peaks.epoch + (d->peaks.on ? 1 : 0);
@@ -130,31 +130,27 @@ int peaks_release(hp_domain* d)
 // with the checkpoint before it, state and peaks, untouched
 int peaks_save_reserve(hp_domain* d)
 {
-	if (!d->peaks.on || d->peaks.saved) return HP_OK;
-	return alloc_or_fail(&d->peaks.saved, peaks_bytes(d), "hp_state_save: cannot allocate the copy of the peak accumulators: ");
+	return slot_reserve(d->stream, d->peaks.saved, d->peaks.on ? peaks_bytes(d) : 0, 1, "hp_state_save: cannot allocate the copy of the peak accumulators: ");
 }
-// ... and behind the state's copies, while the tracker is on: accumulators and block in one copy
+// ... and behind the state's copies, while the tracker is on: accumulators and block in one copy.  Off, it keeps no mark
 int peaks_save(hp_domain* d)
 {
-	d->peaks.saved_valid = false;
-	if (!d->peaks.on) return HP_OK;
-	HIP_TRY(hipMemcpyAsync(d->peaks.saved, d->peaks.acc, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
-	d->peaks.saved_epoch = d->peaks.epoch;
-	d->peaks.saved_samples = d->peaks.samples;
-	d->peaks.saved_valid = true;
+	PeakTracker& P = d->peaks;
+	if (P.on) return slot_take(d->stream, P.saved, P.acc, peaks_bytes(d), P.epoch, P.samples);
+	P.saved.mark.drop();
 	return HP_OK;
 }
-// hp_state_restore, behind the state's copies
+// hp_state_restore, behind the state's copies, while the tracker is on.  No checkpoint of its own, stale or none at all: the peaks are reset
 int peaks_restore(hp_domain* d)
 {
-	if (!d->peaks.on) return HP_OK;
-	if (d->peaks.saved_valid && d->peaks.saved_epoch == d->peaks.epoch) {
-		HIP_TRY(hipMemcpyAsync(d->peaks.acc, d->peaks.saved, peaks_bytes(d), hipMemcpyDeviceToDevice, d->stream));
-		d->peaks.samples = d->peaks.saved_samples;
-		return HP_OK;
+	PeakTracker& P = d->peaks;
+	if (!P.on) return HP_OK;
+	int rc;
+	if (P.saved.mark.verdict(P.epoch) == Verdict::BRING_BACK) {
+		if ((rc = slot_bring_back(d->stream, P.saved, P.acc, peaks_bytes(d))) == HP_OK) P.samples = P.saved.mark.count;
+		return rc;
 	}
-	const int rc = peaks_reset_queue(d);                                 // (the time block has come back with the state: t_previous is the restored time)
-	if (rc != HP_OK) return rc;
+	if ((rc = peaks_reset_queue(d)) != HP_OK) return rc;                  // (the time block has come back with the state: t_previous is the restored time)
 	log_line(HP_LOG_WARNING, "hp_state_restore: the saved state holds no peaks (the tracker was enabled after it was taken): the peaks are reset");
 	return HP_OK;
 }
@@ -185,22 +181,31 @@ int log_release(hp_domain* d, const Recorder& r)
 	return HP_OK;
 }
 
-// hp_state_save: the sample count only (the records taken after it are re-recorded by the samples a restore repeats)
-void log_save(hp_domain* d, const Recorder& r)
+// hp_state_save: the sample count only (the records taken after it are re-recorded by the samples a restore repeats).  Off, it keeps no mark
+int log_save(hp_domain* d, const Recorder& r)
 {
 	RecordLog& g = r.log(d);
-	g.saved_valid = g.on;
-	g.saved_epoch = g.epoch;
-	g.saved_samples = g.samples;
+	if (g.on) g.saved.take(g.epoch, g.samples); else g.saved.drop();
+	return HP_OK;
 }
-void log_restore(hp_domain* d, const Recorder& r)
+// hp_state_restore, while the recorder is on.  No count of its own, stale or none at all: the count is 0
+int log_restore(hp_domain* d, const Recorder& r)
 {
 	RecordLog& g = r.log(d);
-	if (!g.on) return;
-	const bool mine = g.saved_valid && g.saved_epoch == g.epoch;
-	g.samples = mine ? g.saved_samples : 0;
+	if (!g.on) return HP_OK;
+	const bool mine = g.saved.verdict(g.epoch) == Verdict::BRING_BACK;
+	g.samples = mine ? g.saved.count : 0;
 	if (!mine) log_line(HP_LOG_WARNING, std::string("hp_state_restore: the saved state holds no ") + r.noun + " sample count (the recorder was enabled or reset after it was taken): the count is 0");
+	return HP_OK;
 }
+// ... of either recorder, by name: what hp_actors.hpp's PARTICIPANTS lists.  (Named functions, not lambdas in the table: hipcc 7 mangled those
+// to the very symbols of the accessors in PROBES and ZONES above, _ZN12_GLOBAL__N_1UlP9hp_domainE_8__invokeES1_, and the table called these)
+int probes_save(hp_domain* d) { return log_save(d, PROBES); }
+int probes_restore(hp_domain* d) { return log_restore(d, PROBES); }
+void probes_destroy(hp_domain* d) { log_destroy(d, PROBES); }
+int zones_save(hp_domain* d) { return log_save(d, ZONES); }
+int zones_restore(hp_domain* d) { return log_restore(d, ZONES); }
+void zones_destroy(hp_domain* d) { log_destroy(d, ZONES); }
 
 // <prefix><call> on a recorder that is off, or inside a split step
 int log_check_state(hp_domain* d, const Recorder& r, const char* call)
@@ -302,12 +307,6 @@ int log_info(hp_domain* d, const Recorder& r, uint64_t* samples, uint64_t* capac
 	if (stride) *stride = r.log(d).stride;
 	return HP_OK;
 }
-
-// ---- what hp_state_save (the reserve: before it touches anything), hp_state_restore and hp_domain_destroy do for the four ----
-int observers_save_reserve(hp_domain* d) { return peaks_save_reserve(d); }
-int observers_save(hp_domain* d) { const int rc = peaks_save(d); if (rc == HP_OK) { log_save(d, PROBES); log_save(d, ZONES); } return rc; }
-int observers_restore(hp_domain* d) { const int rc = peaks_restore(d); if (rc == HP_OK) { log_restore(d, PROBES); log_restore(d, ZONES); } return rc; }
-void observers_destroy(hp_domain* d) { out_destroy(d); peaks_destroy(d); log_destroy(d, PROBES); log_destroy(d, ZONES); }
 
 } // namespace
 
