@@ -18,6 +18,7 @@ static_assert(sizeof(hp_bed_shape_desc_t) == 40 && sizeof(hp_bed_info_t) == 48, 
 static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeof(LinkDev) == 56, "hp_link_*_t layout");
 static_assert(sizeof(hp_soil_class_t) == 32 && sizeof(hp_infiltration_desc_t) == 32, "hp_soil_class_t / hp_infiltration_desc_t layout");
 static_assert(sizeof(hp_tracer_desc_t) == 16, "hp_tracer_desc_t layout");
+static_assert(sizeof(hp_tracer_set_desc_t) == 24, "hp_tracer_set_desc_t layout");
 static_assert(sizeof(hp_open_segment_t) == 24 && sizeof(hp_open_record_t) == 32 && sizeof(OpenDev) == 24, "hp_open_*_t layout");
 
 // ---- the boundaries ----
@@ -295,8 +296,12 @@ template <typename T> int apply_tracer(hp_domain* d, const void* source)
 	if (R.sources && R.lists.count)
 		hipLaunchKernelGGL(tracer_sources<T>, dim3(stream_blocks((size_t)R.lists.count)), dim3(256), 0, d->stream, p, (const Scalars<T>*)d->scalars, R.lists, R.M[R.phase]);
 	const dim3 block(64, 4), grid((unsigned)((p.cols + 63) / 64), (unsigned)((p.rows + 3) / 4));
-	hipLaunchKernelGGL(tracer_step<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
-	                   (const double*)R.M[R.phase], R.M[R.phase ^ 1]);
+	if (R.set)                                                                // every species by one launch, the face fluxes formed once
+		hipLaunchKernelGGL(tracer_step_set<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
+		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1], R.species, R.rates);
+	else
+		hipLaunchKernelGGL(tracer_step<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
+		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1]);
 	HIP_TRY(hipGetLastError());
 	R.phase ^= 1;
 	++R.iterations;
@@ -308,11 +313,12 @@ void tracer_destroy(hp_domain* d)
 	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.block); slot_free(R.saved);
 	R.M[0] = R.M[1] = nullptr; R.block = nullptr;
 }
-// the copy: the current M of every cell, while the domain has a tracer (hp_tracer_disable frees it with the rest); `iterations` goes with it
-inline size_t tracer_bytes(const hp_domain* d) { return d->tracer.on ? d->cells * sizeof(double) : 0; }
+// the copy: the current M of every cell and species, while the domain has a tracer (hp_tracer_disable frees it with the rest); `iterations` goes with it
+inline size_t tracer_units(const hp_domain* d) { return d->tracer.on ? (size_t)d->tracer.species * d->cells : 0; }
+inline size_t tracer_bytes(const hp_domain* d) { return tracer_units(d) * sizeof(double); }
 int tracer_save_reserve(hp_domain* d)
 {
-	return slot_reserve(d->stream, d->tracer.saved, d->tracer.on ? d->cells : 0, sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
+	return slot_reserve(d->stream, d->tracer.saved, tracer_units(d), sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
 }
 int tracer_save(hp_domain* d)
 {
@@ -323,7 +329,7 @@ int tracer_save(hp_domain* d)
 int tracer_restore(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	const Verdict v = restore_verdict(R.saved, R.epoch, "hp_state_restore: the tracer was enabled or disabled after the state was saved: the tracer is left as it is");
+	const Verdict v = restore_verdict(R.saved, R.epoch, "hp_state_restore: the tracer was enabled or disabled, or its species changed, after the state was saved: the tracer is left as it is");
 	if (v != Verdict::BRING_BACK || !R.on) return HP_OK;
 	const int rc = slot_bring_back(d->stream, R.saved, R.M[R.phase], tracer_bytes(d));
 	if (rc == HP_OK) R.iterations = R.saved.mark.count;
@@ -828,13 +834,10 @@ int hp_open_info(hp_domain_t* d, uint32_t* segments, uint64_t* cells)
 }
 
 // ---- the tracer (hp_tracer.hpp) ----
-int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc)
+// what hp_tracer_enable and hp_tracer_enable_set share behind their argument checks: the refusals, then `species` planes in each of the
+// two buffers (`initial`: that many planes, or NULL for zeros; `decay`: that many rates, or NULL for zeros)
+static int tracer_enable_planes(hp_domain_t* d, const std::string& who, const unsigned species, const double* initial, const double* decay, const bool set)
 {
-	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_enable)
-	const std::string who = "hp_tracer_enable";
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	std::string why;
-	if (!validate_tracer_enable(desc, (uint64_t)d->cells, why)) return fail(HP_ERR_INVALID, why);
 	if (d->desc.scheme != HP_SCHEME_GODUNOV)
 		return fail(HP_ERR_UNSUPPORTED, who + ": the tracer takes its face fluxes from the Godunov scheme's face solve; this domain runs another scheme");
 	if (d->desc.global_rows != d->desc.rows)
@@ -847,12 +850,12 @@ int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc)
 	TracerStore& R = d->tracer;
 	if (R.on) return fail(HP_ERR_STATE, who + ": the domain has a tracer already (hp_tracer_disable removes it)");
 	// everything it needs first: if any of it cannot be had, the domain stays as it is
-	const size_t bytes = d->cells * sizeof(double);
+	const size_t bytes = (size_t)species * d->cells * sizeof(double);
 	double* m0 = nullptr;
 	double* m1 = nullptr;
 	if ((rc = alloc_or_fail((void**)&m0, bytes, who + ": cannot allocate the tracer: ")) != HP_OK) return rc;
 	if ((rc = alloc_or_fail((void**)&m1, bytes, who + ": cannot allocate the tracer's second buffer: ")) != HP_OK) { hipFree(m0); return rc; }
-	hipError_t e = desc->initial ? hipMemcpyAsync(m0, desc->initial, bytes, hipMemcpyHostToDevice, d->stream) : hipMemsetAsync(m0, 0, bytes, d->stream);
+	hipError_t e = initial ? hipMemcpyAsync(m0, initial, bytes, hipMemcpyHostToDevice, d->stream) : hipMemsetAsync(m0, 0, bytes, d->stream);
 	if (e == hipSuccess) e = hipMemsetAsync(m1, 0, bytes, d->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(d->stream);                 // (the caller's raster is free on return)
 	if (e != hipSuccess) {
@@ -863,11 +866,33 @@ int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc)
 	}
 	d->facts.boundaries_or_bed_changed();
 	R.on = true;
+	R.set = set;
+	R.species = species;
+	R.rates = TracerRates{};
+	for (unsigned s = 0; decay && s < species; ++s) R.rates.lambda[s] = decay[s];
 	R.M[0] = m0; R.M[1] = m1;
 	R.phase = 0;
 	R.iterations = 0;
 	++R.epoch;
 	return refresh_fusable(d);
+}
+
+int hp_tracer_enable(hp_domain_t* d, const hp_tracer_desc_t* desc)
+{
+	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_enable)
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	std::string why;
+	if (!validate_tracer_enable(desc, (uint64_t)d->cells, why)) return fail(HP_ERR_INVALID, why);
+	return tracer_enable_planes(d, "hp_tracer_enable", 1, desc->initial, nullptr, false);
+}
+
+int hp_tracer_enable_set(hp_domain_t* d, const hp_tracer_set_desc_t* desc)
+{
+	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_set_enable)
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	std::string why;
+	if (!validate_tracer_set_enable(desc, (uint64_t)d->cells, why)) return fail(HP_ERR_INVALID, why);
+	return tracer_enable_planes(d, "hp_tracer_enable_set", desc->species, desc->initial, desc->decay, true);
 }
 
 int hp_tracer_sources_clear(hp_domain_t* d)
@@ -897,6 +922,9 @@ int hp_tracer_disable(hp_domain_t* d)
 	tracer_destroy(d);
 	d->facts.boundaries_or_bed_changed();
 	R.on = false;
+	R.set = false;
+	R.species = 0;
+	R.rates = TracerRates{};
 	R.lists = TracerLists{};
 	R.sources = 0;
 	R.host = TracerHost{};
@@ -905,15 +933,16 @@ int hp_tracer_disable(hp_domain_t* d)
 	return refresh_fusable(d);
 }
 
-int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries)
+// one source for species `species` (hp_tracer_add_source: species 0)
+static int tracer_add_source_to(hp_domain_t* d, const std::string& who, const uint32_t species, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries)
 {
 	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_source)
-	const std::string who = "hp_tracer_add_source";
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	TracerStore& R = d->tracer;
 	std::vector<uint64_t> listed;
 	std::string why;
-	if (!validate_tracer_source(cells, count, series, entries, R.host, (uint64_t)d->desc.cols, (uint64_t)d->desc.rows, listed, why)) return fail(HP_ERR_INVALID, why);
+	if (!validate_tracer_source(cells, count, series, entries, R.host, (uint64_t)d->desc.cols, (uint64_t)d->desc.rows, listed, why, species, std::max(R.species, 1u), who))
+		return fail(HP_ERR_INVALID, why);
 	int rc = check_domain(d);
 	if (rc != HP_OK) return rc;
 	if (!R.on) return fail(HP_ERR_STATE, who + ": the domain has no tracer (hp_tracer_enable)");
@@ -921,6 +950,7 @@ int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, 
 	TracerHost next = R.host;
 	next.cells.insert(next.cells.end(), cells, cells + count);
 	next.source_of.resize(next.cells.size(), (unsigned char)R.sources);
+	next.species_of.resize(next.cells.size(), (unsigned char)species);
 	next.series.insert(next.series.end(), series, series + 2 * (size_t)entries);
 	next.series_off.push_back((unsigned)(next.series.size() / 2));
 	const unsigned sources = R.sources + 1;
@@ -942,6 +972,8 @@ int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, 
 	char* b = (char*)fresh;
 	R.lists.cells = (const unsigned long long*)(b + l.cells);
 	R.lists.source_of = (const unsigned char*)(b + l.source_of);
+	R.lists.species_of = (const unsigned char*)(b + l.species_of);
+	R.lists.plane = (unsigned long long)d->cells;
 	R.lists.series = (const double*)(b + l.series);
 	R.lists.series_off = (const unsigned*)(b + l.series_off);
 	R.lists.count = next.cells.size();
@@ -951,36 +983,57 @@ int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, 
 	R.host = std::move(next);
 	return HP_OK;
 }
-
-int hp_tracer_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows)
+int hp_tracer_add_source(hp_domain_t* d, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries)
 {
-	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!raster) return fail(HP_ERR_INVALID, "hp_tracer_read: raster == NULL");
-	int rc = check_rows(d, row0, nrows);
-	if (rc != HP_OK) return rc;
-	if ((rc = check_domain(d)) != HP_OK) return rc;
-	if (!d->tracer.on) return fail(HP_ERR_STATE, "hp_tracer_read: the domain has no tracer");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_read between hp_step_begin and hp_step_end");
-	if (nrows == 0) return HP_OK;
-	const size_t cols = (size_t)d->desc.cols;
-	HIP_TRY(hipMemcpyAsync(raster, d->tracer.M[d->tracer.phase] + (size_t)row0 * cols, (size_t)nrows * cols * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-	return HP_OK;
+	return tracer_add_source_to(d, "hp_tracer_add_source", 0, cells, count, series, entries);
+}
+int hp_tracer_add_source_to(hp_domain_t* d, uint32_t species, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries)
+{
+	return tracer_add_source_to(d, "hp_tracer_add_source_to", species, cells, count, series, entries);
 }
 
-int hp_tracer_write(hp_domain_t* d, const double* raster, int64_t row0, int64_t nrows)
+// the checks hp_tracer_read / hp_tracer_write and their per-species forms share, in the header's order; *plane: species' current plane
+static int tracer_plane(hp_domain_t* d, const std::string& who, const uint32_t species, const void* raster, int64_t row0, int64_t nrows, double** plane)
 {
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
-	if (!raster) return fail(HP_ERR_INVALID, "hp_tracer_write: raster == NULL");
+	if (!raster) return fail(HP_ERR_INVALID, who + ": raster == NULL");
+	const TracerStore& R = d->tracer;
+	if (species >= std::max(R.species, 1u))
+		return fail(HP_ERR_INVALID, who + ": species " + std::to_string(species) + " of a tracer of " + std::to_string(std::max(R.species, 1u)));
 	int rc = check_rows(d, row0, nrows);
 	if (rc != HP_OK) return rc;
 	if ((rc = check_domain(d)) != HP_OK) return rc;
-	if (!d->tracer.on) return fail(HP_ERR_STATE, "hp_tracer_write: the domain has no tracer");
-	if (d->in_step) return fail(HP_ERR_STATE, "hp_tracer_write between hp_step_begin and hp_step_end");
-	if (nrows == 0) return HP_OK;
-	const size_t cols = (size_t)d->desc.cols;
-	HIP_TRY(hipMemcpyAsync(d->tracer.M[d->tracer.phase] + (size_t)row0 * cols, raster, (size_t)nrows * cols * sizeof(double), hipMemcpyHostToDevice, d->stream));
+	if (!R.on) return fail(HP_ERR_STATE, who + ": the domain has no tracer");
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	*plane = R.M[R.phase] + (size_t)species * d->cells + (size_t)row0 * (size_t)d->desc.cols;
+	return HP_OK;
+}
+static int tracer_read_plane(hp_domain_t* d, const std::string& who, uint32_t species, double* raster, int64_t row0, int64_t nrows)
+{
+	double* plane = nullptr;
+	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane);
+	if (rc != HP_OK || nrows == 0) return rc;
+	HIP_TRY(hipMemcpyAsync(raster, plane, (size_t)nrows * (size_t)d->desc.cols * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+	return HP_OK;
+}
+static int tracer_write_plane(hp_domain_t* d, const std::string& who, uint32_t species, const double* raster, int64_t row0, int64_t nrows)
+{
+	double* plane = nullptr;
+	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane);
+	if (rc != HP_OK || nrows == 0) return rc;
+	HIP_TRY(hipMemcpyAsync(plane, raster, (size_t)nrows * (size_t)d->desc.cols * sizeof(double), hipMemcpyHostToDevice, d->stream));
 	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (the caller's raster is free on return)
 	return HP_OK;
+}
+int hp_tracer_read(hp_domain_t* d, double* raster, int64_t row0, int64_t nrows) { return tracer_read_plane(d, "hp_tracer_read", 0, raster, row0, nrows); }
+int hp_tracer_write(hp_domain_t* d, const double* raster, int64_t row0, int64_t nrows) { return tracer_write_plane(d, "hp_tracer_write", 0, raster, row0, nrows); }
+int hp_tracer_read_species(hp_domain_t* d, uint32_t species, double* raster, int64_t row0, int64_t nrows)
+{
+	return tracer_read_plane(d, "hp_tracer_read_species", species, raster, row0, nrows);
+}
+int hp_tracer_write_species(hp_domain_t* d, uint32_t species, const double* raster, int64_t row0, int64_t nrows)
+{
+	return tracer_write_plane(d, "hp_tracer_write_species", species, raster, row0, nrows);
 }
 
 int hp_tracer_info(hp_domain_t* d, uint64_t* iterations, uint32_t* sources, uint64_t* source_cells)
@@ -989,6 +1042,15 @@ int hp_tracer_info(hp_domain_t* d, uint64_t* iterations, uint32_t* sources, uint
 	if (iterations) *iterations = d->tracer.on ? d->tracer.iterations : 0;
 	if (sources) *sources = d->tracer.sources;
 	if (source_cells) *source_cells = (uint64_t)d->tracer.host.cells.size();
+	return HP_OK;
+}
+
+int hp_tracer_set_info(hp_domain_t* d, uint32_t* species, double* decay)
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const TracerStore& R = d->tracer;
+	if (species) *species = R.on ? R.species : 0;
+	for (unsigned s = 0; decay && R.on && s < R.species; ++s) decay[s] = R.rates.lambda[s];
 	return HP_OK;
 }
 

@@ -238,6 +238,9 @@ struct OpenStore {
 // exists while the domain has none
 struct TracerStore {
 	bool             on = false;
+	bool             set = false;                     // enabled by hp_tracer_enable_set: tracer_step_set moves it (K == 1 included)
+	unsigned         species = 0;                     // K: the planes of each buffer, species after species (a single tracer: 1; none: 0)
+	TracerRates      rates = {};                      // the species' decay rates (a single tracer: zeros)
 	double*          M[2] = {nullptr, nullptr};       // device: M[phase] is the current M, the other one what the next step writes
 	int              phase = 0;                       // its own, independent of the state's ping-pong
 	uint64_t         iterations = 0;                  // steps since hp_tracer_enable (as restored)

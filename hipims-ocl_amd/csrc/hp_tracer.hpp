@@ -6,7 +6,9 @@
 // the kernels use it, tests/tracer_probe.cpp includes this file with a host compiler, and frontend.Tracer restates it in NumPy.  It
 // uses correctly rounded add, multiply, divide and compare only; nothing is fused: hp_engine.hip's translation unit is built with
 // -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.  The face fluxes themselves are the STRICT face solve of
-// hp_math.hpp in the domain's precision, whatever the domain's math mode.  The contract is in include/hipims_mi.h; the host side
+// hp_math.hpp in the domain's precision, whatever the domain's math mode.  A tracer SET (hp_tracer_enable_set) carries up to 8 species,
+// planes of M one after the other, by one launch of tracer_step_set -- the face fluxes formed once per cell -- and lets each decay
+// (tracer_decay; frontend.TracerSet).  The contract is in include/hipims_mi.h; the host side
 // (hp_tracer_*, the launches in front of the flux kernel, M's part of a checkpoint) is in hp_actors.hpp.
 #pragma once
 #include "../../include/hipims_mi.h"
@@ -54,6 +56,15 @@ HP_TRACER_FN double tracer_source_add(const double M, const double rate, const d
 	return M + add;
 }
 
+// step 6 (tracer sets): first-order decay at the rate lambda over dt, implicit Euler; lambda == 0 divides nothing
+HP_TRACER_FN double tracer_decay(const double M, const double lambda, const double dt)
+{
+	if (!(lambda > 0.0 && dt > 0.0)) return M;
+	const double growth = lambda * dt;
+	const double denom = 1.0 + growth;
+	return M / denom;
+}
+
 // the rate of a source at time t: the bed shapes' rule on {time, mass rate} pairs
 HP_TRACER_FN double tracer_rate(const double* series, const unsigned n, const double t) { return bed_fraction(series, n, t); }
 
@@ -69,9 +80,10 @@ namespace hp {
 
 // The host's copies of a domain's source lists (TracerStore, hp_domain.hpp)
 struct TracerHost {
-	std::vector<uint64_t> listed;                     // ids of every cell of every source, sorted: the repeated-cell check
+	std::vector<uint64_t> listed;                     // species * (cols * rows) + id of every cell of every source, sorted: the repeated-cell check
 	std::vector<uint64_t> cells;                      // source after source
 	std::vector<unsigned char> source_of;
+	std::vector<unsigned char> species_of;            // the species of each listed cell (all 0 for a single tracer)
 	std::vector<double>   series;
 	std::vector<unsigned> series_off = {0u};          // [sources + 1]
 };
@@ -92,13 +104,37 @@ inline bool validate_tracer_enable(const hp_tracer_desc_t* desc, const uint64_t 
 }
 
 // -------------------------------------------------------------------------------------------------
-// validate_tracer_source : every argument error of hp_tracer_add_source that needs no device, in the order the header lists them.
-//     `have`: the domain's lists so far.  On success `listed_after` holds have.listed merged with the new cells.
+// validate_tracer_set_enable : every argument error of hp_tracer_enable_set that needs no device.  `cells`: cols * rows of the local array.
+//     Returns false with `why` set; a bad initial value is named by its species and its cell.
+// -------------------------------------------------------------------------------------------------
+inline bool validate_tracer_set_enable(const hp_tracer_set_desc_t* desc, const uint64_t cells, std::string& why)
+{
+	const std::string who = "hp_tracer_enable_set";
+	if (!desc) { why = who + ": desc == NULL"; return false; }
+	if (desc->struct_size != sizeof(hp_tracer_set_desc_t)) { why = "hp_tracer_set_desc_t size mismatch (ABI)"; return false; }
+	if (desc->species < 1 || desc->species > HP_TRACER_MAX_SPECIES) { why = who + ": species outside 1..8"; return false; }
+	if (desc->decay)
+		for (uint32_t s = 0; s < desc->species; ++s)
+			if (!std::isfinite(desc->decay[s]) || desc->decay[s] < 0.0) { why = who + ": species " + std::to_string(s) + ": the decay rate must be finite and >= 0"; return false; }
+	if (desc->initial)
+		for (uint32_t s = 0; s < desc->species; ++s)
+			for (uint64_t i = 0; i < cells; ++i) {
+				const double m = desc->initial[(uint64_t)s * cells + i];
+				if (!std::isfinite(m) || m < 0.0) { why = who + ": species " + std::to_string(s) + ", cell " + std::to_string(i) + ": initial must be finite and >= 0"; return false; }
+			}
+	return true;
+}
+
+// -------------------------------------------------------------------------------------------------
+// validate_tracer_source : every argument error of hp_tracer_add_source (`who`; hp_tracer_add_source_to likewise) that needs no device, in
+//     the order the header lists them.  `have`: the domain's lists so far; `species` of `species_count`: the species the source feeds (a
+//     single tracer: 0 of 1).  A cell may be listed once per species.  On success `listed_after` holds have.listed merged with the new keys.
 // -------------------------------------------------------------------------------------------------
 inline bool validate_tracer_source(const uint64_t* cells, const uint64_t count, const double* series, const uint32_t entries, const TracerHost& have,
-                                   const uint64_t cols, const uint64_t rows, std::vector<uint64_t>& listed_after, std::string& why)
+                                   const uint64_t cols, const uint64_t rows, std::vector<uint64_t>& listed_after, std::string& why,
+                                   const uint32_t species = 0, const uint32_t species_count = 1, const std::string& who = "hp_tracer_add_source")
 {
-	const std::string who = "hp_tracer_add_source";
+	if (species >= species_count) { why = who + ": species " + std::to_string(species) + " of a tracer of " + std::to_string(species_count); return false; }
 	if (!cells || !series) { why = who + ": cells / series == NULL"; return false; }
 	if (entries < 1 || entries > TRACER_MAX_SERIES) { why = who + ": entries outside 1..4096"; return false; }
 	if (count < 1 || count > TRACER_MAX_CELLS) { why = who + ": count outside 1..1048576"; return false; }
@@ -112,22 +148,24 @@ inline bool validate_tracer_source(const uint64_t* cells, const uint64_t count, 
 		const uint64_t y = cells[k] / cols, x = cells[k] - y * cols;
 		if (x == 0 || y == 0 || x + 1 >= cols || y + 1 >= rows) { why = who + ": cell " + std::to_string(cells[k]) + " lies on the grid's edge ring"; return false; }
 	}
+	const uint64_t plane = cols * rows;                                       // a listed cell's key: species * plane + cell
 	std::vector<uint64_t> sorted(cells, cells + count);
+	for (uint64_t& key : sorted) key += (uint64_t)species * plane;
 	std::sort(sorted.begin(), sorted.end());
 	auto twice = std::adjacent_find(sorted.begin(), sorted.end());
-	if (twice != sorted.end()) { why = who + ": cell " + std::to_string(*twice) + " is listed twice"; return false; }
+	if (twice != sorted.end()) { why = who + ": cell " + std::to_string(*twice - (uint64_t)species * plane) + " is listed twice"; return false; }
 	if (have.series_off.size() > TRACER_MAX_SOURCES) { why = who + ": more than 64 sources"; return false; }
 	if (have.listed.size() + count > TRACER_MAX_CELLS) { why = who + ": more than 1048576 cells over all sources"; return false; }
 	listed_after.resize(have.listed.size() + (size_t)count);
 	std::merge(have.listed.begin(), have.listed.end(), sorted.begin(), sorted.end(), listed_after.begin());
 	twice = std::adjacent_find(listed_after.begin(), listed_after.end());
-	if (twice != listed_after.end()) { why = who + ": cell " + std::to_string(*twice) + " is listed twice (another source has it)"; return false; }
+	if (twice != listed_after.end()) { why = who + ": cell " + std::to_string(*twice - (uint64_t)species * plane) + " is listed twice (another source has it)"; return false; }
 	return true;
 }
 
 // The device block of the lists of n cells, `pairs` series entries and `sources` sources (TracerLists points into it), in bytes:
-// [cells: n x 8 | series: pairs x 16 | series_off: (sources + 1) x 4, to 8 | source_of: n]
-struct TracerLayout { size_t cells, series, series_off, source_of, bytes; };
+// [cells: n x 8 | series: pairs x 16 | series_off: (sources + 1) x 4, to 8 | source_of: n | species_of: n]
+struct TracerLayout { size_t cells, series, series_off, source_of, species_of, bytes; };
 inline TracerLayout tracer_layout(const size_t n, const size_t pairs, const size_t sources)
 {
 	TracerLayout l;
@@ -135,7 +173,8 @@ inline TracerLayout tracer_layout(const size_t n, const size_t pairs, const size
 	l.series = l.cells + n * 8;
 	l.series_off = l.series + pairs * 16;
 	l.source_of = l.series_off + ((sources + 1) * 4 + 7) / 8 * 8;
-	l.bytes = l.source_of + std::max<size_t>(n, 1);
+	l.species_of = l.source_of + std::max<size_t>(n, 1);
+	l.bytes = l.species_of + std::max<size_t>(n, 1);
 	return l;
 }
 inline std::vector<unsigned char> tracer_image(const TracerLayout& l, const TracerHost& h)
@@ -144,6 +183,7 @@ inline std::vector<unsigned char> tracer_image(const TracerLayout& l, const Trac
 	if (!h.cells.empty()) {
 		std::memcpy(image.data() + l.cells, h.cells.data(), h.cells.size() * 8);
 		std::memcpy(image.data() + l.source_of, h.source_of.data(), h.source_of.size());
+		std::memcpy(image.data() + l.species_of, h.species_of.data(), h.species_of.size());
 	}
 	if (!h.series.empty()) std::memcpy(image.data() + l.series, h.series.data(), h.series.size() * 8);
 	std::memcpy(image.data() + l.series_off, h.series_off.data(), h.series_off.size() * 4);
@@ -161,6 +201,8 @@ namespace hp {
 struct TracerLists {
 	const unsigned long long* cells;              // [count] flat ids of the local array
 	const unsigned char*      source_of;          // [count] the cell's source
+	const unsigned char*      species_of;         // [count] the plane of M the entry writes (a single tracer: all 0)
+	unsigned long long        plane;              // cells of one plane: cols * rows
 	const double*             series;             // all sources' {time, mass rate} pairs, source after source
 	const unsigned*           series_off;         // [sources + 1] entries (pairs) into `series`
 	unsigned long long        count;
@@ -170,8 +212,8 @@ struct TracerLists {
 // -------------------------------------------------------------------------------------------------
 // tracer_sources : one small launch over the listed cells, in front of tracer_step, in place on the M the step is about to read.
 //     Per block the first `sources` threads form the sources' rates into LDS from the device's own "Time" (a binary search each),
-//     one barrier, then the cells by grid stride.  Nothing happens when dt <= 0.  A cell is listed once over all sources, so no two
-//     threads touch the same entry.
+//     one barrier, then the cells by grid stride.  Nothing happens when dt <= 0.  Each entry writes the plane of its species (M: the
+//     current planes, species after species); a (species, cell) pair is listed once over all sources, so no two threads touch the same value.
 // -------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void tracer_sources(const Params<T> p, const Scalars<T>* __restrict__ sc, const TracerLists L, double* __restrict__ M)
@@ -186,8 +228,8 @@ __global__ __launch_bounds__(256) void tracer_sources(const Params<T> p, const S
 	__syncthreads();
 	const double dx = (double)p.dx;
 	for (unsigned long long k = (unsigned long long)blockIdx.x * 256u + threadIdx.x; k < L.count; k += (unsigned long long)gridDim.x * 256u) {
-		const unsigned long long cell = L.cells[k];
-		M[cell] = tracer_source_add(M[cell], rate[L.source_of[k]], dt, dx);
+		const unsigned long long at = (unsigned long long)L.species_of[k] * L.plane + L.cells[k];
+		M[at] = tracer_source_add(M[at], rate[L.source_of[k]], dt, dx);
 	}
 }
 
@@ -235,6 +277,102 @@ __global__ __launch_bounds__(256) void tracer_step(const Params<T> p, const Scal
 	const double ce = tracer_conc(M0[iE], (double)cE.z - (double)zE);
 	const double cw = tracer_conc(M0[iW], (double)cW.z - (double)zW);
 	M1[id] = tracer_update(m, cc, cn, cs, ce, cw, FN, FS, FE, FW, (double)dt, (double)p.dx);
+}
+
+// The decay rates of a set's species, by value in the kernel's arguments
+struct TracerRates { double lambda[HP_TRACER_MAX_SPECIES]; };
+
+constexpr int TRACER_SET_ROWS = 4;                    // rows of a block of tracer_step_set: one wave each
+constexpr int TRACER_SET_PITCH = 66;                  // 64 columns and the two halo columns
+
+// -------------------------------------------------------------------------------------------------
+// tracer_step_set : tracer_step for the K species of a set (hp_tracer_enable_set), planes of p.cols * p.rows doubles, species after
+//     species.  Same block shape, same copy cases, same four STRICT face solves -- formed ONCE per cell: they depend on the water only.
+//     Then per species: every lane forms the concentration of its own cell (one correctly rounded division), the lanes of the first
+//     two waves also those of the tile's halo (its row below, its row above, its two side columns: 136 cells), all into an LDS tile
+//     of (rows + 2) x 66 doubles; one barrier; the lane reads its four neighbours' from the tile and updates (steps 4 and 5), then
+//     decays (step 6).  That is (256 + 136) divisions a block and species where five per lane would be 1280.  A neighbour's
+//     concentration is the same statement on the same operands whichever lane forms it, so the bits are tracer_step's.  The tile is
+//     double-buffered: one barrier per species.  Lanes of the copy cases and lanes outside the array reach every barrier (a flag, no
+//     return); a block without a single moving cell -- still or dry ground, dt <= 0 -- skips the tile: block-uniform, by one
+//     __syncthreads_or.  Writes M1 at EVERY cell of every plane.
+// -------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void tracer_step_set(const Params<T> p, const Scalars<T>* __restrict__ sc, const T* __restrict__ bed,
+                                                       const State4<T>* __restrict__ src, const double* __restrict__ M0, double* __restrict__ M1,
+                                                       const unsigned species, const TracerRates rates)
+{
+	__shared__ double tile[2][TRACER_SET_ROWS + 2][TRACER_SET_PITCH];
+	const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
+	const long x0 = (long)blockIdx.x * 64, y0 = (long)blockIdx.y * TRACER_SET_ROWS;
+	const long x = x0 + tx, y = y0 + ty;
+	const bool inside = x < p.cols && y < p.rows;
+	const size_t plane = (size_t)p.cols * (size_t)p.rows;
+	const size_t id = inside ? (size_t)y * p.cols + x : 0;
+	const T dt = sc->dt;
+	const double dt64 = (double)dt, dx64 = (double)p.dx;
+
+	// the copy cases in the contract's order, as a flag; the cell's own raw depth is needed whatever the verdict (its neighbours read c)
+	bool moves = inside && !(x <= 0 || y <= 0 || x >= p.cols - 1 || y >= p.rows - 1 || dt <= T(0));
+	double hC = 0.0;
+	double FN = 0.0, FS = 0.0, FE = 0.0, FW = 0.0;
+	if (inside && dt > T(0)) {
+		const State4<T> c = src[id];
+		const T zb = bed[id];
+		hC = (double)c.z - (double)zb;
+		if (c.zmax <= T(-9999.0) || c.z == T(-9999.0)) moves = false;
+		if (moves) {
+			const size_t iW = id - 1, iE = id + 1, iS = id - p.cols, iN = id + p.cols;
+			const State4<T> cW = src[iW], cE = src[iE], cS = src[iS], cN = src[iN];
+			const T zW = bed[iW], zE = bed[iE], zS = bed[iS], zN = bed[iN];
+			if (c.z - zb < p.vs && cN.z - zN < p.vs && cE.z - zE < p.vs && cS.z - zS < p.vs && cW.z - zW < p.vs) moves = false;
+			else {
+				const Side<T> sC = make_side<true>(c.z, c.qx, c.qy, zb, p.vs);
+				const Side<T> sN = make_side<true>(cN.z, cN.qx, cN.qy, zN, p.vs);
+				const Side<T> sE = make_side<true>(cE.z, cE.qx, cE.qy, zE, p.vs);
+				const Side<T> sS = make_side<true>(cS.z, cS.qx, cS.qy, zS, p.vs);
+				const Side<T> sW = make_side<true>(cW.z, cW.qx, cW.qy, zW, p.vs);
+				FN = (double)face_solve<AXIS_Y, true, true, false>(sC, sN, p.vs).forL.f0;
+				FS = (double)face_solve<AXIS_Y, true, false, true>(sS, sC, p.vs).forR.f0;
+				FE = (double)face_solve<AXIS_X, true, true, false>(sC, sE, p.vs).forL.f0;
+				FW = (double)face_solve<AXIS_X, true, false, true>(sW, sC, p.vs).forR.f0;
+			}
+		}
+	}
+	if (!__syncthreads_or(moves ? 1 : 0)) {                                    // (block-uniform) nothing moves here: copy, then decay
+		if (inside)
+			for (unsigned s = 0; s < species; ++s) M1[s * plane + id] = tracer_decay(M0[s * plane + id], rates.lambda[s], dt64);
+		return;
+	}
+
+	// this lane's halo cell, if it has one: waves 0 and 1 share the 2 x 64 + 2 x 4 cells of the tile's rim (corners are never read)
+	const int lane = ty * 64 + tx;
+	int hr = -1, hc = 0;                                                      // its place in the tile
+	if (lane < 64) { hr = 0; hc = lane + 1; }                                 // the row below the block
+	else if (lane < 128) { hr = TRACER_SET_ROWS + 1; hc = lane - 64 + 1; }    // the row above
+	else if (lane < 128 + TRACER_SET_ROWS) { hr = lane - 128 + 1; hc = 0; }   // the column to the west
+	else if (lane < 128 + 2 * TRACER_SET_ROWS) { hr = lane - 128 - TRACER_SET_ROWS + 1; hc = TRACER_SET_PITCH - 1; }   // to the east
+	const long hx = x0 + hc - 1, hy = y0 + hr - 1;
+	const bool halo = hr >= 0 && hx >= 0 && hy >= 0 && hx < p.cols && hy < p.rows;
+	const size_t hid = halo ? (size_t)hy * p.cols + hx : 0;
+	double hH = 0.0;
+	if (halo) hH = (double)src[hid].z - (double)bed[hid];
+
+	for (unsigned s = 0; s < species; ++s) {
+		const double* __restrict__ m0 = M0 + s * plane;
+		double (*t)[TRACER_SET_PITCH] = tile[s & 1];
+		const double m = inside ? m0[id] : 0.0;
+		t[ty + 1][tx + 1] = inside ? tracer_conc(m, hC) : 0.0;
+		if (hr >= 0) t[hr][hc] = halo ? tracer_conc(m0[hid], hH) : 0.0;
+		__syncthreads();
+		if (inside) {
+			double next = m;
+			if (moves)
+				next = tracer_update(m, t[ty + 1][tx + 1], t[ty + 2][tx + 1], t[ty][tx + 1], t[ty + 1][tx + 2], t[ty + 1][tx],
+				                     FN, FS, FE, FW, dt64, dx64);
+			M1[s * plane + id] = tracer_decay(next, rates.lambda[s], dt64);
+		}
+	}
 }
 
 } // namespace hp

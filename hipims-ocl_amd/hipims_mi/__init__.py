@@ -52,7 +52,8 @@ EXPORTS = [
     "hp_bed_shape_add", "hp_bed_shapes_clear", "hp_bed_apply", "hp_bed_info",
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info",
     "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_add_open", "hp_open_read", "hp_open_info", "hp_boundary_clear", "hp_boundaries_fused",
-    "hp_tracer_enable", "hp_tracer_disable", "hp_tracer_add_source", "hp_tracer_sources_clear", "hp_tracer_read", "hp_tracer_write", "hp_tracer_info", "hp_set_target_time", "hp_set_time",
+    "hp_tracer_enable", "hp_tracer_disable", "hp_tracer_add_source", "hp_tracer_sources_clear", "hp_tracer_read", "hp_tracer_write", "hp_tracer_info",
+    "hp_tracer_enable_set", "hp_tracer_add_source_to", "hp_tracer_read_species", "hp_tracer_write_species", "hp_tracer_set_info", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
     "hp_stream_halo", "hp_comm_load", "hp_comm_unique_id", "hp_strip_comm_init", "hp_strip_step_batch", "hp_strip_update_timestep",
@@ -245,6 +246,14 @@ class TracerDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("initial", C.c_void_p)]
 
 
+TRACER_MAX_SPECIES = 8
+
+
+# hp_tracer_set_desc_t
+class TracerSetDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("species", C.c_uint32), ("decay", C.c_void_p), ("initial", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -333,6 +342,12 @@ def load_library(path: str | None = None):
         lib.hp_tracer_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_tracer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_tracer_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "hp_tracer_enable_set"):
+        lib.hp_tracer_enable_set.argtypes = [C.c_void_p, C.POINTER(TracerSetDesc)]
+        lib.hp_tracer_add_source_to.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+        lib.hp_tracer_read_species.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_write_species.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_set_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -1112,43 +1127,77 @@ class Domain:
         desc = TracerDesc(C.sizeof(TracerDesc), 0, None if m0 is None else m0.ctypes.data)
         _check(self.lib, self.lib.hp_tracer_enable(self.h, C.byref(desc)), "hp_tracer_enable")
 
+    def tracer_enable_set(self, initial=None, decay=None, species=None):
+        """A tracer set (hp_tracer_enable_set): K species moved by one launch per iteration, the face fluxes formed once, each with a
+        first-order decay rate.  `initial`: [K, rows, cols] M0 or None for zeros; `decay`: K rates in 1/s or None for zeros; `species`:
+        K, needed only when neither says it.  frontend.TracerSet is the same arithmetic on the host, bit for bit."""
+        m0 = lam = None
+        if initial is not None:
+            m0 = np.ascontiguousarray(initial, dtype=np.float64)
+            if m0.ndim != 3 or m0.shape[1:] != (self.rows, self.cols):
+                raise ValueError(f"the initial tracers must be [species, {self.rows}, {self.cols}]")
+        if decay is not None:
+            lam = np.ascontiguousarray(decay, dtype=np.float64).reshape(-1)
+        said = ([] if species is None else [int(species)]) + ([] if m0 is None else [m0.shape[0]]) + ([] if lam is None else [lam.size])
+        if not said or len(set(said)) != 1:
+            raise ValueError("species, initial and decay must name one number of species")
+        desc = TracerSetDesc(C.sizeof(TracerSetDesc), said[0], None if lam is None or not lam.size else lam.ctypes.data,
+                             None if m0 is None or not m0.size else m0.ctypes.data)
+        _check(self.lib, self.lib.hp_tracer_enable_set(self.h, C.byref(desc)), "hp_tracer_enable_set")
+
     def tracer_disable(self):
         _check(self.lib, self.lib.hp_tracer_disable(self.h), "hp_tracer_disable")
 
-    def tracer_add_source(self, cells, series):
-        """One source (hp_tracer_add_source): `cells` flat ids (y * cols + x) or (x, y) pairs, `series` [(time, mass rate)]: every
-        listed cell receives the rate, interpolated by the bed shapes' rule."""
+    def tracer_add_source(self, cells, series, species=0):
+        """One source (hp_tracer_add_source; hp_tracer_add_source_to for a `species` other than 0): `cells` flat ids (y * cols + x) or
+        (x, y) pairs, `series` [(time, mass rate)]: every listed cell receives the rate, interpolated by the bed shapes' rule."""
         c = np.asarray(cells)
         if c.ndim == 2:
             c = c[:, 1].astype(np.uint64) * np.uint64(self.cols) + c[:, 0].astype(np.uint64)
         c = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1)
         s = np.ascontiguousarray(series, dtype=np.float64).reshape(-1, 2)
+        if species:
+            _check(self.lib, self.lib.hp_tracer_add_source_to(self.h, species, c.ctypes.data if c.size else None, c.size, s.ctypes.data if s.size else None, len(s)),
+                   "hp_tracer_add_source_to")
+            return
         _check(self.lib, self.lib.hp_tracer_add_source(self.h, c.ctypes.data if c.size else None, c.size, s.ctypes.data if s.size else None, len(s)),
                "hp_tracer_add_source")
 
     def tracer_sources_clear(self):
         _check(self.lib, self.lib.hp_tracer_sources_clear(self.h), "hp_tracer_sources_clear")
 
-    def tracer_read(self, row0=0, nrows=None):
-        """The current M in units * m, fp64 [nrows, cols] (default: every row of the local array); blocks."""
+    def tracer_read(self, row0=0, nrows=None, species=0):
+        """The current M in units * m, fp64 [nrows, cols] (default: every row of the local array), of `species` of a set; blocks."""
         nrows = self.rows - row0 if nrows is None else nrows
         out = np.zeros((max(0, nrows), self.cols), np.float64)
-        _check(self.lib, self.lib.hp_tracer_read(self.h, out.ctypes.data, row0, nrows), "hp_tracer_read")
+        if species:
+            _check(self.lib, self.lib.hp_tracer_read_species(self.h, species, out.ctypes.data, row0, nrows), "hp_tracer_read_species")
+        else:
+            _check(self.lib, self.lib.hp_tracer_read(self.h, out.ctypes.data, row0, nrows), "hp_tracer_read")
         self.sync()
         return out
 
-    def tracer_write(self, raster, row0=0):
-        """Replace rows row0 .. of the current M by `raster` [nrows, cols]."""
+    def tracer_write(self, raster, row0=0, species=0):
+        """Replace rows row0 .. of the current M (of `species` of a set) by `raster` [nrows, cols]."""
         m = np.ascontiguousarray(raster, dtype=np.float64)
         if m.ndim != 2 or m.shape[1] != self.cols:
             raise ValueError(f"the raster must be [nrows, {self.cols}]")
-        _check(self.lib, self.lib.hp_tracer_write(self.h, m.ctypes.data, row0, m.shape[0]), "hp_tracer_write")
+        if species:
+            _check(self.lib, self.lib.hp_tracer_write_species(self.h, species, m.ctypes.data, row0, m.shape[0]), "hp_tracer_write_species")
+        else:
+            _check(self.lib, self.lib.hp_tracer_write(self.h, m.ctypes.data, row0, m.shape[0]), "hp_tracer_write")
 
     def tracer_info(self):
         """dict(iterations, sources, source_cells): host counters (all 0 without a tracer)."""
         n, s, c = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
         _check(self.lib, self.lib.hp_tracer_info(self.h, C.byref(n), C.byref(s), C.byref(c)), "hp_tracer_info")
         return dict(iterations=n.value, sources=s.value, source_cells=c.value)
+
+    def tracer_set_info(self):
+        """dict(species, decay): K (0 without a tracer, 1 for a single one) and the K decay rates."""
+        k, lam = C.c_uint32(0), (C.c_double * TRACER_MAX_SPECIES)()
+        _check(self.lib, self.lib.hp_tracer_set_info(self.h, C.byref(k), lam), "hp_tracer_set_info")
+        return dict(species=k.value, decay=[float(v) for v in lam[:k.value]])
 
     def clear_boundaries(self):
         _check(self.lib, self.lib.hp_boundary_clear(self.h), "hp_boundary_clear")

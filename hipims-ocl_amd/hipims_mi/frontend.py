@@ -122,7 +122,9 @@ class Configuration:
     links: list = field(default_factory=list)      # dict(a (x, y), b (x, y), kind, one_way, level, size, coeff, limit): rows of the <links> elements' mapFiles
     soil_classes: list = field(default_factory=list)  # dict(ks, suction, deficit, capacity): rows of the <soilClasses> element's source; the id raster is the "soil" data source
     open_edges: list = field(default_factory=list)  # dict(edge, name, first, last): <domainEdge treatment="open"> elements; first / last None = the whole edge
-    tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2]): <tracerSource> elements; the initial M is the "tracer" data source
+    tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2], species name or None): <tracerSource> elements; the initial M is the "tracer" data source
+    tracer_species: list = field(default_factory=list)  # dict(name, decay, initial file or None): <tracerSpecies> elements, the species of a tracer set
+    target_species: list = field(default_factory=list)  # per entry of `targets`: the species="..." of a tracer / concentration target, or None
 
 
 def _params(elem):
@@ -169,6 +171,7 @@ def parse_configuration(xml_path):
                                   dt.get("target"), (dt.get("format") or "").upper()))
             continue
         cfg.targets.append(((dt.get("value") or "").lower(), dt.get("target")))
+        cfg.target_species.append(dt.get("species"))
         cfg.target_formats.append((dt.get("format") or "").upper())
     for sp in data.findall("sparseTarget"):   # the values at the selected cells only, as CSR in one .npz (no reference counterpart)
         cfg.sparse = dict(select=(sp.get("select") or "depth").lower(), above=float(sp.get("above") or 0.0),
@@ -195,7 +198,11 @@ def parse_configuration(xml_path):
     for e in data.findall("tracerSource"):
         cells = _read_csv(os.path.join(cfg.source_dir, e.get("mapFile"))).reshape(-1, 2)
         cfg.tracer_sources.append(dict(cells=[(int(r[0]), int(r[1])) for r in cells],
-                                       series=_read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2)))
+                                       series=_read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2), species=e.get("species")))
+    # a tracer set's species: <tracerSpecies name="sewage" decay="2.3e-5" source="m0.asc"/> (decay in 1/s, default 0; source: the initial M, a
+    # raster, default zeros); <tracerSource species="sewage" .../> feeds it, <dataTarget value="tracer|concentration" species="sewage" .../> writes it
+    for k, e in enumerate(data.findall("tracerSpecies")):
+        cfg.tracer_species.append(dict(name=e.get("name") or f"species{k}", decay=float(e.get("decay") or 0.0), initial=e.get("source")))
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -1195,8 +1202,12 @@ class Tracer:
     # (_pos: the flux is > 0, _neg: it is not), and whether a cell too shallow to have a concentration was among the five
     BRANCHES = ("ring", "dt_zero", "disabled", "dry5", "moved", "e_pos", "e_neg", "w_pos", "w_neg", "n_pos", "n_neg", "s_pos", "s_neg",
                 "no_concentration", "source")
+    MAX_SPECIES = 8
 
-    def __init__(self, rows, cols, dx, functions, initial=None, dry_threshold=1e-10):
+    def __init__(self, rows, cols, dx, functions, initial=None, dry_threshold=1e-10, decay=0.0):
+        self.decay = np.float64(decay)                                         # lambda of step 6 (a tracer set's species), 1 / s
+        if not np.isfinite(self.decay) or self.decay < 0:
+            raise ValueError("the decay rate must be finite and >= 0")
         self.rows, self.cols = int(rows), int(cols)
         self.fn = functions
         self.real = np.dtype(functions.real).type
@@ -1213,7 +1224,7 @@ class Tracer:
                 raise ValueError(f"cell {bad}: initial must be finite and >= 0")
         self.sources = []                               # (flat cells, series)
         self.iterations = 0
-        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES}
+        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES + ("decayed",)}
 
     def branch_totals(self):
         return {k: int(v.sum()) for k, v in self.branches.items()}
@@ -1257,6 +1268,23 @@ class Tracer:
         return np.asarray(M, dtype=np.float64) + add
 
     @staticmethod
+    def decay_step(M, lam, dt):
+        """tracer_decay on fp64 arrays: step 6."""
+        M, lam, dt = np.asarray(M, dtype=np.float64), np.float64(lam), np.float64(dt)
+        if not (lam > 0.0 and dt > 0.0):
+            return M
+        with np.errstate(over="ignore", invalid="ignore"):
+            growth = lam * dt
+            denom = np.float64(1.0) + growth
+            return M / denom
+
+    def _decay(self, dt64):
+        """Step 6 on the M the step left, at every cell of the array."""
+        if self.decay > 0.0 and dt64 > 0.0:
+            self.M = self.decay_step(self.M, self.decay, dt64)
+            self.branches["decayed"] += 1
+
+    @staticmethod
     def concentration(M, h):
         """tracer_conc on fp64 arrays."""
         M, h = np.asarray(M, dtype=np.float64), np.asarray(h, dtype=np.float64)
@@ -1297,9 +1325,10 @@ class Tracer:
         FW = f.hllc(self.DIR_W, L, R)[0]
         return FN, FS, FE, FW
 
-    def apply(self, state, bed, dt, t):
+    def apply(self, state, bed, dt, t, shared=None):
         """One iteration's tracer on `state` (the iteration's source buffer, not changed); `dt`, `t`: the timestep and time scalars of
-        that iteration.  Returns the number of cells moved."""
+        that iteration.  Returns the number of cells moved.  `shared`: a dict in which the species of a TracerSet keep the iteration's
+        face fluxes, which depend on the water only."""
         if state.shape != (self.rows, self.cols, 4) or bed.shape != (self.rows, self.cols) or state.dtype != bed.dtype:
             raise ValueError("state must be [rows, cols, 4] and bed [rows, cols], of one dtype")
         if state.dtype.type is not self.real:
@@ -1334,8 +1363,13 @@ class Tracer:
         self.branches["moved"] += moved
         ys, xs = np.nonzero(moved)
         if ys.size == 0:
+            self._decay(dt64)
             return 0
-        F = np.array([self.face_fluxes(state, bed, int(x), int(y)) for x, y in zip(xs, ys)], dtype=np.float64).reshape(-1, 4)
+        if shared is None or "F" not in shared:
+            F = np.array([self.face_fluxes(state, bed, int(x), int(y)) for x, y in zip(xs, ys)], dtype=np.float64).reshape(-1, 4)
+            if shared is not None:
+                shared["F"] = F
+        F = F if shared is None else shared["F"]
         h = z.astype(np.float64) - bed.astype(np.float64)                     # the RAW depth, widened
         c = self.concentration(M0, h)
         out, masks = self.update(M0[ys, xs], c[ys, xs], c[ys + 1, xs], c[ys - 1, xs], c[ys, xs + 1], c[ys, xs - 1],
@@ -1347,7 +1381,60 @@ class Tracer:
         M1 = M0.copy()
         M1[ys, xs] = out
         self.M = M1
+        self._decay(dt64)
         return int(ys.size)
+
+
+class TracerSet:
+    """A tracer set on the host (hp_tracer_enable_set restated): K Tracers over one state, each with its own M, sources and decay
+    rate.  The device forms the face fluxes once for all of them; here every species is a Tracer of its own, which is the contract."""
+
+    def __init__(self, rows, cols, dx, functions, initial=None, decay=None, species=None, dry_threshold=1e-10):
+        said = (([] if species is None else [int(species)]) + ([] if initial is None else [len(initial)]) + ([] if decay is None else [len(decay)]))
+        if not said or len(set(said)) != 1 or not 1 <= said[0] <= Tracer.MAX_SPECIES:
+            raise ValueError("species, initial and decay must name one number of species, 1..8")
+        self.tracers = []
+        for s in range(said[0]):
+            try:
+                self.tracers.append(Tracer(rows, cols, dx, functions, initial=None if initial is None else initial[s], dry_threshold=dry_threshold,
+                                           decay=0.0 if decay is None else decay[s]))
+            except ValueError as e:
+                raise ValueError(f"species {s}: {e}") from None
+
+    def __len__(self):
+        return len(self.tracers)
+
+    def __getitem__(self, s):
+        return self.tracers[s]
+
+    @property
+    def M(self):
+        return np.stack([t.M for t in self.tracers])
+
+    @property
+    def iterations(self):
+        return self.tracers[0].iterations
+
+    def add_source(self, species, cells, series):
+        if not 0 <= species < len(self.tracers):
+            raise ValueError(f"species {species} of a tracer of {len(self.tracers)}")
+        listed = sum(c.size for t in self.tracers for c, _ in t.sources)
+        if sum(len(t.sources) for t in self.tracers) >= Tracer.MAX_SOURCES:
+            raise ValueError("more than 64 sources")
+        if listed + np.asarray(cells).shape[0] > Tracer.MAX_CELLS:
+            raise ValueError("more than 1048576 cells over all sources")
+        self.tracers[species].add_source(cells, series)
+
+    def apply(self, state, bed, dt, t):
+        shared = {}                                                           # the face fluxes: formed once, as on the device
+        return [tr.apply(state, bed, dt, t, shared=shared) for tr in self.tracers][0]
+
+    def branch_totals(self):
+        totals = {}
+        for tr in self.tracers:
+            for k, v in tr.branch_totals().items():
+                totals[k] = totals.get(k, 0) + v
+        return totals
 
 
 def tracer_concentration(M, state, bed):

@@ -182,7 +182,7 @@ class Model:
     def __init__(self, xml_path, make_sim=None, output_format=".npy", log=None, progress_interval=0.85,
                  clock=time.perf_counter, device_outputs=None, peaks=None, peak_arrival_depth=0.01, gauges=None, sections=None,
                  probe_capacity=4096, zones=None, zone_flood_depth=0.1, zone_capacity=4096, overviews=None, sparse=None, bed_shapes=None,
-                 links=None, infiltration=None, tracer=None, open_edges=None):
+                 links=None, infiltration=None, tracer=None, open_edges=None, tracers=None):
         self.cfg = cfg = frontend.parse_configuration(xml_path)
         self.state0, self.bed, self.manning, self.res = frontend.build_domain(cfg)
         self.rows, self.cols = self.bed.shape
@@ -256,14 +256,61 @@ class Model:
         # series=)]) with initial an array [rows, cols] (row 0 = south), a raster file or None.  Enabled behind everything that may refuse
         # it.  It moves inside every iteration, so only an engine that has it on the device will do.  A <dataTarget value="tracer" .../>
         # writes M at every output time, a <dataTarget value="concentration" .../> M / h (frontend.tracer_concentration).
+        # A tracer SET: the <tracerSpecies name= decay= source=/> elements with their <tracerSource species=.../>, or `tracers`: [dict(name=,
+        # initial=, decay=, sources=[dict(cells=, series=)])]: one run of the water carries them all (hp_tracer_enable_set).  Targets name
+        # their species (<dataTarget value="tracer|concentration" species=.../>) and their files carry its name.  Either form, not both.
+        species = [dict(t) for t in tracers] if tracers is not None else None
+        if species is None and cfg.tracer_species:
+            species = [dict(name=t["name"], decay=t["decay"], initial=os.path.join(cfg.source_dir, t["initial"]) if t["initial"] else None,
+                            sources=[s for s in cfg.tracer_sources if s.get("species") == t["name"]]) for t in cfg.tracer_species]
         spec = dict(tracer) if tracer is not None else None
         source = next((src for src in cfg.sources if "tracer" in src[1]), None)
-        if spec is None and (source is not None or cfg.tracer_sources):
+        unnamed = [s for s in cfg.tracer_sources if s.get("species") is None]
+        if species is not None and (spec is not None or (tracers is None and (source is not None or unnamed))):
+            raise ValueError("a single tracer (tracer=, a tracer data source, a <tracerSource> without species) and a tracer set "
+                             "(tracers=, <tracerSpecies>) are given: a domain carries one or the other")
+        if species is None and any(s.get("species") is not None for s in cfg.tracer_sources):
+            raise ValueError("a <tracerSource species=...> needs its <tracerSpecies> element")
+        self.tracer_set = None
+        if species is not None:
+            names = [t.get("name") or f"species{k}" for k, t in enumerate(species)]
+            if len(set(names)) != len(names):
+                raise ValueError("two tracer species of one name")
+            known = set(names)
+            for s in cfg.tracer_sources:
+                if tracers is None and s.get("species") not in known:
+                    raise ValueError(f"a <tracerSource> names the species {s.get('species')!r}, which no <tracerSpecies> declares")
+            planes = np.zeros((len(species), self.rows, self.cols))
+            for k, t in enumerate(species):
+                m0 = t.get("initial")
+                if m0 is not None:
+                    m0 = frontend.read_raster(m0)[0] if isinstance(m0, (str, os.PathLike)) else np.asarray(m0, dtype=np.float64)
+                    if m0.shape != (self.rows, self.cols):
+                        raise ValueError(f"the raster of species {names[k]!r} is {m0.shape[1]} x {m0.shape[0]} cells, the domain {self.cols} x {self.rows}")
+                    planes[k] = m0
+            if not hasattr(sim, "tracer_enable_set"):
+                raise NotImplementedError("a tracer set moves inside every iteration: it needs an engine with tracer_enable_set (the HIP engine)")
+            self.tracer_set = dict(names=names, decay=[float(t.get("decay") or 0.0) for t in species], initial=planes,
+                                   sources=[[dict(cells=list(s["cells"]), series=np.asarray(s["series"], dtype=np.float64).reshape(-1, 2))
+                                             for s in (t.get("sources") or [])] for t in species])
+            sim.tracer_enable_set(initial=planes, decay=self.tracer_set["decay"])
+            for k, sources in enumerate(self.tracer_set["sources"]):
+                for s in sources:
+                    sim.tracer_add_source(s["cells"], s["series"], species=k)
+        target_species = list(getattr(cfg, "target_species", None) or []) + [None] * len(cfg.targets)
+        for (what, _), name in zip(cfg.targets, target_species):
+            if what in ("tracer", "concentration") and self.tracer_set is not None and name not in self.tracer_set["names"]:
+                raise ValueError(f"a {what} data target of a tracer set must name one of its species ({name!r})")
+            if what in ("tracer", "concentration") and self.tracer_set is None and name is not None:
+                raise ValueError(f"a {what} data target names the species {name!r}, and the model has no tracer set")
+        if self.tracer_set is None and spec is None and (source is not None or cfg.tracer_sources):
             if source is not None and source[0] != "raster":
                 raise ValueError("the tracer data source must be a raster")
             spec = dict(initial=os.path.join(cfg.source_dir, source[2]) if source is not None else None, sources=cfg.tracer_sources)
         self.tracer = None
-        if spec is not None:
+        if self.tracer_set is not None:
+            pass
+        elif spec is not None:
             m0 = spec.get("initial")
             if m0 is not None:
                 m0 = frontend.read_raster(m0)[0] if isinstance(m0, (str, os.PathLike)) else np.asarray(m0, dtype=np.float64)
@@ -559,12 +606,19 @@ class Model:
             elif is_soil[k]:
                 arr = self.sim.infiltration_read()
             elif is_tracer[k]:
-                arr = self.sim.tracer_read()
+                species = (list(getattr(self.cfg, "target_species", None) or []) + [None] * (k + 1))[k] if self.tracer_set is not None else None
+                arr = self.sim.tracer_read() if species is None else self.sim.tracer_read(species=self.tracer_set["names"].index(species))
                 if what == "concentration":
                     arr = frontend.tracer_concentration(arr, self.sim.download(), self.sim.download_bed() if hasattr(self.sim, "download_bed") else self.bed)
             else:
                 arr = derived[what] if self.device_outputs else frontend.derive_output(what, final, self.bed, self.res)
-            out[what] = arr
+            out[what if not is_tracer[k] or species is None else (what, species)] = arr
+            if is_tracer[k] and species is not None and pattern:           # the file carries the species' name: at %s, else in front of %t, else last
+                stem, tail = os.path.splitext(pattern)
+                if "%s" in pattern:
+                    pattern = pattern.replace("%s", species)
+                elif species not in stem:
+                    pattern = (stem.replace("%t", species + "_%t", 1) if "%t" in stem else stem + "_" + species) + tail
             if pattern and self.cfg.target_dir and self.output_format:
                 ext = self.output_format
                 if ext == "xml":             # what the model file asks for: format="HFA" -> Imagine .img, anything else ESRI ASCII

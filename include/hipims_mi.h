@@ -815,6 +815,50 @@ int hp_tracer_write(hp_domain_t* d, const double* raster, int64_t row0, int64_t 
  * hp_state_restore), its sources and their cells (all 0 without a tracer); any pointer may be NULL. */
 int hp_tracer_info(hp_domain_t* d, uint64_t* iterations, uint32_t* sources, uint64_t* source_cells);
 
+/* ---- a tracer SET: K species carried in one pass, each with a first-order decay.  Separating river, rain and sewer water, or a
+ *      spill from a background load, takes one run of the water, not K: the face mass fluxes depend on the water only, so one
+ *      kernel launch per iteration (csrc/hp_tracer.hpp: tracer_step_set) forms the copy-case verdict and FN, FS, FE, FW of a cell
+ *      once and moves every species by them.  A domain has at most ONE tracer, single (hp_tracer_enable) or set; a second enable
+ *      of either form is HP_ERR_STATE.  Everything the tracer block above says holds per species: the state (two allocations of
+ *      K * cols * rows doubles, the old and the new planes, species after species, with one phase for the whole set), the place
+ *      in the iteration, steps 0 to 5 word for word -- the STRICT face solve whatever the math mode, the copy cases --, what it
+ *      does to the water's launches, and what is refused: hp_tracer_enable_set refuses exactly what hp_tracer_enable refuses, for
+ *      the same reasons, and hp_boundary_add_links / hp_boundary_add_infiltration refuse a domain with a set likewise.
+ *        6. Decay, after step 5 and in fp64, correctly rounded multiply, add and divide only, never fused, at EVERY cell of the
+ *      array, copy cases and ring included: M'' = (lambda_s > 0 && dt > 0) ? M' / (1.0 + lambda_s * dt) : M'.  Implicit Euler: it
+ *      never overshoots zero and is stable for any dt; residue on dry ground decays too.  With lambda_s == 0 nothing is divided.
+ *      THE BITS.  Species s of a set equals, in every bit of M after every iteration, a single tracer (hp_tracer_enable) on the
+ *      same water with that species' initial raster and sources if lambda_s == 0, and frontend.Tracer(decay=lambda_s) -- K of
+ *      them are frontend.TracerSet -- for any lambda_s.  State, scalars, launch counts and pair statistics of the run are those of
+ *      the single-tracer run.  hp_tracer_enable_set always runs tracer_step_set, K == 1 included; hp_tracer_enable keeps
+ *      tracer_step.
+ *      SOURCES feed one species each; a cell may be listed once PER SPECIES over that species' sources; the limits on sources
+ *      (64) and listed cells (1 048 576) hold over the whole set.
+ *      THE SINGLE-TRACER CALLS ON A SET: hp_tracer_add_source, hp_tracer_read and hp_tracer_write act on species 0;
+ *      hp_tracer_disable frees all species; hp_tracer_info counts sources and cells over all species; hp_tracer_sources_clear
+ *      clears all sources.  The per-species calls on a single tracer see a set of one species.
+ *      hp_state_save / hp_state_restore carry all K current planes, the phase and the iteration counter by the tracer's rule;
+ *      enabling, disabling or changing K since the snapshot is the stale case: M is left as it is, one HP_LOG_WARNING. ---- */
+#define HP_TRACER_MAX_SPECIES 8
+typedef struct {
+	uint32_t struct_size;
+	uint32_t species;                  /* K, 1..8 */
+	const double* decay;               /* K rates lambda in 1/s, finite and >= 0, or NULL for zeros */
+	const double* initial;             /* K planes of cols*rows M0 (finite, >= 0), species after species, or NULL for zeros */
+} hp_tracer_set_desc_t;
+/* Argument errors -- a NULL desc, a bad struct_size, species outside 1..8, a negative or non-finite decay rate (the message names
+ * the species) or initial value (species and cell) -- are HP_ERR_INVALID before any device call; HP_ERR_STATE, HP_ERR_HIP and
+ * HP_ERR_UNSUPPORTED as hp_tracer_enable.  The arrays are free on return. */
+int hp_tracer_enable_set(hp_domain_t* d, const hp_tracer_set_desc_t* desc);
+/* hp_tracer_add_source for species `species`; a species >= K is HP_ERR_INVALID before any device call. */
+int hp_tracer_add_source_to(hp_domain_t* d, uint32_t species, const uint64_t* cells, uint64_t count, const double* series, uint32_t entries);
+/* hp_tracer_read / hp_tracer_write on the current plane of species `species`; a species >= K is HP_ERR_INVALID. */
+int hp_tracer_read_species(hp_domain_t* d, uint32_t species, double* raster, int64_t row0, int64_t nrows);
+int hp_tracer_write_species(hp_domain_t* d, uint32_t species, const double* raster, int64_t row0, int64_t nrows);
+/* Host values, does not block: K (0 without a tracer, 1 for a single one) and the K decay rates into decay[0 .. K - 1] (an array
+ * of HP_TRACER_MAX_SPECIES doubles); either pointer may be NULL. */
+int hp_tracer_set_info(hp_domain_t* d, uint32_t* species, double* decay);
+
 /* ---- time control ---- */
 int hp_set_target_time(hp_domain_t* d, double t);     /* CScheme::setTargetTime -> "Target time (sync)" buffer (:1166-1176) */
 int hp_set_time(hp_domain_t* d, double t);            /* rewrite the "Time" buffer: rollbackSimulation (:1480-1494) */
