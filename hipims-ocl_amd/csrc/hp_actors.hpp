@@ -19,6 +19,7 @@ static_assert(sizeof(hp_link_t) == 56 && sizeof(hp_link_record_t) == 32 && sizeo
 static_assert(sizeof(hp_soil_class_t) == 32 && sizeof(hp_infiltration_desc_t) == 32, "hp_soil_class_t / hp_infiltration_desc_t layout");
 static_assert(sizeof(hp_tracer_desc_t) == 16, "hp_tracer_desc_t layout");
 static_assert(sizeof(hp_tracer_set_desc_t) == 24, "hp_tracer_set_desc_t layout");
+static_assert(sizeof(hp_tracer_exchange_desc_t) == 48 && sizeof(TracerExchangeParams) == 32, "hp_tracer_exchange_desc_t layout");
 static_assert(sizeof(hp_open_segment_t) == 24 && sizeof(hp_open_record_t) == 32 && sizeof(OpenDev) == 24, "hp_open_*_t layout");
 
 // ---- the boundaries ----
@@ -296,9 +297,17 @@ template <typename T> int apply_tracer(hp_domain* d, const void* source)
 	if (R.sources && R.lists.count)
 		hipLaunchKernelGGL(tracer_sources<T>, dim3(stream_blocks((size_t)R.lists.count)), dim3(256), 0, d->stream, p, (const Scalars<T>*)d->scalars, R.lists, R.M[R.phase]);
 	const dim3 block(64, 4), grid((unsigned)((p.cols + 63) / 64), (unsigned)((p.rows + 3) / 4));
-	if (R.set)                                                                // every species by one launch, the face fluxes formed once
-		hipLaunchKernelGGL(tracer_step_set<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
-		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1], R.species, R.rates);
+	if (R.set && R.exchanging) {                                              // ... and step 7 behind the decay, in place on D
+		TracerBedArgs<T, true> X;
+		X.D = R.D;
+		X.manning = (const T*)d->manning;
+		X.exchanging = R.exchanging;
+		for (unsigned s = 0; s < HP_TRACER_MAX_SPECIES; ++s) X.of[s] = R.exchange[s];
+		hipLaunchKernelGGL((tracer_step_set<T, true>), grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
+		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1], R.species, R.rates, X);
+	} else if (R.set)                                                         // every species by one launch, the face fluxes formed once
+		hipLaunchKernelGGL((tracer_step_set<T, false>), grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
+		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1], R.species, R.rates, TracerBedArgs<T, false>{});
 	else
 		hipLaunchKernelGGL(tracer_step<T>, grid, block, 0, d->stream, p, (const Scalars<T>*)d->scalars, (const T*)d->bed, (const State4<T>*)source,
 		                   (const double*)R.M[R.phase], R.M[R.phase ^ 1]);
@@ -310,12 +319,13 @@ template <typename T> int apply_tracer(hp_domain* d, const void* source)
 void tracer_destroy(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.block); slot_free(R.saved);
-	R.M[0] = R.M[1] = nullptr; R.block = nullptr;
+	hipFree(R.M[0]); hipFree(R.M[1]); hipFree(R.D); hipFree(R.block); slot_free(R.saved);
+	R.M[0] = R.M[1] = nullptr; R.D = nullptr; R.block = nullptr;
 }
-// the copy: the current M of every cell and species, while the domain has a tracer (hp_tracer_disable frees it with the rest); `iterations` goes with it
-inline size_t tracer_units(const hp_domain* d) { return d->tracer.on ? (size_t)d->tracer.species * d->cells : 0; }
-inline size_t tracer_bytes(const hp_domain* d) { return tracer_units(d) * sizeof(double); }
+// the copy: the current M of every cell and species, then D likewise while the set has one, while the domain has a tracer (hp_tracer_disable
+// frees it with the rest); `iterations` goes with it
+inline size_t tracer_bytes(const hp_domain* d) { return d->tracer.on ? (size_t)d->tracer.species * d->cells * sizeof(double) : 0; }   // of M; D's are as many
+inline size_t tracer_units(const hp_domain* d) { return d->tracer.on ? (d->tracer.D ? 2 : 1) * (size_t)d->tracer.species * d->cells : 0; }
 int tracer_save_reserve(hp_domain* d)
 {
 	return slot_reserve(d->stream, d->tracer.saved, tracer_units(d), sizeof(double), "hp_state_save: cannot allocate the copy of the tracer: ");
@@ -323,15 +333,20 @@ int tracer_save_reserve(hp_domain* d)
 int tracer_save(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
+	if (R.D) {                                                                // D first, behind M's place: the mark is taken once both copies are queued
+		R.saved.mark.drop();
+		HIP_TRY(hipMemcpyAsync((char*)R.saved.copy + tracer_bytes(d), R.D, tracer_bytes(d), hipMemcpyDeviceToDevice, d->stream));
+	}
 	return slot_take(d->stream, R.saved, R.M[R.phase], tracer_bytes(d), R.epoch, R.iterations);
 }
-// stale: M is left as it is.  (The phase names a buffer, nothing more: the saved M goes into the buffer that is current now, and the counter comes back)
+// stale: M and D are left as they are.  (The phase names a buffer, nothing more: the saved M goes into the buffer that is current now, and the counter comes back)
 int tracer_restore(hp_domain* d)
 {
 	TracerStore& R = d->tracer;
-	const Verdict v = restore_verdict(R.saved, R.epoch, "hp_state_restore: the tracer was enabled or disabled, or its species changed, after the state was saved: the tracer is left as it is");
+	const Verdict v = restore_verdict(R.saved, R.epoch, "hp_state_restore: the tracer was enabled or disabled, its species changed or its exchange with the bed began after the state was saved: the tracer is left as it is");
 	if (v != Verdict::BRING_BACK || !R.on) return HP_OK;
-	const int rc = slot_bring_back(d->stream, R.saved, R.M[R.phase], tracer_bytes(d));
+	int rc = slot_bring_back(d->stream, R.saved, R.M[R.phase], tracer_bytes(d));
+	if (rc == HP_OK && R.D) rc = slot_bring_back(d->stream, SaveSlot{(char*)R.saved.copy + tracer_bytes(d), R.saved.mark}, R.D, tracer_bytes(d));
 	if (rc == HP_OK) R.iterations = R.saved.mark.count;
 	return rc;
 }
@@ -925,6 +940,7 @@ int hp_tracer_disable(hp_domain_t* d)
 	R.set = false;
 	R.species = 0;
 	R.rates = TracerRates{};
+	R.exchanging = 0;
 	R.lists = TracerLists{};
 	R.sources = 0;
 	R.host = TracerHost{};
@@ -992,8 +1008,10 @@ int hp_tracer_add_source_to(hp_domain_t* d, uint32_t species, const uint64_t* ce
 	return tracer_add_source_to(d, "hp_tracer_add_source_to", species, cells, count, series, entries);
 }
 
-// the checks hp_tracer_read / hp_tracer_write and their per-species forms share, in the header's order; *plane: species' current plane
-static int tracer_plane(hp_domain_t* d, const std::string& who, const uint32_t species, const void* raster, int64_t row0, int64_t nrows, double** plane)
+// the checks hp_tracer_read / hp_tracer_write, their per-species forms and the deposit's share, in the header's order; *plane: species'
+// current plane of M, or (`deposit`) its plane of D
+static int tracer_plane(hp_domain_t* d, const std::string& who, const uint32_t species, const void* raster, int64_t row0, int64_t nrows, double** plane,
+                        const bool deposit = false)
 {
 	if (!d) return fail(HP_ERR_INVALID, "null domain");
 	if (!raster) return fail(HP_ERR_INVALID, who + ": raster == NULL");
@@ -1005,21 +1023,22 @@ static int tracer_plane(hp_domain_t* d, const std::string& who, const uint32_t s
 	if ((rc = check_domain(d)) != HP_OK) return rc;
 	if (!R.on) return fail(HP_ERR_STATE, who + ": the domain has no tracer");
 	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
-	*plane = R.M[R.phase] + (size_t)species * d->cells + (size_t)row0 * (size_t)d->desc.cols;
+	if (deposit && !(R.D && R.exchanging)) return fail(HP_ERR_STATE, who + ": no species of the tracer exchanges with a deposit (hp_tracer_set_exchange)");
+	*plane = (deposit ? R.D : R.M[R.phase]) + (size_t)species * d->cells + (size_t)row0 * (size_t)d->desc.cols;
 	return HP_OK;
 }
-static int tracer_read_plane(hp_domain_t* d, const std::string& who, uint32_t species, double* raster, int64_t row0, int64_t nrows)
+static int tracer_read_plane(hp_domain_t* d, const std::string& who, uint32_t species, double* raster, int64_t row0, int64_t nrows, const bool deposit = false)
 {
 	double* plane = nullptr;
-	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane);
+	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane, deposit);
 	if (rc != HP_OK || nrows == 0) return rc;
 	HIP_TRY(hipMemcpyAsync(raster, plane, (size_t)nrows * (size_t)d->desc.cols * sizeof(double), hipMemcpyDeviceToHost, d->stream));
 	return HP_OK;
 }
-static int tracer_write_plane(hp_domain_t* d, const std::string& who, uint32_t species, const double* raster, int64_t row0, int64_t nrows)
+static int tracer_write_plane(hp_domain_t* d, const std::string& who, uint32_t species, const double* raster, int64_t row0, int64_t nrows, const bool deposit = false)
 {
 	double* plane = nullptr;
-	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane);
+	const int rc = tracer_plane(d, who, species, raster, row0, nrows, &plane, deposit);
 	if (rc != HP_OK || nrows == 0) return rc;
 	HIP_TRY(hipMemcpyAsync(plane, raster, (size_t)nrows * (size_t)d->desc.cols * sizeof(double), hipMemcpyHostToDevice, d->stream));
 	HIP_TRY(hipStreamSynchronize(d->stream));                                 // (the caller's raster is free on return)
@@ -1051,6 +1070,66 @@ int hp_tracer_set_info(hp_domain_t* d, uint32_t* species, double* decay)
 	const TracerStore& R = d->tracer;
 	if (species) *species = R.on ? R.species : 0;
 	for (unsigned s = 0; decay && R.on && s < R.species; ++s) decay[s] = R.rates.lambda[s];
+	return HP_OK;
+}
+
+// ---- a set's exchange with the bed (hp_tracer.hpp: tracer_exchange) ----
+int hp_tracer_set_exchange(hp_domain_t* d, const hp_tracer_exchange_desc_t* desc)
+{
+	// argument checks first: none of them touches the device (hp_tracer.hpp: validate_tracer_exchange)
+	const std::string who = "hp_tracer_set_exchange";
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	TracerStore& R = d->tracer;
+	std::string why;
+	if (!validate_tracer_exchange(desc, std::max(R.species, 1u), (uint64_t)d->cells, why)) return fail(HP_ERR_INVALID, why);
+	int rc = check_domain(d);
+	if (rc != HP_OK) return rc;
+	if (!R.on) return fail(HP_ERR_STATE, who + ": the domain has no tracer (hp_tracer_enable_set)");
+	if (d->in_step) return fail(HP_ERR_STATE, who + " between hp_step_begin and hp_step_end");
+	if (!R.set) return fail(HP_ERR_UNSUPPORTED, who + ": the domain's tracer is a single one (hp_tracer_enable), which keeps its own kernel: enable it as a set of one (hp_tracer_enable_set)");
+	const size_t plane = d->cells * sizeof(double);
+	const bool first = !R.D;
+	double* D = R.D;
+	// the planes first: if they cannot be had, the domain stays as it is, without exchange
+	if (first && (rc = alloc_or_fail((void**)&D, (size_t)R.species * plane, who + ": cannot allocate the deposit: ")) != HP_OK) return rc;
+	hipError_t e = first ? hipMemsetAsync(D, 0, (size_t)R.species * plane, d->stream) : hipSuccess;
+	if (e == hipSuccess && desc->deposit_initial) e = hipMemcpyAsync(D + (size_t)desc->species * d->cells, desc->deposit_initial, plane, hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess && (first || desc->deposit_initial)) e = hipStreamSynchronize(d->stream);   // (the caller's raster is free on return)
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(d->stream);
+		if (first) hipFree(D);
+		(void)hipGetLastError();
+		return fail(HP_ERR_HIP, who + ": writing the deposit: " + hipGetErrorString(e));
+	}
+	if (first) {                                                              // the store changes: an older checkpoint has no D
+		R.D = D;
+		R.exchanging = 0;
+		for (TracerExchangeParams& q : R.exchange) q = TracerExchangeParams{0.0, __builtin_inf(), __builtin_inf(), 0.0};
+		++R.epoch;
+	}
+	R.exchange[desc->species] = TracerExchangeParams{desc->settling, desc->tau_deposit, desc->tau_erode, desc->erodibility};
+	const unsigned bit = 1u << desc->species;
+	R.exchanging = desc->settling > 0.0 || desc->erodibility > 0.0 ? R.exchanging | bit : R.exchanging & ~bit;
+	return HP_OK;
+}
+int hp_tracer_deposit_read(hp_domain_t* d, uint32_t species, double* raster, int64_t row0, int64_t nrows)
+{
+	return tracer_read_plane(d, "hp_tracer_deposit_read", species, raster, row0, nrows, true);
+}
+int hp_tracer_deposit_write(hp_domain_t* d, uint32_t species, const double* raster, int64_t row0, int64_t nrows)
+{
+	return tracer_write_plane(d, "hp_tracer_deposit_write", species, raster, row0, nrows, true);
+}
+int hp_tracer_exchange_info(hp_domain_t* d, uint32_t* exchanging_species, hp_tracer_exchange_desc_t out[HP_TRACER_MAX_SPECIES])
+{
+	if (!d) return fail(HP_ERR_INVALID, "null domain");
+	const TracerStore& R = d->tracer;
+	const bool has = R.on && R.D;
+	if (exchanging_species) *exchanging_species = has ? (uint32_t)__builtin_popcount(R.exchanging) : 0;
+	for (unsigned s = 0; out && R.on && s < R.species; ++s) {
+		const TracerExchangeParams q = has ? R.exchange[s] : TracerExchangeParams{0.0, __builtin_inf(), __builtin_inf(), 0.0};
+		out[s] = hp_tracer_exchange_desc_t{(uint32_t)sizeof(hp_tracer_exchange_desc_t), s, q.settling, q.tau_deposit, q.tau_erode, q.erodibility, nullptr};
+	}
 	return HP_OK;
 }
 

@@ -241,6 +241,9 @@ struct TracerStore {
 	bool             set = false;                     // enabled by hp_tracer_enable_set: tracer_step_set moves it (K == 1 included)
 	unsigned         species = 0;                     // K: the planes of each buffer, species after species (a single tracer: 1; none: 0)
 	TracerRates      rates = {};                      // the species' decay rates (a single tracer: zeros)
+	double*          D = nullptr;                     // device: the species' deposits, K planes, from the first hp_tracer_set_exchange on (else NULL)
+	unsigned         exchanging = 0;                  // bit s: species s has settling > 0 or erodibility > 0 (tracer_step_set<T, true> while any is set)
+	TracerExchangeParams exchange[HP_TRACER_MAX_SPECIES] = {};   // as set (never set: 0, +inf, +inf, 0); meaningful while D exists
 	double*          M[2] = {nullptr, nullptr};       // device: M[phase] is the current M, the other one what the next step writes
 	int              phase = 0;                       // its own, independent of the state's ping-pong
 	uint64_t         iterations = 0;                  // steps since hp_tracer_enable (as restored)
@@ -248,8 +251,8 @@ struct TracerStore {
 	TracerLists      lists = {};
 	unsigned         sources = 0;
 	TracerHost       host;
-	uint64_t         epoch = 0;                       // counts enable / disable: a checkpoint's M belongs to one epoch
-	SaveSlot         saved;                           // hp_state_save's copy of the current M, in cells; comes back with `iterations`
+	uint64_t         epoch = 0;                       // counts enable / disable / the first hp_tracer_set_exchange: a checkpoint's M and D belong to one epoch
+	SaveSlot         saved;                           // hp_state_save's copy of the current M, then D if it exists, in cells; comes back with `iterations`
 };
 
 } // namespace

@@ -8,11 +8,16 @@
 // -ffp-contract=off -fno-fast-math (the Makefile), the probe likewise.  The face fluxes themselves are the STRICT face solve of
 // hp_math.hpp in the domain's precision, whatever the domain's math mode.  A tracer SET (hp_tracer_enable_set) carries up to 8 species,
 // planes of M one after the other, by one launch of tracer_step_set -- the face fluxes formed once per cell -- and lets each decay
-// (tracer_decay; frontend.TracerSet).  The contract is in include/hipims_mi.h; the host side
-// (hp_tracer_*, the launches in front of the flux kernel, M's part of a checkpoint) is in hp_actors.hpp.
+// (tracer_decay; frontend.TracerSet).  A species of a set may also exchange mass with a deposit D on the ground (hp_tracer_set_exchange:
+// tracer_exchange below, step 7, behind the decay in the same launch; its cube root is hp_crmath.h's).  The contract is in
+// include/hipims_mi.h; the host side (hp_tracer_*, the launches in front of the flux kernel, M's and D's part of a checkpoint) is in hp_actors.hpp.
 #pragma once
 #include "../../include/hipims_mi.h"
 #include "hp_bed.hpp"          // bed_fraction: the one interpolation rule of a {time, value} series
+#ifdef __HIPCC__
+#define HP_CR_FN __host__ __device__ __forceinline__
+#endif
+#include "hp_crmath.h"         // hp_cr_cbrt: the correctly rounded cube root of the bed shear stress, for host and device
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -63,6 +68,50 @@ HP_TRACER_FN double tracer_decay(const double M, const double lambda, const doub
 	const double growth = lambda * dt;
 	const double denom = 1.0 + growth;
 	return M / denom;
+}
+
+// step 7 (tracer sets): what one species exchanges with its deposit D -- Krone's deposition below tau_deposit, Partheniades' erosion
+// above tau_erode.  One definition in two halves, because the shear stress depends on the water only: a lane forms it once for all species
+struct TracerExchangeParams { double settling, tau_deposit, tau_erode, erodibility; };
+struct TracerPair { double M, D; };
+constexpr double TRACER_RHO_G = 9810.0;                   // rho g of the Manning bed shear stress, N/m3
+
+// the Manning bed shear stress rho g n^2 |u|^2 / h^(1/3) of a cell deeper than TRACER_DEPTH_MIN (the caller's test); NaN discharges give NaN
+HP_TRACER_FN double tracer_shear(const double h, const double qx, const double qy, const double n)
+{
+	const double vx = qx / h;
+	const double vy = qy / h;
+	const double sp2 = vx * vx + vy * vy;
+	const double nn = n * n;
+	return ((TRACER_RHO_G * nn) * sp2) / hp_cr_cbrt(h);
+}
+// ... and what a species does at that shear stress: implicit Euler into D, or a clipped explicit step out of it; a NaN tau does neither
+HP_TRACER_FN TracerPair tracer_exchange_at(const double M, const double D, const double tau, const double h, const double dt, const TracerExchangeParams q)
+{
+	TracerPair out = {M, D};
+	if (q.settling > 0.0 && M > 0.0 && tau < q.tau_deposit) {
+		const double pd = q.tau_deposit == __builtin_inf() ? 1.0 : 1.0 - tau / q.tau_deposit;
+		const double k = (q.settling * pd) * dt;
+		const double r = k / h;
+		const double M3 = M / (1.0 + r);
+		const double dep = M - M3;
+		out.D = D + dep;
+		out.M = M3;
+	} else if (q.erodibility > 0.0 && D > 0.0 && tau > q.tau_erode) {
+		const double ex = tau / q.tau_erode - 1.0;
+		double ero = (q.erodibility * ex) * dt;
+		if (ero > D) ero = D;
+		out.D = D - ero;
+		out.M = M + ero;
+	}
+	return out;
+}
+// step 7 of one cell that is no copy case: M the decayed M'', h the RAW depth, qx qy its discharge, n its Manning value, all widened
+HP_TRACER_FN TracerPair tracer_exchange(const double M, const double D, const double h, const double qx, const double qy, const double n,
+                                        const double dt, const TracerExchangeParams q)
+{
+	if (!(h > TRACER_DEPTH_MIN)) return TracerPair{M, D};
+	return tracer_exchange_at(M, D, tracer_shear(h, qx, qy, n), h, dt, q);
 }
 
 // the rate of a source at time t: the bed shapes' rule on {time, mass rate} pairs
@@ -122,6 +171,26 @@ inline bool validate_tracer_set_enable(const hp_tracer_set_desc_t* desc, const u
 				const double m = desc->initial[(uint64_t)s * cells + i];
 				if (!std::isfinite(m) || m < 0.0) { why = who + ": species " + std::to_string(s) + ", cell " + std::to_string(i) + ": initial must be finite and >= 0"; return false; }
 			}
+	return true;
+}
+
+// -------------------------------------------------------------------------------------------------
+// validate_tracer_exchange : every argument error of hp_tracer_set_exchange that needs no device, in the order the header lists them.
+//     `species_count`: K of the domain's set; `cells`: cols * rows of the local array.  Returns false with `why` set.
+// -------------------------------------------------------------------------------------------------
+inline bool validate_tracer_exchange(const hp_tracer_exchange_desc_t* desc, const uint32_t species_count, const uint64_t cells, std::string& why)
+{
+	const std::string who = "hp_tracer_set_exchange";
+	if (!desc) { why = who + ": desc == NULL"; return false; }
+	if (desc->struct_size != sizeof(hp_tracer_exchange_desc_t)) { why = "hp_tracer_exchange_desc_t size mismatch (ABI)"; return false; }
+	if (desc->species >= species_count) { why = who + ": species " + std::to_string(desc->species) + " of a tracer of " + std::to_string(species_count); return false; }
+	if (!std::isfinite(desc->settling) || desc->settling < 0.0) { why = who + ": settling must be finite and >= 0"; return false; }
+	if (!(desc->tau_deposit > 0.0)) { why = who + ": tau_deposit must be > 0 (+inf allowed)"; return false; }
+	if (std::isnan(desc->tau_erode) || desc->tau_erode < desc->tau_deposit) { why = who + ": tau_erode must be >= tau_deposit (+inf allowed)"; return false; }
+	if (!std::isfinite(desc->erodibility) || desc->erodibility < 0.0) { why = who + ": erodibility must be finite and >= 0"; return false; }
+	if (desc->deposit_initial)
+		for (uint64_t i = 0; i < cells; ++i)
+			if (!std::isfinite(desc->deposit_initial[i]) || desc->deposit_initial[i] < 0.0) { why = who + ": cell " + std::to_string(i) + ": deposit_initial must be finite and >= 0"; return false; }
 	return true;
 }
 
@@ -282,6 +351,17 @@ __global__ __launch_bounds__(256) void tracer_step(const Params<T> p, const Scal
 // The decay rates of a set's species, by value in the kernel's arguments
 struct TracerRates { double lambda[HP_TRACER_MAX_SPECIES]; };
 
+// What tracer_step_set<T, true> takes besides: the K planes of D, the Manning array the flux kernel reads (Params says whether it is
+// uniform) and the species' parameters by value; bit s of `exchanging`: species s has settling > 0 or erodibility > 0.  The <T, false>
+// kernel takes an empty one
+template <typename T, bool EXCHANGE> struct TracerBedArgs {};
+template <typename T> struct TracerBedArgs<T, true> {
+	double*              D;
+	const T*             manning;
+	unsigned             exchanging;
+	TracerExchangeParams of[HP_TRACER_MAX_SPECIES];
+};
+
 constexpr int TRACER_SET_ROWS = 4;                    // rows of a block of tracer_step_set: one wave each
 constexpr int TRACER_SET_PITCH = 66;                  // 64 columns and the two halo columns
 
@@ -296,11 +376,15 @@ constexpr int TRACER_SET_PITCH = 66;                  // 64 columns and the two 
 //     double-buffered: one barrier per species.  Lanes of the copy cases and lanes outside the array reach every barrier (a flag, no
 //     return); a block without a single moving cell -- still or dry ground, dt <= 0 -- skips the tile: block-uniform, by one
 //     __syncthreads_or.  Writes M1 at EVERY cell of every plane.
+//     EXCHANGE (a set with a species that exchanges with its deposit, hp_tracer_set_exchange): a moving lane deeper than
+//     TRACER_DEPTH_MIN forms its bed shear stress once, from the cell it has loaded anyway; behind the decay, for every exchanging
+//     species (a uniform branch: the flag is a kernel argument), it loads its own D, applies step 7 and stores D if it changed.  D is
+//     its lane's alone and updated in place.  The block without a moving cell exchanges nothing.  <T, false> is the kernel without it.
 // -------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool EXCHANGE>
 __global__ __launch_bounds__(256) void tracer_step_set(const Params<T> p, const Scalars<T>* __restrict__ sc, const T* __restrict__ bed,
                                                        const State4<T>* __restrict__ src, const double* __restrict__ M0, double* __restrict__ M1,
-                                                       const unsigned species, const TracerRates rates)
+                                                       const unsigned species, const TracerRates rates, const TracerBedArgs<T, EXCHANGE> X)
 {
 	__shared__ double tile[2][TRACER_SET_ROWS + 2][TRACER_SET_PITCH];
 	const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
@@ -316,6 +400,8 @@ __global__ __launch_bounds__(256) void tracer_step_set(const Params<T> p, const 
 	bool moves = inside && !(x <= 0 || y <= 0 || x >= p.cols - 1 || y >= p.rows - 1 || dt <= T(0));
 	double hC = 0.0;
 	double FN = 0.0, FS = 0.0, FE = 0.0, FW = 0.0;
+	[[maybe_unused]] double tau = 0.0;                                        // (EXCHANGE) the cell's bed shear stress ...
+	[[maybe_unused]] bool exchanges = false;                                  // ... if it moves and is deep enough to have one
 	if (inside && dt > T(0)) {
 		const State4<T> c = src[id];
 		const T zb = bed[id];
@@ -336,6 +422,11 @@ __global__ __launch_bounds__(256) void tracer_step_set(const Params<T> p, const 
 				FS = (double)face_solve<AXIS_Y, true, false, true>(sS, sC, p.vs).forR.f0;
 				FE = (double)face_solve<AXIS_X, true, true, false>(sC, sE, p.vs).forL.f0;
 				FW = (double)face_solve<AXIS_X, true, false, true>(sW, sC, p.vs).forR.f0;
+				if constexpr (EXCHANGE)
+					if (X.exchanging && hC > TRACER_DEPTH_MIN) {
+						exchanges = true;
+						tau = tracer_shear(hC, (double)c.qx, (double)c.qy, (double)(p.manning_uniform ? p.manning_value : X.manning[id]));
+					}
 			}
 		}
 	}
@@ -370,7 +461,16 @@ __global__ __launch_bounds__(256) void tracer_step_set(const Params<T> p, const 
 			if (moves)
 				next = tracer_update(m, t[ty + 1][tx + 1], t[ty + 2][tx + 1], t[ty][tx + 1], t[ty + 1][tx + 2], t[ty + 1][tx],
 				                     FN, FS, FE, FW, dt64, dx64);
-			M1[s * plane + id] = tracer_decay(next, rates.lambda[s], dt64);
+			next = tracer_decay(next, rates.lambda[s], dt64);
+			if constexpr (EXCHANGE)
+				if ((X.exchanging >> s & 1u) && exchanges) {
+					double* __restrict__ at = X.D + s * plane + id;
+					const double d0 = *at;
+					const TracerPair after = tracer_exchange_at(next, d0, tau, hC, dt64, X.of[s]);
+					if (after.D != d0) *at = after.D;
+					next = after.M;
+				}
+			M1[s * plane + id] = next;
 		}
 	}
 }

@@ -53,7 +53,8 @@ EXPORTS = [
     "hp_boundary_add_uniform", "hp_boundary_add_gridded", "hp_boundary_add_cell", "hp_boundary_add_links", "hp_links_read", "hp_links_info",
     "hp_boundary_add_infiltration", "hp_infiltration_read", "hp_infiltration_info", "hp_boundary_add_open", "hp_open_read", "hp_open_info", "hp_boundary_clear", "hp_boundaries_fused",
     "hp_tracer_enable", "hp_tracer_disable", "hp_tracer_add_source", "hp_tracer_sources_clear", "hp_tracer_read", "hp_tracer_write", "hp_tracer_info",
-    "hp_tracer_enable_set", "hp_tracer_add_source_to", "hp_tracer_read_species", "hp_tracer_write_species", "hp_tracer_set_info", "hp_set_target_time", "hp_set_time",
+    "hp_tracer_enable_set", "hp_tracer_add_source_to", "hp_tracer_read_species", "hp_tracer_write_species", "hp_tracer_set_info",
+    "hp_tracer_set_exchange", "hp_tracer_deposit_read", "hp_tracer_deposit_write", "hp_tracer_exchange_info", "hp_set_target_time", "hp_set_time",
     "hp_force_timestep", "hp_reset_counters", "hp_update_timestep", "hp_step_batch", "hp_read_scalars",
     "hp_sync", "hp_is_busy", "hp_step_begin", "hp_step_end", "hp_step_needs_reduction", "hp_device_ptr", "hp_stream", "hp_set_halo_overlap",
     "hp_stream_halo", "hp_comm_load", "hp_comm_unique_id", "hp_strip_comm_init", "hp_strip_step_batch", "hp_strip_update_timestep",
@@ -254,6 +255,12 @@ class TracerSetDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("species", C.c_uint32), ("decay", C.c_void_p), ("initial", C.c_void_p)]
 
 
+# hp_tracer_exchange_desc_t
+class TracerExchangeDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("species", C.c_uint32), ("settling", C.c_double), ("tau_deposit", C.c_double),
+                ("tau_erode", C.c_double), ("erodibility", C.c_double), ("deposit_initial", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -348,6 +355,11 @@ def load_library(path: str | None = None):
         lib.hp_tracer_read_species.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_tracer_write_species.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
         lib.hp_tracer_set_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    if hasattr(lib, "hp_tracer_set_exchange"):
+        lib.hp_tracer_set_exchange.argtypes = [C.c_void_p, C.POINTER(TracerExchangeDesc)]
+        lib.hp_tracer_deposit_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_deposit_write.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64]
+        lib.hp_tracer_exchange_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(TracerExchangeDesc)]
     lib.hp_state_save.argtypes = [C.c_void_p]
     lib.hp_state_restore.argtypes = [C.c_void_p]
     lib.hp_boundary_add_uniform.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
@@ -1198,6 +1210,43 @@ class Domain:
         k, lam = C.c_uint32(0), (C.c_double * TRACER_MAX_SPECIES)()
         _check(self.lib, self.lib.hp_tracer_set_info(self.h, C.byref(k), lam), "hp_tracer_set_info")
         return dict(species=k.value, decay=[float(v) for v in lam[:k.value]])
+
+    def tracer_set_exchange(self, species, settling=0.0, tau_deposit=float("inf"), tau_erode=float("inf"), erodibility=0.0, deposit=None):
+        """Let `species` of a tracer set exchange mass with its deposit D on the ground (hp_tracer_set_exchange): it settles at
+        `settling` m/s where the bed shear stress is below `tau_deposit` N/m2 (Krone) and is eroded at `erodibility` units/(m2 s)
+        where it exceeds `tau_erode` (Partheniades).  `deposit`: D0 [rows, cols], or None: zeros on the domain's first call, D as it
+        is on a later one.  frontend.Tracer(exchange=...) is the same arithmetic on the host, bit for bit."""
+        d0 = None
+        if deposit is not None:
+            d0 = np.ascontiguousarray(deposit, dtype=np.float64)
+            if d0.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial deposit must be [{self.rows}, {self.cols}]")
+        desc = TracerExchangeDesc(C.sizeof(TracerExchangeDesc), species, settling, tau_deposit, tau_erode, erodibility, None if d0 is None else d0.ctypes.data)
+        _check(self.lib, self.lib.hp_tracer_set_exchange(self.h, C.byref(desc)), "hp_tracer_set_exchange")
+
+    def tracer_deposit_read(self, species=0, row0=0, nrows=None):
+        """The deposit D of `species` in units * m, fp64 [nrows, cols] (default: every row of the local array); blocks."""
+        nrows = self.rows - row0 if nrows is None else nrows
+        out = np.zeros((max(0, nrows), self.cols), np.float64)
+        _check(self.lib, self.lib.hp_tracer_deposit_read(self.h, species, out.ctypes.data, row0, nrows), "hp_tracer_deposit_read")
+        self.sync()
+        return out
+
+    def tracer_deposit_write(self, raster, species=0, row0=0):
+        """Replace rows row0 .. of the deposit D of `species` by `raster` [nrows, cols]."""
+        m = np.ascontiguousarray(raster, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != self.cols:
+            raise ValueError(f"the raster must be [nrows, {self.cols}]")
+        _check(self.lib, self.lib.hp_tracer_deposit_write(self.h, species, m.ctypes.data, row0, m.shape[0]), "hp_tracer_deposit_write")
+
+    def tracer_exchange_info(self):
+        """dict(exchanging, species): how many species exchange with a deposit, and per species of the set what was set
+        (settling, tau_deposit, tau_erode, erodibility; never set: 0, inf, inf, 0)."""
+        n, out = C.c_uint32(0), (TracerExchangeDesc * TRACER_MAX_SPECIES)()
+        _check(self.lib, self.lib.hp_tracer_exchange_info(self.h, C.byref(n), out), "hp_tracer_exchange_info")
+        k = self.tracer_set_info()["species"]
+        return dict(exchanging=n.value, species=[dict(settling=q.settling, tau_deposit=q.tau_deposit, tau_erode=q.tau_erode, erodibility=q.erodibility)
+                                                  for q in out[:k]])
 
     def clear_boundaries(self):
         _check(self.lib, self.lib.hp_boundary_clear(self.h), "hp_boundary_clear")

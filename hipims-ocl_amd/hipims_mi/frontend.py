@@ -21,6 +21,7 @@ never parses the element (quirk Q9), so its own behaviour there is undefined.
 from __future__ import annotations
 
 import csv
+import math
 import os
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass, field
@@ -123,7 +124,7 @@ class Configuration:
     soil_classes: list = field(default_factory=list)  # dict(ks, suction, deficit, capacity): rows of the <soilClasses> element's source; the id raster is the "soil" data source
     open_edges: list = field(default_factory=list)  # dict(edge, name, first, last): <domainEdge treatment="open"> elements; first / last None = the whole edge
     tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2], species name or None): <tracerSource> elements; the initial M is the "tracer" data source
-    tracer_species: list = field(default_factory=list)  # dict(name, decay, initial file or None): <tracerSpecies> elements, the species of a tracer set
+    tracer_species: list = field(default_factory=list)  # dict(name, decay, initial file or None[, exchange dict, deposit file or None]): <tracerSpecies> elements, the species of a tracer set
     target_species: list = field(default_factory=list)  # per entry of `targets`: the species="..." of a tracer / concentration target, or None
 
 
@@ -201,8 +202,14 @@ def parse_configuration(xml_path):
                                        series=_read_csv(os.path.join(cfg.source_dir, e.get("source"))).reshape(-1, 2), species=e.get("species")))
     # a tracer set's species: <tracerSpecies name="sewage" decay="2.3e-5" source="m0.asc"/> (decay in 1/s, default 0; source: the initial M, a
     # raster, default zeros); <tracerSource species="sewage" .../> feeds it, <dataTarget value="tracer|concentration" species="sewage" .../> writes it
+    # ... and what it exchanges with the bed: settling= (m/s) tauDeposit= tauErode= (N/m2) erodibility= (units/(m2 s)) deposit= (the initial
+    # deposit D, a raster); any of them makes the species one that exchanges; <dataTarget value="deposit" species="silt" .../> writes D
     for k, e in enumerate(data.findall("tracerSpecies")):
+        said = {name: float(e.get(attr)) for name, attr in (("settling", "settling"), ("tau_deposit", "tauDeposit"), ("tau_erode", "tauErode"),
+                                                            ("erodibility", "erodibility")) if e.get(attr) is not None}
         cfg.tracer_species.append(dict(name=e.get("name") or f"species{k}", decay=float(e.get("decay") or 0.0), initial=e.get("source")))
+        if said or e.get("deposit"):                                           # (a species without them keeps the three keys it had)
+            cfg.tracer_species[-1].update(exchange=said, deposit=e.get("deposit"))
     sch = dom.find("scheme")
     name = (sch.get("name") or "godunov").lower()
     # CScheme::createFromConfig (CScheme.cpp:140-176): "muscl-hancock" | "godunov" | "inertial"
@@ -1187,6 +1194,47 @@ class Infiltration:
         return int(move.sum())
 
 
+def _icbrt(n):
+    """floor(n ** (1/3)) of a non-negative Python integer: Newton's iteration from above."""
+    if n < 2:
+        return n
+    r = 1 << -(-n.bit_length() // 3)                                           # 2^ceil(bits / 3) >= the root
+    while True:
+        nxt = (2 * r + n // (r * r)) // 3
+        if nxt >= r:
+            return r
+        r = nxt
+
+
+def cbrt_exact(x):
+    """The correctly rounded (to nearest) cube root of a positive, finite double, by integer arithmetic alone: the significand is scaled
+    to an integer of more than 3 * 55 bits whose exponent is a multiple of three, its integer cube root taken, and the root rounded to
+    53 bits.  A cube root of a double is never halfway between two doubles unless it is exact, so the remainder decides.  Independent of
+    csrc/hp_crmath.h: what tests hold hp_cr_cbrt against, and the cube root of Tracer's bed shear stress."""
+    x = float(x)
+    if not (x > 0.0) or x == float("inf"):
+        raise ValueError("cbrt_exact takes a positive, finite double")
+    m, e = math.frexp(x)
+    m, e = int(m * (1 << 53)), e - 53                                          # x = m * 2^e exactly, 2^52 <= m < 2^53
+    k = 120 + (e - 120) % 3                                                    # m << k has 173 bits or more; e - k is a multiple of 3
+    n = m << k
+    r = _icbrt(n)
+    exact = r * r * r == n
+    drop = r.bit_length() - 53                                                 # >= 4: the root has 57 bits or more
+    q, rem, half = r >> drop, r & ((1 << drop) - 1), 1 << (drop - 1)
+    if rem > half or (rem == half and (not exact or q & 1)):               # (not exact: the true root lies above r)
+        q += 1
+    return math.ldexp(q, drop + (e - k) // 3)
+
+
+def cbrt_exact_array(x):
+    """cbrt_exact over an array of positive, finite doubles (each distinct value once)."""
+    x = np.asarray(x, dtype=np.float64)
+    values, where = np.unique(x.reshape(-1), return_inverse=True)
+    roots = np.array([cbrt_exact(v) for v in values], dtype=np.float64)
+    return roots[where].reshape(x.shape)
+
+
 class Tracer:
     """The passive tracer on the host (hp_tracer_enable restated in NumPy, in exactly the operation order of csrc/hp_tracer.hpp):
     the solute mass per unit area M, fp64 whatever the state's precision.  `apply` is one iteration's tracer on the iteration's
@@ -1203,11 +1251,31 @@ class Tracer:
     BRANCHES = ("ring", "dt_zero", "disabled", "dry5", "moved", "e_pos", "e_neg", "w_pos", "w_neg", "n_pos", "n_neg", "s_pos", "s_neg",
                 "no_concentration", "source")
     MAX_SPECIES = 8
+    RHO_G = 9810.0                                      # rho g of the Manning bed shear stress, N/m3
 
-    def __init__(self, rows, cols, dx, functions, initial=None, dry_threshold=1e-10, decay=0.0):
+    @staticmethod
+    def exchange_params(exchange):
+        """The four parameters of step 7 (hp_tracer_exchange_desc_t) as fp64, checked in the header's order."""
+        unknown = set(exchange) - {"settling", "tau_deposit", "tau_erode", "erodibility"}
+        if unknown:
+            raise ValueError(f"exchange has no parameter {sorted(unknown)[0]!r}")
+        ws, tcd = np.float64(exchange.get("settling", 0.0)), np.float64(exchange.get("tau_deposit", np.inf))
+        tce, E = np.float64(exchange.get("tau_erode", np.inf)), np.float64(exchange.get("erodibility", 0.0))
+        if not np.isfinite(ws) or ws < 0:
+            raise ValueError("settling must be finite and >= 0")
+        if not tcd > 0:
+            raise ValueError("tau_deposit must be > 0 (+inf allowed)")
+        if np.isnan(tce) or tce < tcd:
+            raise ValueError("tau_erode must be >= tau_deposit (+inf allowed)")
+        if not np.isfinite(E) or E < 0:
+            raise ValueError("erodibility must be finite and >= 0")
+        return dict(settling=ws, tau_deposit=tcd, tau_erode=tce, erodibility=E)
+
+    def __init__(self, rows, cols, dx, functions, initial=None, dry_threshold=1e-10, decay=0.0, exchange=None, deposit=None, manning=0.0):
         self.decay = np.float64(decay)                                         # lambda of step 6 (a tracer set's species), 1 / s
         if not np.isfinite(self.decay) or self.decay < 0:
             raise ValueError("the decay rate must be finite and >= 0")
+        self.exchange = None if exchange is None else self.exchange_params(exchange)   # step 7 (hp_tracer_set_exchange), or None
         self.rows, self.cols = int(rows), int(cols)
         self.fn = functions
         self.real = np.dtype(functions.real).type
@@ -1222,9 +1290,20 @@ class Tracer:
             if not np.isfinite(self.M).all() or (self.M < 0).any():
                 bad = int(np.flatnonzero(~(np.isfinite(self.M) & (self.M >= 0)).reshape(-1))[0])
                 raise ValueError(f"cell {bad}: initial must be finite and >= 0")
+        # the deposit D of step 7 and the Manning values the flux kernel uses (a scalar or [rows, cols]), in the state's precision
+        if deposit is None:
+            self.D = np.zeros((self.rows, self.cols))
+        else:
+            self.D = np.array(deposit, dtype=np.float64)
+            if self.D.shape != (self.rows, self.cols):
+                raise ValueError(f"the initial deposit must be [{self.rows}, {self.cols}]")
+            if not (np.isfinite(self.D) & (self.D >= 0)).all():
+                bad = int(np.flatnonzero(~(np.isfinite(self.D) & (self.D >= 0)).reshape(-1))[0])
+                raise ValueError(f"cell {bad}: deposit_initial must be finite and >= 0")
+        self.manning = np.broadcast_to(np.asarray(manning, dtype=self.real), (self.rows, self.cols)).astype(np.float64)
         self.sources = []                               # (flat cells, series)
         self.iterations = 0
-        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES + ("decayed",)}
+        self.branches = {k: np.zeros((self.rows, self.cols), np.int64) for k in self.BRANCHES + ("decayed", "deposited", "eroded")}
 
     def branch_totals(self):
         return {k: int(v.sum()) for k, v in self.branches.items()}
@@ -1283,6 +1362,64 @@ class Tracer:
         if self.decay > 0.0 and dt64 > 0.0:
             self.M = self.decay_step(self.M, self.decay, dt64)
             self.branches["decayed"] += 1
+
+    @staticmethod
+    def shear(h, qx, qy, n):
+        """tracer_shear on fp64 arrays: the Manning bed shear stress of cells deeper than DEPTH_MIN (NaN elsewhere)."""
+        h, qx, qy, n = (np.asarray(v, dtype=np.float64) for v in (h, qx, qy, n))
+        deep = h > Tracer.DEPTH_MIN
+        hh = np.where(deep, h, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+            vx = qx / hh
+            vy = qy / hh
+            sp2 = vx * vx + vy * vy
+            nn = n * n
+            tau = ((np.float64(Tracer.RHO_G) * nn) * sp2) / cbrt_exact_array(hh)
+        return np.where(deep, tau, np.nan)
+
+    @staticmethod
+    def exchange_step(M, D, h, qx, qy, n, dt, q, tau=None):
+        """tracer_exchange on fp64 arrays: step 7 -> (M, D, deposited mask, eroded mask).  `q`: exchange_params' dict; `tau`: shear(h, qx,
+        qy, n) if the caller has it already."""
+        M, D, h = (np.asarray(v, dtype=np.float64) for v in (M, D, h))
+        dt = np.float64(dt)
+        ws, tcd, tce, E = q["settling"], q["tau_deposit"], q["tau_erode"], q["erodibility"]
+        deep = h > Tracer.DEPTH_MIN
+        tau = Tracer.shear(h, qx, qy, n) if tau is None else np.asarray(tau, dtype=np.float64)
+        hh = np.where(deep, h, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+            dep_at = deep & bool(ws > 0.0) & (M > 0.0) & (tau < tcd)
+            pd = np.float64(1.0) if np.isinf(tcd) else np.float64(1.0) - tau / tcd
+            k = (ws * pd) * dt
+            r = k / hh
+            M3 = M / (np.float64(1.0) + r)
+            dep = M - M3
+            ero_at = deep & ~dep_at & bool(E > 0.0) & (D > 0.0) & (tau > tce)
+            ex = tau / tce - np.float64(1.0)
+            ero = (E * ex) * dt
+            ero = np.where(ero > D, D, ero)
+            M_out = np.where(dep_at, M3, np.where(ero_at, M + ero, M))
+            D_out = np.where(dep_at, D + dep, np.where(ero_at, D - ero, D))
+        return M_out, D_out, dep_at, ero_at
+
+    def _exchange(self, state, bed, ys, xs, dt64, shared):
+        """Step 7 behind the decay, at the moved cells (ys, xs)."""
+        q = self.exchange
+        if q is None or not (q["settling"] > 0.0 or q["erodibility"] > 0.0):
+            return
+        if shared is None or "tau" not in shared:                             # the water's part: formed once for all species, as on the device
+            h = state[ys, xs, 0].astype(np.float64) - bed[ys, xs].astype(np.float64)
+            tau = self.shear(h, state[ys, xs, 2], state[ys, xs, 3], self.manning[ys, xs])
+            if shared is not None:
+                shared["h"], shared["tau"] = h, tau
+        else:
+            h, tau = shared["h"], shared["tau"]
+        M, D, dep_at, ero_at = self.exchange_step(self.M[ys, xs], self.D[ys, xs], h, None, None, None, dt64, q, tau=tau)
+        self.M = self.M.copy()
+        self.D = self.D.copy()
+        self.M[ys, xs], self.D[ys, xs] = M, D
+        self.branches["deposited"][ys, xs] += dep_at
+        self.branches["eroded"][ys, xs] += ero_at
 
     @staticmethod
     def concentration(M, h):
@@ -1382,6 +1519,7 @@ class Tracer:
         M1[ys, xs] = out
         self.M = M1
         self._decay(dt64)
+        self._exchange(state, bed, ys, xs, dt64, shared)
         return int(ys.size)
 
 
@@ -1389,15 +1527,18 @@ class TracerSet:
     """A tracer set on the host (hp_tracer_enable_set restated): K Tracers over one state, each with its own M, sources and decay
     rate.  The device forms the face fluxes once for all of them; here every species is a Tracer of its own, which is the contract."""
 
-    def __init__(self, rows, cols, dx, functions, initial=None, decay=None, species=None, dry_threshold=1e-10):
-        said = (([] if species is None else [int(species)]) + ([] if initial is None else [len(initial)]) + ([] if decay is None else [len(decay)]))
+    def __init__(self, rows, cols, dx, functions, initial=None, decay=None, species=None, dry_threshold=1e-10, exchange=None, deposit=None, manning=0.0):
+        """`exchange`: per species a dict of step 7's parameters or None; `deposit`: per species D0 or None; `manning`: the domain's."""
+        said = (([] if species is None else [int(species)]) + ([] if initial is None else [len(initial)]) + ([] if decay is None else [len(decay)]) +
+                ([] if exchange is None else [len(exchange)]) + ([] if deposit is None else [len(deposit)]))
         if not said or len(set(said)) != 1 or not 1 <= said[0] <= Tracer.MAX_SPECIES:
             raise ValueError("species, initial and decay must name one number of species, 1..8")
         self.tracers = []
         for s in range(said[0]):
             try:
                 self.tracers.append(Tracer(rows, cols, dx, functions, initial=None if initial is None else initial[s], dry_threshold=dry_threshold,
-                                           decay=0.0 if decay is None else decay[s]))
+                                           decay=0.0 if decay is None else decay[s], exchange=None if exchange is None else exchange[s],
+                                           deposit=None if deposit is None else deposit[s], manning=manning))
             except ValueError as e:
                 raise ValueError(f"species {s}: {e}") from None
 
@@ -1410,6 +1551,10 @@ class TracerSet:
     @property
     def M(self):
         return np.stack([t.M for t in self.tracers])
+
+    @property
+    def D(self):
+        return np.stack([t.D for t in self.tracers])
 
     @property
     def iterations(self):

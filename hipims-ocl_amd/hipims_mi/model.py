@@ -259,10 +259,14 @@ class Model:
         # A tracer SET: the <tracerSpecies name= decay= source=/> elements with their <tracerSource species=.../>, or `tracers`: [dict(name=,
         # initial=, decay=, sources=[dict(cells=, series=)])]: one run of the water carries them all (hp_tracer_enable_set).  Targets name
         # their species (<dataTarget value="tracer|concentration" species=.../>) and their files carry its name.  Either form, not both.
+        # A species may settle onto the ground and be picked up again (hp_tracer_set_exchange): <tracerSpecies ... settling= tauDeposit=
+        # tauErode= erodibility= deposit="d0.asc"/>, or exchange=dict(settling=, tau_deposit=, tau_erode=, erodibility=) and deposit= (an array,
+        # a raster file or None) in its dict; <dataTarget value="deposit" species=.../> writes its deposit D at every output time.
         species = [dict(t) for t in tracers] if tracers is not None else None
         if species is None and cfg.tracer_species:
             species = [dict(name=t["name"], decay=t["decay"], initial=os.path.join(cfg.source_dir, t["initial"]) if t["initial"] else None,
-                            sources=[s for s in cfg.tracer_sources if s.get("species") == t["name"]]) for t in cfg.tracer_species]
+                            sources=[s for s in cfg.tracer_sources if s.get("species") == t["name"]], exchange=t.get("exchange"),
+                            deposit=os.path.join(cfg.source_dir, t["deposit"]) if t.get("deposit") else None) for t in cfg.tracer_species]
         spec = dict(tracer) if tracer is not None else None
         source = next((src for src in cfg.sources if "tracer" in src[1]), None)
         unnamed = [s for s in cfg.tracer_sources if s.get("species") is None]
@@ -297,12 +301,30 @@ class Model:
             for k, sources in enumerate(self.tracer_set["sources"]):
                 for s in sources:
                     sim.tracer_add_source(s["cells"], s["series"], species=k)
+            # the species that exchange with the bed: an exchange dict (an empty one: the defaults) or a deposit asks for it
+            self.tracer_set["exchange"] = [None] * len(species)
+            for k, t in enumerate(species):
+                if t.get("exchange") is None and t.get("deposit") is None:
+                    continue
+                d0 = t.get("deposit")
+                if d0 is not None:
+                    d0 = frontend.read_raster(d0)[0] if isinstance(d0, (str, os.PathLike)) else np.asarray(d0, dtype=np.float64)
+                    if d0.shape != (self.rows, self.cols):
+                        raise ValueError(f"the deposit raster of species {names[k]!r} is {d0.shape[1]} x {d0.shape[0]} cells, the domain {self.cols} x {self.rows}")
+                q = frontend.Tracer.exchange_params(dict(t.get("exchange") or {}))
+                if not hasattr(sim, "tracer_set_exchange"):
+                    raise NotImplementedError("a species that settles exchanges inside every iteration: it needs an engine with tracer_set_exchange (the HIP engine)")
+                self.tracer_set["exchange"][k] = dict(deposit=d0, **{name: float(v) for name, v in q.items()})
+                sim.tracer_set_exchange(k, deposit=d0, **{name: float(v) for name, v in q.items()})
         target_species = list(getattr(cfg, "target_species", None) or []) + [None] * len(cfg.targets)
         for (what, _), name in zip(cfg.targets, target_species):
             if what in ("tracer", "concentration") and self.tracer_set is not None and name not in self.tracer_set["names"]:
                 raise ValueError(f"a {what} data target of a tracer set must name one of its species ({name!r})")
             if what in ("tracer", "concentration") and self.tracer_set is None and name is not None:
                 raise ValueError(f"a {what} data target names the species {name!r}, and the model has no tracer set")
+            if what == "deposit" and (self.tracer_set is None or name not in self.tracer_set["names"] or
+                                      self.tracer_set["exchange"][self.tracer_set["names"].index(name)] is None):
+                raise ValueError(f"a deposit data target must name a species of the tracer set that exchanges with the bed ({name!r})")
         if self.tracer_set is None and spec is None and (source is not None or cfg.tracer_sources):
             if source is not None and source[0] != "raster":
                 raise ValueError("the tracer data source must be a raster")
@@ -573,7 +595,7 @@ class Model:
             return False
         is_peak = [frontend.peak_value_code(what) is not None for what, _ in self.cfg.targets]
         is_soil = [what == "infiltration" for what, _ in self.cfg.targets]     # the cumulative infiltration F: the engine's own raster
-        is_tracer = [what in ("tracer", "concentration") for what, _ in self.cfg.targets]   # M, or M / h: the engine's own raster
+        is_tracer = [what in ("tracer", "concentration", "deposit") for what, _ in self.cfg.targets]   # M, M / h or D: the engine's own raster
         plain = [what for (what, _), pk, so, tr in zip(self.cfg.targets, is_peak, is_soil, is_tracer) if not pk and not so and not tr]
         if self.device_outputs:                                    # every target in ONE call, rasters only over the host link
             derived = self.sim.derive(plain) if plain else {}
@@ -607,7 +629,10 @@ class Model:
                 arr = self.sim.infiltration_read()
             elif is_tracer[k]:
                 species = (list(getattr(self.cfg, "target_species", None) or []) + [None] * (k + 1))[k] if self.tracer_set is not None else None
-                arr = self.sim.tracer_read() if species is None else self.sim.tracer_read(species=self.tracer_set["names"].index(species))
+                if what == "deposit":
+                    arr = self.sim.tracer_deposit_read(species=self.tracer_set["names"].index(species))
+                else:
+                    arr = self.sim.tracer_read() if species is None else self.sim.tracer_read(species=self.tracer_set["names"].index(species))
                 if what == "concentration":
                     arr = frontend.tracer_concentration(arr, self.sim.download(), self.sim.download_bed() if hasattr(self.sim, "download_bed") else self.bed)
             else:

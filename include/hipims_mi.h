@@ -859,6 +859,58 @@ int hp_tracer_write_species(hp_domain_t* d, uint32_t species, const double* rast
  * of HP_TRACER_MAX_SPECIES doubles); either pointer may be NULL. */
 int hp_tracer_set_info(hp_domain_t* d, uint32_t* species, double* decay);
 
+/* ---- exchange with the bed: a species of a tracer set may settle onto the ground and be picked up again.  A decay rate destroys
+ *      mass; silt, sediment-bound metals and sewage solids do not vanish: they drop out where the water slows, lie on the ground
+ *      and are entrained again by the next flood wave.  A species of a set (hp_tracer_enable_set) can exchange mass with a DEPOSIT
+ *      D: a second fp64 raster per species, in M's units (units * m, mass per unit area), that lies on the ground: it does not move,
+ *      does not decay and is not diluted.  Opt-in per species by hp_tracer_set_exchange; the bed itself does not change.
+ *        7. Exchange, after step 6, for every species with settling > 0 || erodibility > 0, in the same launch
+ *      (csrc/hp_tracer.hpp: tracer_step_set<T, true>, tracer_exchange), ONLY at cells that are not copy cases of step 1 (ring cells,
+ *      dt <= 0, disabled cells, five dry cells: those keep M'' and D).  Everything in fp64 on widened values, by correctly
+ *      rounded add, multiply, divide and compare and the correctly rounded cube root of csrc/hp_crmath.h, never fused, in this order:
+ *          h = (double)Z - (double)bed of the iteration's raw source state (step 3's h); if !(h > 1e-10) nothing happens.
+ *          vx = Qx / h; vy = Qy / h; sp2 = vx*vx + vy*vy;
+ *          n: the Manning value the flux kernel uses for the cell (the uniform value or the array's element), widened;
+ *          nn = n*n; tau = ((9810.0 * nn) * sp2) / hp_cr_cbrt(h);            rho g n^2 |u|^2 / h^(1/3), N/m2
+ *          deposition (Krone) if settling > 0 && M'' > 0 && tau < tau_deposit:
+ *              pd = tau_deposit == +inf ? 1.0 : 1.0 - tau / tau_deposit;  k = (settling * pd) * dt;  r = k / h;
+ *              M3 = M'' / (1.0 + r);  dep = M'' - M3;  D = D + dep;  M = M3;                       implicit Euler, as the decay
+ *          else erosion (Partheniades) if erodibility > 0 && D > 0 && tau > tau_erode:
+ *              ex = tau / tau_erode - 1.0;  ero = (erodibility * ex) * dt;  if (ero > D) ero = D;  D = D - ero;  M = M'' + ero;
+ *      A NaN tau fails both comparisons; tau_erode >= tau_deposit makes the branches exclusive.  M + D of a species changes by
+ *      rounding only in this step: with lambda == 0 a closed domain conserves the sum of M and D.
+ *      THE BITS.  Every plane of M and D equals frontend.TracerSet(exchange=...) in every bit after every iteration, whatever the
+ *      math mode.  A set without an exchanging species, and every other path, queues exactly what it queued before
+ *      (tracer_step_set<T, false>); a single tracer (hp_tracer_enable) keeps tracer_step.
+ *      STORAGE.  D is K planes of cols * rows doubles, allocated by the first successful hp_tracer_set_exchange of the domain;
+ *      planes of species without exchange stay zero and are never touched.  D is updated in place.  hp_tracer_disable and
+ *      hp_domain_destroy free it; hp_domain_upload and hp_boundary_clear do not touch it.
+ *      hp_state_save / hp_state_restore carry D in the tracer's own copy, behind M.  The FIRST hp_tracer_set_exchange of a domain
+ *      counts as a change of the store: a snapshot taken before it is the tracer's stale case (M and D are left as they are, one
+ *      HP_LOG_WARNING).  A later call, for the same or another species, changes parameters (and D's plane if deposit_initial is
+ *      given) only and stales nothing. ---- */
+typedef struct {
+	uint32_t struct_size;
+	uint32_t species;                  /* < K */
+	double   settling;                 /* w_s, m/s: finite, >= 0; 0 = never deposits */
+	double   tau_deposit;              /* tau_cd, N/m2: > 0, +inf allowed (= deposits at any shear, probability 1) */
+	double   tau_erode;                /* tau_ce, N/m2: >= tau_deposit, +inf allowed (= never erodes) */
+	double   erodibility;              /* E, units/(m2 s): finite, >= 0; 0 = never erodes */
+	const double* deposit_initial;     /* cols*rows D0 of the LOCAL array (finite, >= 0) or NULL: zeros on the first call for the domain, keep D on a later one */
+} hp_tracer_exchange_desc_t;
+/* Argument errors -- a NULL desc, a bad struct_size, species >= K, a settling, tau_deposit, tau_erode (also < tau_deposit) or
+ * erodibility outside its range (the message names the field), a negative or non-finite deposit_initial (the message names the first
+ * bad cell) -- are HP_ERR_INVALID before any device call.  HP_ERR_STATE before a tracer exists and between hp_step_begin and
+ * hp_step_end; HP_ERR_UNSUPPORTED on a single tracer from hp_tracer_enable (enable it as a set of one); HP_ERR_HIP if D cannot be
+ * allocated: the domain stays usable without exchange.  The raster is free on return. */
+int hp_tracer_set_exchange(hp_domain_t* d, const hp_tracer_exchange_desc_t* desc);
+/* hp_tracer_read_species / hp_tracer_write_species on the plane of D of species `species`; HP_ERR_STATE while no species exchanges. */
+int hp_tracer_deposit_read (hp_domain_t* d, uint32_t species, double* raster, int64_t row0, int64_t nrows);
+int hp_tracer_deposit_write(hp_domain_t* d, uint32_t species, const double* raster, int64_t row0, int64_t nrows);
+/* Host values, does not block: the number of species with settling > 0 || erodibility > 0, and what was set for each of the K species
+ * into out[0 .. K - 1] (struct_size and species filled in, pointers NULL; a species never set: 0, +inf, +inf, 0); either may be NULL. */
+int hp_tracer_exchange_info(hp_domain_t* d, uint32_t* exchanging_species, hp_tracer_exchange_desc_t out[HP_TRACER_MAX_SPECIES]);
+
 /* ---- time control ---- */
 int hp_set_target_time(hp_domain_t* d, double t);     /* CScheme::setTargetTime -> "Target time (sync)" buffer (:1166-1176) */
 int hp_set_time(hp_domain_t* d, double t);            /* rewrite the "Time" buffer: rollbackSimulation (:1480-1494) */
