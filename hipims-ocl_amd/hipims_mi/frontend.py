@@ -126,6 +126,7 @@ class Configuration:
     tracer_sources: list = field(default_factory=list)  # dict(cells [(x, y)], series [m, 2], species name or None): <tracerSource> elements; the initial M is the "tracer" data source
     tracer_species: list = field(default_factory=list)  # dict(name, decay, initial file or None[, exchange dict, deposit file or None]): <tracerSpecies> elements, the species of a tracer set
     target_species: list = field(default_factory=list)  # per entry of `targets`: the species="..." of a tracer / concentration target, or None
+    target_formats: list = field(default_factory=list)  # per entry of `targets`: the GDAL driver name of its format="..." attribute, upper case (CDomainCartesian.cpp:300)
 
 
 def _params(elem):
@@ -165,7 +166,6 @@ def parse_configuration(xml_path):
     for ds in data.findall("dataSource"):
         cfg.sources.append(((ds.get("type") or "").lower(), [v.strip().lower() for v in (ds.get("value") or "").split(",")],
                             ds.get("source")))
-    cfg.target_formats = []                  # GDAL driver names of the <dataTarget format=...> attributes (CDomainCartesian.cpp:300)
     for dt in data.findall("dataTarget"):
         if dt.get("overview") is not None:   # a block-aggregated overview of the value (no reference counterpart): not a full raster
             cfg.overviews.append(((dt.get("value") or "").lower(), aggregate_name(dt.get("aggregate") or "max"), int(dt.get("overview")),
